@@ -36,6 +36,7 @@ for p in (ROOT, os.path.join(ROOT, "rl-selfplay-mnk_amd")):
 # multi-process GPU work on this pool needs dmabuf IPC; must be in the environment before HIP initialises
 os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
+import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (/opt/skills/guides/MI355X_MICROARCH.md)
@@ -107,7 +108,14 @@ def parse():
     ap.add_argument("--allow-fallback", action="store_true",
                     help="if the C-ABI RCCL communicator (mnk_comm_*) cannot be created, run the same all-gather through "
                          "torch.distributed instead of exiting non-zero")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed launch returned to its caller (its packed "
+                         "records, the rollout statistics and the env state it left) as DIR/<name>.npy, float64, at "
+                         "most 64 MB in all (a fixed, seeded sample of envs when the records are larger): two builds run "
+                         "with the same arguments can be compared output for output")
     args = ap.parse_args()
+    if args.dump_outputs is not None and args.mode != "rollout":
+        ap.error("--dump-outputs dumps the flagship workload (--mode rollout)")
     if args.exchange_every < 1:
         ap.error("--exchange-every must be at least 1")
     if args.exchange_every > 1 and any(v % args.exchange_every for v in (args.steps, args.warmup, args.settle)):
@@ -641,8 +649,47 @@ def replay_rate(env, roll, chunk, reps=8):
     return reps * chunk * env.num_envs / (time.perf_counter() - t0)
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs: the whole dump stays below this
+DUMP_SAMPLE_SEED = 1234  # the envs of a sampled dump
+
+
+def _u64_halves(t: torch.Tensor):
+    """int64 words (u64 bits) as two float64 arrays of their low and high 32 bits (exact)"""
+    w = t.detach().cpu().numpy().view(np.uint64)
+    return (w & np.uint64(0xFFFFFFFF)).astype(np.float64), (w >> np.uint64(32)).astype(np.float64)
+
+
+def dump_outputs(path, rec, roll):
+    """--dump-outputs: what the last timed launch of mnk_rollout_random handed its caller, as float64 .npy files --
+    the packed records of its plies (u64 planes split into 32-bit halves, u32 meta words), the rollout statistics and
+    the env state after the launch (planes, meta).  When the records of all envs exceed the budget, the same fixed,
+    seeded sample of envs is taken in every run (records_env_ids)."""
+    os.makedirs(path, exist_ok=True)
+    env = roll.env
+    if rec.meta.is_cuda:
+        torch.cuda.synchronize(rec.meta.device)
+    nenv = rec.meta.shape[1]
+    arrays = {"rollout_stats": roll.stats.cpu().numpy().astype(np.float64),
+              "env_meta": env._meta.cpu().numpy().view(np.uint32).astype(np.float64)}
+    arrays["env_planes_lo"], arrays["env_planes_hi"] = _u64_halves(env._planes)
+    per_env = 8 * (2 * rec.planes.shape[0] * rec.planes.shape[1] + rec.meta.shape[0] + 1)  # float64 bytes of one env's records
+    room = DUMP_BYTES - sum(a.nbytes for a in arrays.values()) - 4096 * len(arrays) - 4 * 4096
+    if room < per_env * nenv:
+        if room < per_env:
+            raise SystemExit(f"--dump-outputs: the env state alone takes the {DUMP_BYTES >> 20} MB budget")
+        ids = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nenv, room // per_env, replace=False))
+    else:
+        ids = np.arange(nenv)
+    sel = torch.from_numpy(ids).to(rec.meta.device)
+    arrays["records_planes_lo"], arrays["records_planes_hi"] = _u64_halves(rec.planes.index_select(2, sel))
+    arrays["records_meta"] = rec.meta.index_select(1, sel).cpu().numpy().view(np.uint32).astype(np.float64)
+    arrays["records_env_ids"] = ids.astype(np.float64)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def selfplay_mode(args):
-    print(json.dumps(selfplay_config3(args, min(args.steps * 4, 256), 64)), flush=True)
+    print(json.dumps(selfplay_config3(args, args.steps, args.warmup)), flush=True)
 
 
 def selfplay_config3(args, steps, warm):
@@ -919,6 +966,7 @@ def main():
     groups = [{}, {}]   # --gather actions: per slot, state pattern of a group -> LogGroup (send + gathered buffers)
     rec_groups = None   # --gather records: per slot (planes [J, T, R, N], meta [J, T, N], gathered planes, gathered meta)
     chunk_no = [0]  # chunks played so far (keyframes are counted from the first chunk of the run)
+    last_out = [None]  # the records the latest launch wrote (--dump-outputs)
 
     def is_keyframe(c):
         return keyframe == 1 or (keyframe > 1 and c % keyframe == 0)
@@ -1015,6 +1063,7 @@ def main():
                 ks, ke = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ks.record(main_stream)
             roll.run(chunk, out=out)
+            last_out[0] = out
             if timing[0] and mode != "none":
                 ke.record(main_stream)
                 kernel_events.append((ks, ke))
@@ -1098,6 +1147,8 @@ def main():
     assert launches == args.steps
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs is not None and rank == 0:  # (outside the timed region; the repetitions overwrite the records)
+        dump_outputs(args.dump_outputs, last_out[0], roll)
     # time spent in the rollout kernel (HIP events on the stream it is launched on)
     dev_ms = sum(a.elapsed_time(b) for a, b in kernel_events) if kernel_events else region0.elapsed_time(region1)
     if multi:

@@ -9,9 +9,9 @@ and every output after *every* operation, bit for bit:
   * ``TorchSelfPlayWrapper`` vs ``OracleSelfPlay``  (random and deterministic
     opponents, fixed and drawn sides) under the same ``torch.manual_seed``.
 
-The reference tree never travels to the GPU box, so nothing here is imported by
-the GPU tests; ``tests/test_oracle_golden.py`` runs it (fixed cases + a hypothesis property test) when the tree is present and
-the golden fixtures cover the rest.
+The reference tree is not part of the repository: ``tests/golden/make_golden_pin.py`` records the
+reference's traces of the cases below as digests (``tests/golden/pin_traces.npz``), and
+``tests/test_oracle_golden.py`` compares the oracle's traces with them.
 
 Usage:  python -m oracle.pin_against_reference     (or: python oracle/pin_against_reference.py)
 """
@@ -61,27 +61,24 @@ def _same(a: torch.Tensor, b: torch.Tensor, what: str):
         raise AssertionError(f"oracle differs from reference: {what}")
 
 
-def _same_env(ref, ora, what: str):
-    _same(ref.boards, ora.boards, what + " boards")
-    _same(ref.current_player, ora.current_player, what + " current_player")
-    _same(ref.move_counts, ora.move_counts, what + " move_counts")
-
-
-def _same_obs(a, b, what: str):
-    _same(a["observation"], b["observation"], what + " observation")
-    _same(a["action_mask"], b["action_mask"], what + " action_mask")
-
-
-def check_env(m, n, k, nenv, steps, seed, illegal_rate=0.15, subset_rate=0.5):
-    RefEnv, _, _ = import_reference()
-    from oracle.env_torch import OracleVectorEnv
-
+def env_trace(make_env, m, n, k, nenv, steps, seed, illegal_rate=0.15, subset_rate=0.5):
+    """(what, tensor) after every operation of a randomized trace of ``make_env(m, n, k, nenv)``: reset, step /
+    step_subset with legal, illegal and negative actions, partial resets; the actions come from a seeded generator and
+    the env's own legal mask, so two envs that agree on every output are driven through the same trace."""
     g = torch.Generator().manual_seed(seed)
-    ref, ora = RefEnv(m, n, k, nenv, device="cpu"), OracleVectorEnv(m, n, k, nenv)
-    _same_obs(ref.reset(), ora.reset(), "reset")
+    env = make_env(m, n, k, nenv)
+
+    def obs(o, what):
+        return [(what + " observation", o["observation"]), (what + " action_mask", o["action_mask"])]
+
+    def state(what):
+        return [(what + " boards", env.boards.clone()), (what + " current_player", env.current_player.clone()),
+                (what + " move_counts", env.move_counts.clone())]
+
+    out = obs(env.reset(), "reset")
     c = m * n
     for t in range(steps):
-        mask = ref.observe()["action_mask"]
+        mask = env.observe()["action_mask"]
         weights = mask.float() + 1e-6
         legal = torch.multinomial(weights, 1, generator=g).squeeze(1)
         anycell = torch.randint(-c, c, (nenv,), generator=g)  # includes negatives: torch wraps them
@@ -91,57 +88,113 @@ def check_env(m, n, k, nenv, steps, seed, illegal_rate=0.15, subset_rate=0.5):
         # (the reference cannot step an empty subset -- view(0, -1) raises -- and none of its callers does)
         if torch.rand((), generator=g) < subset_rate and bool(keep.any()):
             idx = torch.nonzero(keep).squeeze(1)
-            o1, r1, d1 = ref.step_subset(acts[idx], idx)
-            o2, r2, d2 = ora.step_subset(acts[idx], idx)
+            o, r, d = env.step_subset(acts[idx], idx)
         else:
-            o1, r1, d1 = ref.step(acts)
-            o2, r2, d2 = ora.step(acts)
-        _same_obs(o1, o2, f"step {t}")
-        _same(r1, r2, f"step {t} rewards")
-        _same(d1, d2, f"step {t} dones")
-        _same_env(ref, ora, f"step {t}")
+            o, r, d = env.step(acts)
+        out += obs(o, f"step {t}") + [(f"step {t} rewards", r), (f"step {t} dones", d)] + state(f"step {t}")
         # reset most finished envs, leave some finished ones running (they keep toggling / counting)
-        fin = d1 & (torch.rand(nenv, generator=g) < 0.8)
+        fin = d & (torch.rand(nenv, generator=g) < 0.8)
         if t % 7 == 3:
             fin = torch.zeros_like(fin)  # also exercises reset(empty index list)
         ridx = torch.nonzero(fin).squeeze(1)
-        _same_obs(ref.reset(ridx), ora.reset(ridx), f"reset {t}")
-        _same_env(ref, ora, f"reset {t}")
+        out += obs(env.reset(ridx), f"reset {t}") + state(f"reset {t}")
+    return out
+
+
+def selfplay_trace(make_env, make_wrap, make_opp, m, n, k, nenv, steps, seed, fixed_sides=None):
+    """(what, tensor) after every step of a self-play trace: ``make_wrap(env)`` against ``make_opp()``, the agent the
+    oracle's random policy, everything drawn from torch's global generator under ``torch.manual_seed(seed)``."""
+    from oracle.policies import OracleRandomPolicy
+
+    torch.manual_seed(seed)
+    env = make_env(m, n, k, nenv)
+    wrap = make_wrap(env)
+    wrap.set_opponent(make_opp())
+    agent = OracleRandomPolicy(m * n)
+    obs, _ = wrap.reset(options=None if fixed_sides is None else {"agent_side": fixed_sides})
+    out = [("reset observation", obs["observation"]), ("reset action_mask", obs["action_mask"]),
+           ("reset agent_side", wrap.agent_side.clone()), ("reset boards", env.boards.clone()),
+           ("reset current_player", env.current_player.clone())]
+    for t in range(steps):
+        act = agent.act(obs)
+        obs, rew, term, trunc, info = wrap.step(act)
+        assert info == {}
+        out += [(f"selfplay {t} observation", obs["observation"]), (f"selfplay {t} action_mask", obs["action_mask"]),
+                (f"selfplay {t} rewards", rew), (f"selfplay {t} terminated", term), (f"selfplay {t} truncated", trunc),
+                (f"selfplay {t} agent_side", wrap.agent_side.clone()),
+                (f"selfplay {t} pending_resets", wrap.pending_resets.clone()), (f"selfplay {t} boards", env.boards.clone()),
+                (f"selfplay {t} current_player", env.current_player.clone()),
+                (f"selfplay {t} move_counts", env.move_counts.clone())]
+    return out
+
+
+def _opponent_factory(opponent, m, n, is_ref):
+    from oracle.policies import HighestLegalPolicy, LowestLegalPolicy, MaskHashPolicy, OracleRandomPolicy
+
+    if opponent == "random":
+        if is_ref:
+            _, _, RefRandom = import_reference()
+            return lambda: RefRandom(m * n)
+        return lambda: OracleRandomPolicy(m * n)
+    return {"lowest": LowestLegalPolicy, "highest": HighestLegalPolicy, "hash": MaskHashPolicy}[opponent]
+
+
+def oracle_env_trace(m, n, k, nenv, steps, seed, **kw):
+    from oracle.env_torch import OracleVectorEnv
+
+    return env_trace(OracleVectorEnv, m, n, k, nenv, steps, seed, **kw)
+
+
+def reference_env_trace(m, n, k, nenv, steps, seed, **kw):
+    RefEnv, _, _ = import_reference()
+    return env_trace(lambda *g: RefEnv(*g, device="cpu"), m, n, k, nenv, steps, seed, **kw)
+
+
+def oracle_selfplay_trace(m, n, k, nenv, steps, seed, opponent="random", fixed_sides=None):
+    from oracle.env_torch import OracleVectorEnv
+    from oracle.selfplay_torch import OracleSelfPlay
+
+    return selfplay_trace(OracleVectorEnv, OracleSelfPlay, _opponent_factory(opponent, m, n, False), m, n, k, nenv,
+                          steps, seed, fixed_sides)
+
+
+def reference_selfplay_trace(m, n, k, nenv, steps, seed, opponent="random", fixed_sides=None):
+    RefEnv, RefWrap, _ = import_reference()
+    return selfplay_trace(lambda *g: RefEnv(*g, device="cpu"), RefWrap, _opponent_factory(opponent, m, n, True), m, n,
+                          k, nenv, steps, seed, fixed_sides)
+
+
+def _same_trace(ref, ora):
+    if len(ref) != len(ora):
+        raise AssertionError(f"oracle differs from reference: {len(ora)} trace entries, reference {len(ref)}")
+    for (what, a), (_, b) in zip(ref, ora):
+        _same(a, b, what)
+
+
+def trace_digests(trace):
+    """one 64-bit digest per trace entry (dtype, shape and bytes of the tensor): a reference trace stored as data"""
+    import hashlib
+
+    import numpy as np
+
+    out = []
+    for _, t in trace:
+        t = t.detach().cpu().contiguous()
+        h = hashlib.blake2b(f"{t.dtype}{tuple(t.shape)}".encode(), digest_size=8)
+        h.update(t.numpy().tobytes())
+        out.append(int.from_bytes(h.digest(), "little"))
+    return np.array(out, dtype=np.uint64)
+
+
+def check_env(m, n, k, nenv, steps, seed, illegal_rate=0.15, subset_rate=0.5):
+    kw = dict(illegal_rate=illegal_rate, subset_rate=subset_rate)
+    _same_trace(reference_env_trace(m, n, k, nenv, steps, seed, **kw), oracle_env_trace(m, n, k, nenv, steps, seed, **kw))
     return True
 
 
 def check_selfplay(m, n, k, nenv, steps, seed, opponent="random", fixed_sides=None):
-    RefEnv, RefWrap, RefRandom = import_reference()
-    from oracle.env_torch import OracleVectorEnv
-    from oracle.policies import HighestLegalPolicy, LowestLegalPolicy, MaskHashPolicy, OracleRandomPolicy
-    from oracle.selfplay_torch import OracleSelfPlay
-
-    def make_opp(is_ref):
-        if opponent == "random":
-            return RefRandom(m * n) if is_ref else OracleRandomPolicy(m * n)
-        return {"lowest": LowestLegalPolicy, "highest": HighestLegalPolicy, "hash": MaskHashPolicy}[opponent]()
-
-    outs = []
-    for is_ref in (True, False):
-        torch.manual_seed(seed)
-        env = RefEnv(m, n, k, nenv, device="cpu") if is_ref else OracleVectorEnv(m, n, k, nenv)
-        wrap = RefWrap(env) if is_ref else OracleSelfPlay(env)
-        wrap.set_opponent(make_opp(is_ref))
-        agent = OracleRandomPolicy(m * n)
-        trace = []
-        obs, _ = wrap.reset(options=None if fixed_sides is None else {"agent_side": fixed_sides})
-        trace.append((obs, wrap.agent_side.clone(), env.boards.clone(), env.current_player.clone()))
-        for _ in range(steps):
-            act = agent.act(obs)
-            obs, rew, term, trunc, info = wrap.step(act)
-            assert info == {}
-            trace.append((obs, rew, term, trunc, wrap.agent_side.clone(), wrap.pending_resets.clone(),
-                          env.boards.clone(), env.current_player.clone(), env.move_counts.clone()))
-        outs.append(trace)
-    for t, (a, b) in enumerate(zip(*outs)):
-        _same_obs(a[0], b[0], f"selfplay {t}")
-        for j, (x, y) in enumerate(zip(a[1:], b[1:])):
-            _same(x, y, f"selfplay {t} field {j}")
+    _same_trace(reference_selfplay_trace(m, n, k, nenv, steps, seed, opponent, fixed_sides),
+                oracle_selfplay_trace(m, n, k, nenv, steps, seed, opponent, fixed_sides))
     return True
 
 

@@ -1,5 +1,5 @@
-"""CPU: the oracle against the golden vectors made from the imported reference,
-and (when the reference tree is mounted) against the reference itself."""
+"""CPU: the oracle against the golden vectors made from the imported reference, and against the reference's own
+randomized traces stored as digests (tests/golden/pin_traces.npz)."""
 import numpy as np
 import pytest
 import torch
@@ -7,7 +7,8 @@ import torch
 from oracle import philox
 from oracle.env_torch import OracleVectorEnv
 from oracle.packing import pack_boards, pack_cells, unpack_boards, unpack_cells, valid_cell_words, words_per_plane
-from oracle.pin_against_reference import ENV_CASES, SELFPLAY_CASES, check_env, check_selfplay, reference_available
+from oracle.pin_against_reference import (ENV_CASES, SELFPLAY_CASES, oracle_env_trace, oracle_selfplay_trace,
+                                          trace_digests)
 from oracle.policies import HighestLegalPolicy, LowestLegalPolicy, MaskHashPolicy
 from oracle.selfplay_torch import OracleSelfPlay
 from replay import golden_files, play_scenario, replay_env_log, replay_selfplay_trace
@@ -135,16 +136,24 @@ def test_pick_legal_is_uniform_and_legal():
     assert counts.sum() == 60000 and np.all(np.abs(counts - 20000) < 600)
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference tree not mounted (GPU box)")
+def _same_as_reference(trace, want, what):
+    """the oracle's trace against the reference's, stored as one digest per entry (tests/golden/make_golden_pin.py)"""
+    got = trace_digests(trace)
+    assert len(got) == len(want), f"{what}: {len(got)} trace entries, the reference's trace has {len(want)}"
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, f"{what}: oracle differs from reference first at '{trace[bad[0]][0]}' ({bad.size} entries differ)"
+
+
 @pytest.mark.parametrize("case", ENV_CASES[:5])
-def test_oracle_env_equals_reference(case):
-    assert check_env(*case)
+def test_oracle_env_equals_reference(golden_dir, case):
+    want = np.load(f"{golden_dir}/pin_traces.npz")[f"env_{ENV_CASES.index(case)}"]
+    _same_as_reference(oracle_env_trace(*case), want, f"env {case}")
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference tree not mounted (GPU box)")
 @pytest.mark.parametrize("case", SELFPLAY_CASES[:6])
-def test_oracle_selfplay_equals_reference(case):
-    assert check_selfplay(*case)
+def test_oracle_selfplay_equals_reference(golden_dir, case):
+    want = np.load(f"{golden_dir}/pin_traces.npz")[f"selfplay_{SELFPLAY_CASES.index(case)}"]
+    _same_as_reference(oracle_selfplay_trace(*case), want, f"selfplay {case}")
 
 
 def test_oracle_canonical_view_of_policy_fixture(golden_dir):
@@ -163,18 +172,14 @@ def test_oracle_canonical_view_of_policy_fixture(golden_dir):
     assert np.isfinite(g["logp"]).sum(axis=1).tolist() == obs["action_mask"].sum(dim=1).tolist()
 
 
-@pytest.mark.skipif(not reference_available(), reason="reference tree not mounted (GPU box)")
-def test_oracle_equals_reference_on_random_geometries():
-    """Property test: random board shapes, batch sizes and seeds; oracle == imported
-    reference after every operation, env and wrapper."""
-    from hypothesis import HealthCheck, given, settings, strategies as st
-
-    @settings(max_examples=12, deadline=None, suppress_health_check=list(HealthCheck), derandomize=True)
-    @given(m=st.integers(2, 12), n=st.integers(2, 12), kk=st.integers(1, 6), nenv=st.integers(1, 24),
-           seed=st.integers(0, 10 ** 6))
-    def run(m, n, kk, nenv, seed):
-        k = min(kk, m, n)
-        assert check_env(m, n, k, nenv, 3 * max(m, n), seed)
-        assert check_selfplay(m, n, k, nenv, 2 * max(m, n), seed, "random" if seed % 2 else "hash", None)
-
-    run()
+def test_oracle_equals_reference_on_random_geometries(golden_dir):
+    """Property test: random board shapes, batch sizes and seeds, drawn once and recorded with
+    the reference's traces; oracle == reference after every operation, env and wrapper."""
+    g = np.load(f"{golden_dir}/pin_traces.npz")
+    cases = g["random_cases"]
+    assert len(cases) >= 12
+    for j, (m, n, k, nenv, seed) in enumerate(cases.tolist()):
+        _same_as_reference(oracle_env_trace(m, n, k, nenv, 3 * max(m, n), seed), g[f"random_env_{j}"],
+                           f"env {(m, n, k, nenv, seed)}")
+        _same_as_reference(oracle_selfplay_trace(m, n, k, nenv, 2 * max(m, n), seed, "random" if seed % 2 else "hash"),
+                           g[f"random_selfplay_{j}"], f"selfplay {(m, n, k, nenv, seed)}")
