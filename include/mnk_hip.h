@@ -286,6 +286,40 @@ int mnk_selfplay_step_random_logits(uint64_t* planes, uint32_t* meta, int64_t N,
                                     int32_t* err, float* ep_return, int32_t* ep_length, int64_t* ep_stats, uint32_t flags,
                                     void* stream);
 
+/* ---- the one-ply tactical player: a fixed-strength opponent (take a win, else block one, else play at random).
+ * For the side to move, with C = m*n cells in action order: W = the legal cells where its stone leaves a run of >= k of
+ * its stones through that cell (the win test of env/torch_vector_mnk_env.py:106-119 after that ply: an overline counts),
+ * B = the same for the other side (where it would win next ply); S = W if W is not empty, else B if that is not empty,
+ * else the legal cells (all C cells on a full board).  The move is the r-th cell of S in action order, r = mulhi32(x, |S|)
+ * for one Philox u32 x -- oracle/philox.py pick_legal over the mask of S; deterministic: r = 0.  Where neither side can
+ * complete a run S is the legal set, so the move equals the uniformly random one drawn from the same x.
+ * mnk_selfplay_step_tactical: the arguments of mnk_selfplay_step_random, the same step in ONE launch with this player as
+ * the opponent, drawing x = Philox(seed, env_id0 + i, step [+ *step_dev], MNK_STREAM_OPP) -- the random opponent's u32. */
+int mnk_selfplay_step_tactical(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                               const int64_t* actions, uint8_t* pending, int64_t* agent_side,
+                               const int64_t* forced_side, uint64_t seed, uint64_t step, const uint64_t* step_dev,
+                               int64_t env_id0, float* rewards, uint8_t* terminated, void* obs, int obs_dtype,
+                               uint8_t* legal_mask, uint64_t* packed_obs,
+                               int32_t* err, float* ep_return, int32_t* ep_length, int64_t* ep_stats,
+                               uint32_t flags, void* stream);
+/* the same with the agent's masked draw folded in: the arguments of mnk_selfplay_step_random_logits */
+int mnk_selfplay_step_tactical_logits(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, const void* logits,
+                                      int logits_dtype, const uint8_t* mask, uint64_t sample_seed,
+                                      const uint64_t* sample_seed_dev, uint64_t sample_step, const uint64_t* sample_step_dev,
+                                      int64_t sample_env_id0, int deterministic, int64_t* actions, float* logp,
+                                      uint8_t* pending, int64_t* agent_side, const int64_t* forced_side, uint64_t seed,
+                                      uint64_t step, const uint64_t* step_dev, int64_t env_id0, float* rewards,
+                                      uint8_t* terminated, void* obs, int obs_dtype, uint8_t* legal_mask, uint64_t* packed_obs,
+                                      int32_t* err, float* ep_return, int32_t* ep_length, int64_t* ep_stats, uint32_t flags,
+                                      void* stream);
+/* The player as a policy (selfplay.policy.TacticalPolicy.act): obs = a canonical view [N][2][m][n] of element type
+ * `obs_dtype` (channel 0 = the side to move; a cell is a stone when its element is non-zero); row i draws with
+ * x = Philox(seed, env_id0 + i, step [+ *step_dev], MNK_STREAM_SAMPLE), seed_dev (optional) REPLACES seed.  actions
+ * int64[N]; candidates (optional, NULL = off) u8[N][C] = the mask of S -- a threat map for features, too. */
+int mnk_sample_tactical(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, uint64_t seed,
+                        const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                        int deterministic, int64_t* actions, uint8_t* candidates, void* stream);
+
 /* ---- the random-policy rollout of BASELINE.json (RandomPolicy.act -> env.step -> env.reset(done)),
  * T plies per env in one launch with the state held in registers.
  * rec_planes u64[T][R][N]: the position BEFORE each ply (record rows, see the top of this file);
@@ -336,7 +370,10 @@ const char* mnk_jit_last_error(void);
 #define MNK_JIT_API_SP_STEP 9         /* mnk_selfplay_step_random */
 #define MNK_JIT_API_SP_DRAW 10        /* + 3 * logits form (0 f32, 1 bf16, 2 none) + (0 pre, 1 post, 2 step_random):
                                          mnk_selfplay_pre_logits / _post_logits / _step_random_logits */
-#define MNK_JIT_API_COUNT 19
+#define MNK_JIT_API_SP_TACTICAL 19      /* mnk_selfplay_step_tactical */
+#define MNK_JIT_API_SP_TACTICAL_DRAW 20 /* + logits form (0 f32, 1 bf16, 2 none): mnk_selfplay_step_tactical_logits */
+#define MNK_JIT_API_SAMPLE_TACTICAL 23  /* mnk_sample_tactical */
+#define MNK_JIT_API_COUNT 24
 /* compiles only (no GPU needed): code object bytes, or a negative status with the log in mnk_jit_last_error() */
 int64_t mnk_jit_compile_api(int m, int n, int k, int kind);
 /* compiles and loads, on the current device, the variants named by the bits of `kinds` NOW (kinds == 0: of every kernel

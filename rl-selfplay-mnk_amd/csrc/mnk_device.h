@@ -88,6 +88,20 @@ __device__ __forceinline__ void bs_shr(uint32_t (&x)[NW], int s) {
   }
 }
 
+// x <<= s for a wave-uniform s >= 0; bits shifted past word NW-1 are dropped
+template <int NW>
+__device__ __forceinline__ void bs_shl(uint32_t (&x)[NW], int s) {
+  for (int q = s >> 5; q > 0; --q) {
+#pragma unroll
+    for (int w = NW - 1; w >= 0; --w) x[w] = w > 0 ? x[w - 1] : 0u;
+  }
+  const int r = s & 31;
+  if (r) {
+#pragma unroll
+    for (int w = NW - 1; w >= 0; --w) x[w] = __builtin_amdgcn_alignbit(x[w], w > 0 ? x[w - 1] : 0u, (uint32_t)(32 - r));
+  }
+}
+
 // does the bit string hold k set bits spaced d apart?  log2(k) doubling steps.
 template <int NW>
 __device__ __forceinline__ bool bs_has_run(const uint32_t (&b)[NW], int d, int k) {
@@ -134,6 +148,56 @@ __device__ __forceinline__ bool mnk_plane_wins(const MnkGeom& g, const uint32_t 
   hit |= bs_has_run<NW>(b, n + 2, k);      // diagonals
   hit |= bs_has_run<NW>(b, n, k);          // anti-diagonals
   return hit;
+}
+
+// The cells of `empty` where one more stone of `plane` leaves a run of >= k of its stones through that cell -- the win
+// test of env_play after that ply, for every empty cell at once (an overline counts, as in the reference's "> k - 0.1").
+// Along stride d: R_j = cells whose next j cells along +d are all stones, L_j = the same along -d; a cell completes a
+// run when L_j & R_{k-1-j} holds for some j.  R_j = R_{j-1} & (plane >> j d): the prefixes are shared, so the j-loop
+// below costs 2(k-1) shifts and ~3k AND / OR per stride and word once unrolled (CK known; the compiler merges the
+// repeated prefixes).  Guard-column bits are never stones, so no run wraps a row.  `empty` already carries g.valid.
+template <int NW, int CN, int CK>
+__device__ __forceinline__ void mnk_plane_completions(const MnkGeom& g, const uint32_t (&plane)[NW],
+                                                      const uint32_t (&empty)[NW], uint32_t (&out)[NW]) {
+  const int n = geom_n<CN>(g), k = geom_k<CK>(g);
+  constexpr int UK = CK ? CK : 1;  // the j / i loops unroll when k is known, stay loops when it is not
+  uint32_t acc[NW];
+#pragma unroll
+  for (int w = 0; w < NW; ++w) acc[w] = 0u;
+#pragma unroll
+  for (int dir = 0; dir < 4; ++dir) {
+    const int d = dir == 0 ? 1 : (dir == 1 ? n + 1 : (dir == 2 ? n + 2 : n));  // rows, columns, diagonals, anti-diagonals
+    uint32_t lj[NW];  // L_j, grown one stone per j
+#pragma unroll
+    for (int w = 0; w < NW; ++w) lj[w] = ~0u;
+#pragma unroll UK
+    for (int j = 0; j < k; ++j) {
+      if (j > 0) {
+        uint32_t t[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) t[w] = plane[w];
+        bs_shl<NW>(t, j * d);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) lj[w] &= t[w];
+      }
+      uint32_t rj[NW];  // R_{k-1-j}
+#pragma unroll
+      for (int w = 0; w < NW; ++w) rj[w] = ~0u;
+#pragma unroll UK
+      for (int i = 1; i < k - j; ++i) {
+        uint32_t t[NW];
+#pragma unroll
+        for (int w = 0; w < NW; ++w) t[w] = plane[w];
+        bs_shr<NW>(t, i * d);
+#pragma unroll
+        for (int w = 0; w < NW; ++w) rj[w] &= t[w];
+      }
+#pragma unroll
+      for (int w = 0; w < NW; ++w) acc[w] |= lj[w] & rj[w];
+    }
+  }
+#pragma unroll
+  for (int w = 0; w < NW; ++w) out[w] = acc[w] & empty[w];
 }
 
 // position of the r-th (0-based) set bit of x; r < popcount(x).
@@ -344,19 +408,61 @@ __device__ __forceinline__ void env_legal(const MnkGeom& g, const MnkEnv<NW>& e,
   for (int w = 0; w < NW; ++w) legal[w] = ~(e.p[0][w] | e.p[1][w]) & g.valid[w];
 }
 
+// the r-th cell of `set` in action order with r = mulhi32(x, |set|) (oracle/philox.py pick_legal over the set's mask).
+// An empty set draws over all C cells like RandomPolicy's 1e-8 guard (policy.py:21-24): `set` is replaced by the
+// valid-cell string, whose r-th set bit is cell r -- on return `set` holds what was drawn from.
+template <int NW, int CN>
+__device__ __forceinline__ int bs_pick_cell(const MnkGeom& g, uint32_t (&set)[NW], uint32_t x) {
+  const int nl = bs_popcount<NW>(set);
+#pragma unroll
+  for (int w = 0; w < NW; ++w) set[w] = nl ? set[w] : g.valid[w];
+  const int r = (int)__umulhi(x, (uint32_t)(nl ? nl : g.C));
+  const uint32_t bit = (uint32_t)bs_select<NW>(set, r);
+  return (int)(bit - (CN ? bit / (uint32_t)(CN + 1) : mnk_div(bit, g.magic_stride)));
+}
+
 // uniform legal cell from one u32 (oracle/philox.py pick_legal; selfplay/policy.py:18-29)
 template <int NW, int CN>
 __device__ __forceinline__ int env_pick_legal(const MnkGeom& g, const MnkEnv<NW>& e, uint32_t x) {
   uint32_t legal[NW];
   env_legal<NW>(g, e, legal);
-  const int nl = bs_popcount<NW>(legal);
-  // a full board (nl == 0, poked states only) draws over all C cells like RandomPolicy's 1e-8 guard
-  // (policy.py:21-24): the select then runs over the valid-cell string, whose r-th set bit is cell r
+  // (a full board -- poked states only -- draws over all C cells)
+  return bs_pick_cell<NW, CN>(g, legal, x);
+}
+
+// The candidate set of the one-ply tactical player for the side whose stones are `mine` (the other side's: `theirs`):
+// the legal cells that win now if there are any, else the legal cells where the other side would win next ply, else
+// the legal cells.  (Empty only on a full board; bs_pick_cell then draws over all C cells.)
+template <int NW, int CN, int CK>
+__device__ __forceinline__ void mnk_tactical_set(const MnkGeom& g, const uint32_t (&mine)[NW], const uint32_t (&theirs)[NW],
+                                                 uint32_t (&set)[NW]) {
+  uint32_t legal[NW], win[NW], block[NW];
 #pragma unroll
-  for (int w = 0; w < NW; ++w) legal[w] = nl ? legal[w] : g.valid[w];
-  const int r = (int)__umulhi(x, (uint32_t)(nl ? nl : g.C));
-  const uint32_t bit = (uint32_t)bs_select<NW>(legal, r);
-  return (int)(bit - (CN ? bit / (uint32_t)(CN + 1) : mnk_div(bit, g.magic_stride)));
+  for (int w = 0; w < NW; ++w) legal[w] = ~(mine[w] | theirs[w]) & g.valid[w];
+  mnk_plane_completions<NW, CN, CK>(g, mine, legal, win);
+  mnk_plane_completions<NW, CN, CK>(g, theirs, legal, block);
+  uint32_t any_win = 0, any_block = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    any_win |= win[w];
+    any_block |= block[w];
+  }
+#pragma unroll
+  for (int w = 0; w < NW; ++w) set[w] = any_win ? win[w] : (any_block ? block[w] : legal[w]);
+}
+
+// the tactical reply of the side to move from one u32 (x = 0: the first cell of the set, deterministic=True)
+template <int NW, int CN, int CK>
+__device__ __forceinline__ int env_pick_tactical(const MnkGeom& g, const MnkEnv<NW>& e, uint32_t x) {
+  const uint32_t side = e.meta & 1u;
+  uint32_t mine[NW], theirs[NW], set[NW];
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    mine[w] = side ? e.p[1][w] : e.p[0][w];
+    theirs[w] = side ? e.p[0][w] : e.p[1][w];
+  }
+  mnk_tactical_set<NW, CN, CK>(g, mine, theirs, set);
+  return bs_pick_cell<NW, CN>(g, set, x);
 }
 
 struct MnkPly {

@@ -267,6 +267,9 @@ enum MnkJitApiKind {  // (the public names: MNK_JIT_API_* of include/mnk_hip.h)
   MNK_JK_SP_POST = MNK_JIT_API_SP_POST,
   MNK_JK_SP_STEP = MNK_JIT_API_SP_STEP,
   MNK_JK_SP_DRAW = MNK_JIT_API_SP_DRAW,  // + 3 * lt + which: <NW, CN, CK, Draw<LT, C>>, lt 0 f32 / 1 bf16 / 2 no logits
+  MNK_JK_SP_TACTICAL = MNK_JIT_API_SP_TACTICAL,            // k_selfplay_step_tactical <NW, CN, CK, NoDraw>
+  MNK_JK_SP_TACTICAL_DRAW = MNK_JIT_API_SP_TACTICAL_DRAW,  // + lt: k_selfplay_step_tactical <NW, CN, CK, Draw<LT, C>>
+  MNK_JK_SAMPLE_TACTICAL = MNK_JIT_API_SAMPLE_TACTICAL,    // k_sample_tactical (needs k)
   MNK_JK_COUNT = MNK_JIT_API_COUNT
 };
 inline bool mnk_jit_kind_any_k(int kind) { return kind >= MNK_JK_OBSERVE && kind <= MNK_JK_GATHER_OBS; }

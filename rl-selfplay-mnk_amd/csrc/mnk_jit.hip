@@ -283,11 +283,15 @@ std::string api_kernel_name(const MnkGeom& g, int kind) {
     case MNK_JK_SAMPLE_LEGAL: return "k_sample_legal<" + geo + ">";
     case MNK_JK_UNPACK_RECORDS: return "k_unpack_records<" + geo + ">";
     case MNK_JK_GATHER_OBS: return "k_gather_obs<" + geo + ">";
+    case MNK_JK_SP_TACTICAL: return "k_selfplay_step_tactical<" + geo + ", NoDraw>";
+    case MNK_JK_SAMPLE_TACTICAL: return "k_sample_tactical<" + geo + ">";
     default: break;
   }
   static const char* which[] = {"k_selfplay_pre", "k_selfplay_post", "k_selfplay_step_random"};
   if (kind >= MNK_JK_SP_PRE && kind <= MNK_JK_SP_STEP) return std::string(which[kind - MNK_JK_SP_PRE]) + "<" + geo + ", NoDraw>";
   static const char* lts[] = {"float", "uint16_t", "void"};
+  if (kind >= MNK_JK_SP_TACTICAL_DRAW && kind < MNK_JK_SP_TACTICAL_DRAW + 3)
+    return "k_selfplay_step_tactical<" + geo + ", Draw<" + lts[kind - MNK_JK_SP_TACTICAL_DRAW] + ", " + std::to_string(g.C) + "> >";
   const int d = kind - MNK_JK_SP_DRAW;
   return std::string(which[d % 3]) + "<" + geo + ", Draw<" + lts[d / 3] + ", " + std::to_string(g.C) + "> >";
 }

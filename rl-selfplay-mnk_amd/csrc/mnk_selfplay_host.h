@@ -29,7 +29,7 @@ struct MnkSpArgs {
   uint32_t flags;
 };
 
-enum { MNK_SP_PRE = 0, MNK_SP_POST = 1, MNK_SP_STEP_RANDOM = 2 };
+enum { MNK_SP_PRE = 0, MNK_SP_POST = 1, MNK_SP_STEP_RANDOM = 2, MNK_SP_STEP_TACTICAL = 3 };  // (TACTICAL: step_random's arguments)
 
 // argument checks + MnkSpArgs of the three entry points (shared by their actions and their logits forms)
 inline int mnk_sp_args_pre(MnkSpArgs* a, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, const uint8_t* pending,
@@ -121,9 +121,13 @@ inline void mnk_launch_sp(const MnkSpArgs& a, const int64_t* moves, const MnkSam
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selfplay_post<NW, CN, CK, DRAW>), grid, block, lds, s, a.g, a.planes, a.meta, a.N, moves, sa,
                        a.sp_flags, a.agent_side, a.rewards, a.terminated, a.pending, a.obs, a.obs_dtype, a.mask, a.packed_obs,
                        a.err, a.ep, a.flags, vec_ok, B, span);
-  else
+  else if constexpr (WHICH == MNK_SP_STEP_RANDOM)
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selfplay_step_random<NW, CN, CK, DRAW>), grid, block, lds, s, a.g, a.planes, a.meta, a.N,
                        moves, sa, a.pending, a.agent_side, a.forced_side, a.seed, a.step, a.step_dev, a.env_id0, a.rewards,
+                       a.terminated, a.obs, a.obs_dtype, a.mask, a.packed_obs, a.err, a.ep, a.flags, vec_ok, B, span);
+  else
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(k_selfplay_step_tactical<NW, CN, CK, DRAW>), grid, block, lds, s, a.g, a.planes, a.meta,
+                       a.N, moves, sa, a.pending, a.agent_side, a.forced_side, a.seed, a.step, a.step_dev, a.env_id0, a.rewards,
                        a.terminated, a.obs, a.obs_dtype, a.mask, a.packed_obs, a.err, a.ep, a.flags, vec_ok, B, span);
 }
 
@@ -132,8 +136,10 @@ inline void mnk_launch_sp(const MnkSpArgs& a, const int64_t* moves, const MnkSam
 // ahead-of-time kernel(s).
 template <int WHICH>
 inline bool mnk_launch_sp_jit(const MnkSpArgs& a, const int64_t* moves, const MnkSample& sa, hipStream_t s) {
+  const int lt = !sa.logits ? 2 : (sa.logits_dtype == MNK_LOGITS_BF16 ? 1 : 0);
   int kind = MNK_JK_SP_PRE + WHICH;
-  if (!moves) kind = MNK_JK_SP_DRAW + 3 * (!sa.logits ? 2 : (sa.logits_dtype == MNK_LOGITS_BF16 ? 1 : 0)) + WHICH;
+  if (!moves) kind = MNK_JK_SP_DRAW + 3 * lt + WHICH;
+  if (WHICH == MNK_SP_STEP_TACTICAL) kind = moves ? MNK_JK_SP_TACTICAL : MNK_JK_SP_TACTICAL_DRAW + lt;
   const MnkSpLaunch l = mnk_sp_launch_shape(a);
   const int B = l.B, vec_ok = l.vec_ok;
   const size_t stage = l.emit ? mnk_stage_bytes(a.g.NW, a.g.C, B, a.g.n, mnk_packed_cells(a.g.n, a.g.C)) : 0;
@@ -157,7 +163,7 @@ inline bool mnk_launch_sp_jit(const MnkSpArgs& a, const int64_t* moves, const Mn
     mnk_module_launch(&k_selfplay_post<2, 0, 0, NoDraw>, fn, l.grid, l.block, lds, s, a.g, a.planes, a.meta, a.N, moves, sa,
                       a.sp_flags, a.agent_side, a.rewards, a.terminated, a.pending, a.obs, a.obs_dtype, a.mask, a.packed_obs,
                       a.err, a.ep, a.flags, vec_ok, B, span);
-  else
+  else  // (step_random and step_tactical share one parameter list)
     mnk_module_launch(&k_selfplay_step_random<2, 0, 0, NoDraw>, fn, l.grid, l.block, lds, s, a.g, a.planes, a.meta, a.N,
                       moves, sa, a.pending, a.agent_side, a.forced_side, a.seed, a.step, a.step_dev, a.env_id0, a.rewards,
                       a.terminated, a.obs, a.obs_dtype, a.mask, a.packed_obs, a.err, a.ep, a.flags, vec_ok, B, span);

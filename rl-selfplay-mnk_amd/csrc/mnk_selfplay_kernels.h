@@ -316,3 +316,129 @@ k_selfplay_step_random(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, c
   }
   if (ep.stats) mnk_ep_flush(ep, lds_ep);
 }
+
+// ------------------------------------------------------------------ the same step against the one-ply tactical player
+// (selfplay.policy.TacticalPolicy: take a win, else block one, else play at random -- env_pick_tactical) from the same
+// u32 of stream OPP as the random opponent's.  A sibling of k_selfplay_step_random that differs in the one line that picks
+// the reply: sharing the body through a template parameter or a device function moved the random kernel's generated
+// code (branch layout, scheduling), and that kernel stays exactly as it was.
+template <int NW, int CN, int CK, typename DRAW = NoDraw>
+__global__ void __launch_bounds__(256)
+k_selfplay_step_tactical(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, const int64_t* actions, MnkSample sa,
+                         uint8_t* pending, int64_t* agent_side, const int64_t* forced_side, uint64_t seed,
+                         uint64_t step, const uint64_t* step_dev, int64_t env_id0, float* rewards,
+                         uint8_t* terminated, void* obs, int obs_dtype, uint8_t* legal_mask, uint64_t* packed_obs,
+                         int32_t* err, MnkEpisodes ep, uint32_t flags, int vec_ok, int envs_per_block, int stage_span) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char lds_raw[];
+  if (step_dev) step += *step_dev;
+  __shared__ unsigned int lds_ep[MNK_STATS_COUNTERS];
+  const int B = envs_per_block, NT = blockDim.x, tid = threadIdx.x;
+  const int64_t env0 = (int64_t)blockIdx.x * B;
+  const int64_t i = env0 + tid;
+  const int64_t left = N - env0;
+  const int nb = left < B ? (int)left : B;
+  const bool emit = obs || legal_mask;
+  MnkStage st = mnk_stage_carve(lds_raw, g, B);
+  if (emit) mnk_stage_tables<CN>(st, g, B, tid, NT);
+  if (ep.stats) {
+    if (tid < MNK_STATS_COUNTERS) lds_ep[tid] = 0u;
+    __syncthreads();
+  }
+  const int* drawn = nullptr;
+  if constexpr (DRAW::ON) drawn = mnk_draw_block<DRAW>(sa, lds_raw + stage_span, env0, nb, N, B, tid, NT);
+  if (tid < B && i < N) {
+    MnkEnv<NW> e;
+    env_load<NW>(e, planes, meta, N, g.W, i);
+    int64_t side = agent_side[i];
+    const bool pend = pending[i] != 0;
+    const uint64_t env = (uint64_t)(env_id0 + i);
+    int64_t action;
+    if constexpr (DRAW::ON) action = drawn[tid];
+    else action = actions[i];
+    SpAgent a = sp_agent_half<NW, CN, CK>(g, e, action, pend, side, forced_side, seed, step, env, i, err,
+                                          (flags & MNK_STEP_STRICT) != 0);
+    if (a.need_opp) {
+      const int oa = env_pick_tactical<NW, CN, CK>(g, e, mnk_rand_u32(seed, env, step, MNK_STREAM_OPP));
+      const MnkPly ply = env_play<NW, CN, CK, true>(g, e, oa, false);
+      if (!a.was_reset) {
+        a.reward -= ply.win ? 1.0f : 0.0f;
+        a.term = ply.done;
+      }
+    }
+    env_store<NW>(e, planes, meta, N, g.W, i);
+    if (pend) agent_side[i] = side;
+    rewards[i] = a.reward;
+    terminated[i] = a.term ? 1 : 0;
+    pending[i] = a.term ? 1 : 0;
+    if (ep.stats) mnk_ep_account(ep, i, a.reward, a.term, lds_ep);
+    if (emit) {
+      if (side == 1) mnk_stage_put<NW>(st, g, B, tid, e.p[1], e.p[0], true);
+      else mnk_stage_put<NW>(st, g, B, tid, e.p[0], e.p[1], true);
+    }
+    if (packed_obs) mnk_packed_put<NW>(packed_obs, N, g.W, i, side == 1 ? e.p[1] : e.p[0], side == 1 ? e.p[0] : e.p[1]);
+  }
+  if (emit) {  // (synchronises: the episode counters in LDS are complete after it, too)
+    mnk_write_out<NW, CN, CK>(st, g, B, nb, mnk_obs_slab(obs, obs_dtype, env0, g.C), obs_dtype,
+                                legal_mask ? legal_mask + env0 * g.C : nullptr, vec_ok, tid, NT);
+  } else if (ep.stats) {
+    __syncthreads();
+  }
+  if (ep.stats) mnk_ep_flush(ep, lds_ep);
+}
+
+// ------------------------------------------------------------------ the tactical player as a policy
+// selfplay.policy.TacticalPolicy.act: one lane per row of a canonical observation [N][2][m][n] (channel 0 = the side to
+// move) of any observation dtype -- a cell is a stone when its element is non-zero.  Row i draws with
+// x = Philox(seed, env_id0 + i, step, MNK_STREAM_SAMPLE) (deterministic: x = 0, the first cell of the set);
+// candidates (optional) u8[N][C] = the set drawn from.  The row is read with one element load per cell: a policy call
+// outside the step kernels, not on the one-launch path.
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_sample_tactical(MnkGeom g, const void* obs, int obs_dtype, int64_t N, uint64_t seed, const uint64_t* seed_dev,
+                  uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic, int64_t* actions,
+                  uint8_t* candidates) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N) return;
+  if (step_dev) step += *step_dev;
+  if (seed_dev) seed = *seed_dev;
+  const int n = geom_n<CN>(g), C = g.C, stride = n + 1;
+  const size_t eb = (size_t)mnk_obs_bytes(obs_dtype);
+  const unsigned char* row = (const unsigned char*)obs + (size_t)i * 2 * C * eb;
+  uint32_t p[2][NW];
+#pragma unroll
+  for (int pl = 0; pl < 2; ++pl) {
+    const unsigned char* src = row + (size_t)pl * C * eb;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      uint32_t word = 0u;
+      const uint32_t valid = g.valid[w];
+      for (int b = 0; b < 32; ++b) {  // (not unrolled: a word is built in a scalar, no indexed register array)
+        if (!((valid >> b) & 1u)) continue;
+        const int bit = 32 * w + b;
+        const int cell = bit - bit / stride;
+        uint32_t v;
+        if (obs_dtype == MNK_OBS_F32) v = ((const uint32_t*)src)[cell] << 1;  // (+0.0 and -0.0 are empty)
+        else if (obs_dtype == MNK_OBS_BF16) v = (uint32_t)((const uint16_t*)src)[cell] << 17;
+        else v = src[cell];
+        word |= (v != 0u ? 1u : 0u) << b;
+      }
+      p[pl][w] = word;
+    }
+  }
+  uint32_t set[NW];
+  mnk_tactical_set<NW, CN, CK>(g, p[0], p[1], set);
+  const uint32_t x = deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(env_id0 + i), step, MNK_STREAM_SAMPLE);
+  actions[i] = bs_pick_cell<NW, CN>(g, set, x);
+  if (candidates) {
+    uint8_t* out = candidates + i * C;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const uint32_t valid = g.valid[w], bits = set[w];
+      for (int b = 0; b < 32; ++b) {
+        if (!((valid >> b) & 1u)) continue;
+        const int bit = 32 * w + b;
+        out[bit - bit / stride] = (uint8_t)((bits >> b) & 1u);
+      }
+    }
+  }
+}

@@ -27,7 +27,8 @@ STATS_REPLICAS, STATS_STRIDE, STATS_COUNTERS = 64, 8, 5
 # run-time specialised API kernels (MNK_JIT_API_* of include/mnk_hip.h): bit numbers for jit_prepare()
 (JIT_API_STEP, JIT_API_STEP_DRAW, JIT_API_STEP_SUBSET, JIT_API_OBSERVE, JIT_API_SAMPLE_LEGAL, JIT_API_UNPACK_RECORDS,
  JIT_API_GATHER_OBS, JIT_API_SP_PRE, JIT_API_SP_POST, JIT_API_SP_STEP, JIT_API_SP_DRAW) = range(11)
-JIT_API_COUNT = 19
+JIT_API_SP_TACTICAL, JIT_API_SP_TACTICAL_DRAW, JIT_API_SAMPLE_TACTICAL = 19, 20, 23  # (TACTICAL_DRAW + logits form)
+JIT_API_COUNT = 24
 REC_ACTION_MASK, REC_REWARD_SHIFT, REC_DONE_BIT, REC_SIDE_BIT = 0xFFFF, 16, 24, 25
 
 _vp, _i, _i64, _u64, _u32, _f = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32,
@@ -67,6 +68,15 @@ SIGNATURES = {
     "mnk_selfplay_step_random_logits": [_vp, _vp, _i64, _i, _i, _i] + [_vp, _i, _vp, _u64, _vp, _u64, _vp, _i64, _i, _vp, _vp] +
                                        [_vp, _vp, _vp, _u64, _u64, _vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp,
                                         _u32, _vp],
+    "mnk_selfplay_step_tactical": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _vp, _vp, _u64, _u64, _vp, _i64, _vp, _vp,
+                                   _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _u32, _vp],
+    "mnk_selfplay_step_tactical_logits": [_vp, _vp, _i64, _i, _i, _i] + [_vp, _i, _vp, _u64, _vp, _u64, _vp, _i64, _i, _vp,
+                                                                         _vp] +
+                                         [_vp, _vp, _vp, _u64, _u64, _vp, _i64, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                          _vp, _u32, _vp],
+    # obs, obs dtype, N, m, n, k, then the sampler block (seed, seed_dev, step, step_dev, env_id0, deterministic), actions,
+    # candidates, stream
+    "mnk_sample_tactical": [_vp, _i, _i64, _i, _i, _i, _u64, _vp, _u64, _vp, _i64, _i, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],
     "mnk_action_log_words": [_i, _i],
     "mnk_replay_actions": [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp],
@@ -200,6 +210,12 @@ def jit_api_draw_kind(which: int, logits_dtype=None) -> int:
     step_random; ``logits_dtype`` torch.float32, torch.bfloat16 or None (no logits: uniform over the mask)"""
     lt = 2 if logits_dtype is None else (1 if logits_dtype == torch.bfloat16 else 0)
     return JIT_API_SP_DRAW + 3 * lt + which
+
+
+def jit_api_tactical_draw_kind(logits_dtype=None) -> int:
+    """MNK_JIT_API_* number of the tactical step kernel with the agent's draw folded in (``logits_dtype`` as in
+    ``jit_api_draw_kind``)"""
+    return JIT_API_SP_TACTICAL_DRAW + (2 if logits_dtype is None else (1 if logits_dtype == torch.bfloat16 else 0))
 
 
 def jit_prepare(m: int, n: int, k: int, kinds=None) -> int:

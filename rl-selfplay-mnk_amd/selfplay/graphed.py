@@ -56,8 +56,12 @@ class _CapturedOpponent:
         """point the current opponent's sampler at the device words (call before warm-up / capture); returns the sampler
         (None for policies that draw by themselves) with ``calls`` = 0: the position lives in ``step_dev`` from here on"""
         opp = self.wrapper.opponent_policy
-        # (RandomPolicy folds into the step kernel and draws on the wrapper's own OPP stream: nothing to attach)
-        self.sampler = None if getattr(opp, "fused_uniform_random", False) else getattr(opp, "_sampler", None)
+        # (RandomPolicy and TacticalPolicy fold into the step kernel and draw on the wrapper's own OPP stream: nothing to
+        # attach)
+        from selfplay.policy import folds_tactical
+
+        builtin = getattr(opp, "fused_uniform_random", False) or folds_tactical(opp)
+        self.sampler = None if builtin else getattr(opp, "_sampler", None)
         if self.sampler is not None:
             if self.sampler.step_dev is not self.step_dev:  # first capture with this sampler: take over where it stands
                 self.step_dev.fill_(self.sampler.calls)

@@ -6,6 +6,9 @@
                    (``fused_uniform_random``) and the whole self-play step becomes one launch.
 ``NNPolicy``       the reference's network policy, unchanged in behaviour: the net applies
                    its own mask and ``Categorical`` (policy.py:32-54).
+``TacticalPolicy`` the one-ply tactical player, an opponent of fixed, known strength: take a win, else block one, else
+                   play at random (``mnk_sample_tactical``); as a wrapper opponent it is folded into the one-launch step
+                   (``mnk_selfplay_step_tactical``) like ``RandomPolicy``.
 ``FusedNNPolicy``  same distribution, but mask + softmax + draw run in ``mnk_sample_logits``
                    on the raw logits (the epilogue of cnn.py:69-79 fused with the sample).  As a wrapper opponent it is
                    recognised (``fused_logits``): the wrapper asks it for its logits only and the draw happens INSIDE
@@ -119,6 +122,54 @@ class RandomPolicy(Policy):
         # all logits zero: uniform over the legal cells; deterministic: argmax of the 0/1 weights = first legal
         # cell (policy.py:26-27).  No logits tensor is materialised -- the kernel reads the mask only.
         return self._sampler.draw(None, obs["action_mask"], deterministic)
+
+
+class TacticalPolicy(Policy):
+    """The one-ply tactical player for k-in-a-row (the rule: include/mnk_hip.h, mnk_sample_tactical): a cell that
+    completes its own run of ``k`` if there is one, else a cell where the other side would complete one, else a uniformly
+    random legal cell -- the draw is over the set that applies, in action order, from one Philox u32 per row
+    (``deterministic``: its first cell).  Reads only the observation (channel 0 = the side to move, any of float32 /
+    bfloat16 / uint8; the board size comes from its shape); the mask is not looked at.
+
+    As the opponent of ``TorchSelfPlayWrapper`` the whole step is one launch (``fused_tactical``): the reply is drawn
+    inside the step kernel from the wrapper's own key and stream OPP, like ``RandomPolicy``'s.  A subclass that
+    overrides ``act`` is called as a policy instead."""
+
+    fused_tactical = True  # lets TorchSelfPlayWrapper fold the opponent into its step kernel (only when act is this one)
+
+    def __init__(self, k: int, seed=None):
+        self.k = int(k)
+        self._sampler = _HipSampler(seed)
+
+    def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, candidates=None) -> torch.Tensor:
+        """``candidates``: optional uint8 / bool ``[B, m*n]`` tensor that receives the set each row drew from"""
+        observation = obs["observation"]
+        if observation.dim() == 3:
+            observation = observation.unsqueeze(0)
+        if observation.device.type != "cuda":
+            raise RuntimeError("mnk policies sample on the GPU; got an observation on " + str(observation.device))
+        if observation.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
+            observation = observation.to(torch.float32)
+        observation = observation.contiguous()
+        b, two, m, n = observation.shape
+        if two != 2:
+            raise ValueError(f"expected an observation [B, 2, m, n], got {tuple(observation.shape)}")
+        actions = torch.empty(b, dtype=torch.long, device=observation.device)
+        if candidates is not None and (candidates.shape != (b, m * n) or candidates.dtype not in (torch.uint8, torch.bool)
+                                       or not candidates.is_contiguous() or candidates.device != observation.device):
+            raise ValueError(f"candidates must be a contiguous uint8 / bool ({b}, {m * n}) tensor on {observation.device}")
+        if b:
+            mnk_hip.call("mnk_sample_tactical", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, self.k,
+                         *self._sampler.block(deterministic), mnk_hip.ptr(actions), mnk_hip.ptr(candidates),
+                         mnk_hip.stream_ptr(observation.device))
+        self._sampler.advance()
+        return actions
+
+
+def folds_tactical(policy) -> bool:
+    """does ``policy`` play as the built-in tactical opponent of the one-launch step?  Only a ``TacticalPolicy`` whose
+    ``act`` is not overridden: a subclass that changes the moves goes through pre -> act -> post."""
+    return getattr(policy, "fused_tactical", False) and type(policy).act is TacticalPolicy.act
 
 
 class NNPolicy(Policy):

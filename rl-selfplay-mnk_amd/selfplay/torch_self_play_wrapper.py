@@ -16,7 +16,8 @@ those facts as bits and one step is
     mnk_selfplay_post  opponent ply, zero-sum merge, agent's canonical view (1 launch)
 
 with no host synchronisation; with the built-in ``RandomPolicy`` as opponent the
-three collapse into the single launch ``mnk_selfplay_step_random``.  The masked draws fold into these kernels too
+three collapse into the single launch ``mnk_selfplay_step_random`` (a ``TacticalPolicy`` opponent:
+``mnk_selfplay_step_tactical``).  The masked draws fold into these kernels too
 (SURVEY.md section 7 step 5): a ``FusedNNPolicy`` opponent only runs its network, its mask + softmax + draw happen inside
 ``mnk_selfplay_post_logits``; ``step_logits`` does the same for the agent (``mnk_selfplay_pre_logits`` /
 ``mnk_selfplay_step_random_logits``) -- a network-vs-network agent-step is 2 env-side launches, not 4.
@@ -41,6 +42,7 @@ import torch
 
 import mnk_hip
 from env.constants import PLAYER_BLACK, PLAYER_WHITE  # noqa: F401  (same import as the reference, wrapper:3)
+from selfplay.policy import folds_tactical
 
 
 class TorchSelfPlayWrapper:
@@ -283,17 +285,22 @@ class TorchSelfPlayWrapper:
             return {"observation": obs, "action_mask": mask}, rewards, terminated, self._truncated, {}
 
         geo = (mnk_hip.ptr(env._planes), mnk_hip.ptr(env._meta), n, env.m, env.n, env.k)
-        if getattr(opp, "fused_uniform_random", False):
-            # RandomPolicy opponent: the whole step is one launch (with the agent's draw in it when it comes as logits)
+        tactical = folds_tactical(opp)
+        if tactical and opp.k != env.k:
+            raise ValueError(f"TacticalPolicy(k={opp.k}) as the opponent on a board with k = {env.k}")
+        if getattr(opp, "fused_uniform_random", False) or tactical:
+            # RandomPolicy / TacticalPolicy opponent: the whole step is one launch (with the agent's draw in it when it
+            # comes as logits); both draw the reply from the wrapper's key, stream OPP
             tail = (mnk_hip.ptr(self.pending_resets), mnk_hip.ptr(self.agent_side), mnk_hip.ptr(forced), self.seed, step,
                     mnk_hip.ptr(self.step_dev), self.env_id0, mnk_hip.ptr(rewards), mnk_hip.ptr(terminated),
                     mnk_hip.ptr(obs), mnk_hip.obs_code(obs), mnk_hip.ptr(mask), mnk_hip.ptr(packed), mnk_hip.ptr(env._err),
                     mnk_hip.ptr(self._ep_return), mnk_hip.ptr(self._ep_length), mnk_hip.ptr(self._ep_stats), env._flags(),
                     env._stream())
+            which = "mnk_selfplay_step_tactical" if tactical else "mnk_selfplay_step_random"
             if agent_draw is None:
-                mnk_hip.call("mnk_selfplay_step_random", *geo, mnk_hip.ptr(actions), *tail)
+                mnk_hip.call(which, *geo, mnk_hip.ptr(actions), *tail)
             else:
-                mnk_hip.call("mnk_selfplay_step_random_logits", *geo, *agent_draw, *tail)
+                mnk_hip.call(which + "_logits", *geo, *agent_draw, *tail)
         else:
             if opp is None:
                 raise RuntimeError("TorchSelfPlayWrapper: set_opponent(policy) before reset()/step()")
