@@ -119,6 +119,7 @@ extern "C" {
 #define MNK_STREAM_OPP 1
 #define MNK_STREAM_SIDE 2
 #define MNK_STREAM_SAMPLE 3
+#define MNK_STREAM_PLAYOUT 4 /* the random plies of the Monte Carlo player's playouts (mnk_sample_playouts) */
 
 int mnk_abi_version(void);
 /* Developer knobs (MNK_ROLLOUT_PAIR, MNK_ROLLOUT_FORM, MNK_JIT, MNK_ROLLOUT_SADDR, MNK_EMIT_ENVS, MNK_EMIT_THREADS: A/B
@@ -319,6 +320,29 @@ int mnk_selfplay_step_tactical_logits(uint64_t* planes, uint32_t* meta, int64_t 
 int mnk_sample_tactical(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, uint64_t seed,
                         const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                         int deterministic, int64_t* actions, uint8_t* candidates, void* stream);
+
+/* ---- the flat Monte Carlo player: a fixed-strength opponent whose strength is set by the playout count P.
+ * Row i of obs is a canonical view [N][2][m][n] of element type `obs_dtype` (channel 0 = the side to move, "me"; a cell
+ * is a stone when its element is non-zero, as in mnk_sample_tactical).  L = the legal cells in action order, C = m*n.
+ * For every a in L and j in [0, P) one playout: "me" plays a, then the sides alternate starting with the other side,
+ * each playing a uniformly random legal cell (pick_legal: r = mulhi32(x, |legal|), the r-th legal cell).  The game ends
+ * at the first ply that leaves a run of >= k stones of its mover anywhere on its plane (the env's win test: an overline
+ * counts, a run already on the board counts) or when the board is full; the outcome is a win, a loss or a draw for "me".
+ * Playout j of cell a in row i, on call `step`, draws its t-th random ply (t = 0: the other side's first reply) from
+ *   x = Philox(seed, env_id0 + i, u, MNK_STREAM_PLAYOUT),  u = (((step * C + a) * P + j) * C4) + t,
+ * C4 = C rounded up to a multiple of 4 (one Philox block serves four consecutive plies of a playout).  The counter is keyed
+ * by the global env id: the counts do not depend on the launch layout.  Range: q = u >> 2 must fit in 56 bits, i.e.
+ * (step + 1) * C * P * C4 <= 2^58; a host `step` that breaks it is rejected (*step_dev is added on the device, unchecked).
+ * W[a] = wins, Lo[a] = losses (draws = P - W - Lo), score s[a] = W[a] - Lo[a]; S = the legal cells of maximal score.  The
+ * move is the r-th cell of S in action order, r = mulhi32(x, |S|), x = Philox(seed, env_id0 + i, step [+ *step_dev],
+ * MNK_STREAM_SAMPLE) -- TacticalPolicy's u32; deterministic: r = 0; no legal cell: the draw is over all C cells.  A cell
+ * that wins at once has W = P, Lo = 0 and so always lies in S: the player never misses a win in one ply.
+ * seed_dev (optional) REPLACES seed, step_dev (optional) is ADDED to step.  actions int64[N]; counts (optional, NULL = off)
+ * int32[N][2][C] = W then Lo per cell, 0 on occupied cells.  playouts in [1, 4096].  One launch, one workgroup per row. */
+int mnk_sample_playouts(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int playouts, uint64_t seed,
+                        const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                        int deterministic, int64_t* actions, int32_t* counts, void* stream);
+#define MNK_PLAYOUTS_MAX 4096
 
 /* ---- the random-policy rollout of BASELINE.json (RandomPolicy.act -> env.step -> env.reset(done)),
  * T plies per env in one launch with the state held in registers.

@@ -9,6 +9,9 @@
 ``TacticalPolicy`` the one-ply tactical player, an opponent of fixed, known strength: take a win, else block one, else
                    play at random (``mnk_sample_tactical``); as a wrapper opponent it is folded into the one-launch step
                    (``mnk_selfplay_step_tactical``) like ``RandomPolicy``.
+``MonteCarloPolicy`` the flat Monte Carlo player: for every legal cell P uniformly random playouts to the end of the game,
+                   then a cell of best wins-minus-losses (``mnk_sample_playouts``); strength set by P, no training.  As a
+                   wrapper opponent it goes through pre -> act -> post like any policy.
 ``FusedNNPolicy``  same distribution, but mask + softmax + draw run in ``mnk_sample_logits``
                    on the raw logits (the epilogue of cnn.py:69-79 fused with the sample).  As a wrapper opponent it is
                    recognised (``fused_logits``): the wrapper asks it for its logits only and the draw happens INSIDE
@@ -170,6 +173,57 @@ def folds_tactical(policy) -> bool:
     """does ``policy`` play as the built-in tactical opponent of the one-launch step?  Only a ``TacticalPolicy`` whose
     ``act`` is not overridden: a subclass that changes the moves goes through pre -> act -> post."""
     return getattr(policy, "fused_tactical", False) and type(policy).act is TacticalPolicy.act
+
+
+def _canonical_observation(obs):
+    """the observation of ``obs`` as a contiguous cuda [B, 2, m, n] tensor of float32 / bfloat16 / uint8"""
+    observation = obs["observation"]
+    if observation.dim() == 3:
+        observation = observation.unsqueeze(0)
+    if observation.device.type != "cuda":
+        raise RuntimeError("mnk policies sample on the GPU; got an observation on " + str(observation.device))
+    if observation.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
+        observation = observation.to(torch.float32)
+    observation = observation.contiguous()
+    if observation.dim() != 4 or observation.shape[1] != 2:
+        raise ValueError(f"expected an observation [B, 2, m, n], got {tuple(observation.shape)}")
+    return observation
+
+
+class MonteCarloPolicy(Policy):
+    """The flat Monte Carlo player for k-in-a-row (the rule: include/mnk_hip.h, mnk_sample_playouts): for every legal cell
+    ``playouts`` games are played to the end from that move on, both sides drawing uniformly random legal cells; the move
+    is drawn among the cells of maximal wins-minus-losses, in action order, from one Philox u32 per row (the u32
+    ``TacticalPolicy`` draws; ``deterministic``: the first such cell).  A cell that wins at once scores ``playouts`` and is
+    never missed.  Strength rises with ``playouts`` and needs no training: Random < Tactical < MC(16) < MC(64) < MC(256).
+    Reads only the observation (channel 0 = the side to move, any of float32 / bfloat16 / uint8; the board size comes
+    from its shape).  One launch per call, one workgroup per row.
+
+    As the opponent of ``TorchSelfPlayWrapper`` it is called through pre -> act -> post like any policy; it is not folded
+    into the one-launch step."""
+
+    def __init__(self, k: int, playouts: int = 64, seed=None):
+        self.k = int(k)
+        self.playouts = int(playouts)
+        if not 1 <= self.playouts <= mnk_hip.PLAYOUTS_MAX:
+            raise ValueError(f"playouts must lie in [1, {mnk_hip.PLAYOUTS_MAX}], got {playouts}")
+        self._sampler = _HipSampler(seed)
+
+    def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, counts=None) -> torch.Tensor:
+        """``counts``: optional int32 ``[B, 2, m*n]`` tensor that receives each row's wins (``[:, 0]``) and losses
+        (``[:, 1]``) per cell over its ``playouts`` games (draws = playouts - wins - losses; 0 on occupied cells)"""
+        observation = _canonical_observation(obs)
+        b, _, m, n = observation.shape
+        actions = torch.empty(b, dtype=torch.long, device=observation.device)
+        if counts is not None and (counts.shape != (b, 2, m * n) or counts.dtype != torch.int32
+                                   or not counts.is_contiguous() or counts.device != observation.device):
+            raise ValueError(f"counts must be a contiguous int32 ({b}, 2, {m * n}) tensor on {observation.device}")
+        if b:
+            mnk_hip.call("mnk_sample_playouts", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, self.k,
+                         self.playouts, *self._sampler.block(deterministic), mnk_hip.ptr(actions), mnk_hip.ptr(counts),
+                         mnk_hip.stream_ptr(observation.device))
+        self._sampler.advance()
+        return actions
 
 
 class NNPolicy(Policy):
