@@ -45,11 +45,15 @@ __host__ __device__ inline int mnk_seg_words(int NW, int n) {  // SW: words of o
   return (cw + 1) | 1;
 }
 
-// The boards the ahead-of-time dispatch (MNK_DISPATCH, mnk_host.h) has compile-time geometry for; every other board gets
+// The boards with ahead-of-time compile-time variants, one X(NW, n, k, C) row each: every host dispatch (MNK_DISPATCH and
+// the rollout launchers, mnk_host.h) is derived from this list and tries its rows in this order.  Every other board gets
 // its compile-time variant from hiprtc once it is hot (mnk_jit.hip).
+#define MNK_BUILTIN_BOARDS(X) X(3, 9, 5, 81) X(1, 3, 3, 9) X(6, 13, 5, 169) X(8, 15, 5, 225) X(12, 19, 5, 361)
+
 __host__ __device__ inline bool mnk_geom_builtin(int n, int k, int NW) {
-  return (n == 9 && k == 5 && NW == 3) || (n == 3 && k == 3 && NW == 1) || (n == 13 && k == 5 && NW == 6) ||
-         (n == 15 && k == 5 && NW == 8) || (n == 19 && k == 5 && NW == 12);
+#define MNK_BUILTIN_ROW(NWv, CNv, CKv, Cv) || (n == CNv && k == CKv && NW == NWv)
+  return false MNK_BUILTIN_BOARDS(MNK_BUILTIN_ROW);
+#undef MNK_BUILTIN_ROW
 }
 
 // does a kernel variant with compile-time geometry (CN = n) write out in the packed form on a board of C cells?

@@ -51,8 +51,9 @@ inline int mnk_check_geom(int m, int n, int k, MnkGeom* g) {
 inline int mnk_geom_any_k(int m, int n, MnkGeom* g) {
   int rc = mnk_check_geom(m, n, 1, g);
   if (rc != MNK_OK) return rc;
-  if (n == 3) g->k = 3;
-  if (n == 9 || n == 13 || n == 15 || n == 19) g->k = 5;
+#define MNK_ANY_K_ROW(NWv, CNv, CKv, Cv) if (n == CNv) g->k = CKv;
+  MNK_BUILTIN_BOARDS(MNK_ANY_K_ROW)
+#undef MNK_ANY_K_ROW
   return MNK_OK;
 }
 
@@ -136,45 +137,67 @@ inline int mnk_block_threads(bool writes_obs = true) {
 }
 
 // Kernel variants: NW = u32 register words per plane; CN / CK = compile-time board width and
-// run length (0 = run time).  The boards people actually train on get fully specialised code
-// (immediate shift amounts, unrolled run doubling); everything else takes the generic form.
-#define MNK_CASE(NWv, CNv, CKv, ...)                      \
-  {                                                       \
-    constexpr int NW = NWv, CN = CNv, CK = CKv;           \
-    __VA_ARGS__;                                          \
+// run length (0 = run time).  The boards people actually train on (MNK_BUILTIN_BOARDS, mnk_emit.h) get fully specialised
+// code (immediate shift amounts, unrolled run doubling); everything else takes the generic form.
+template <int NWv, int CNv, int CKv, int Cv>
+struct MnkBoard {  // one row of MNK_BUILTIN_BOARDS as a type
+  static constexpr int NW = NWv, CN = CNv, CK = CKv, C = Cv;
+};
+
+// f(MnkBoard<row>{}) for the row of MNK_BUILTIN_BOARDS that is g's board; f returns whether it launched (false: the row is
+// outside the subset f has variants for).  false when no row is g's board.
+template <typename F>
+inline bool mnk_builtin_board(const MnkGeom& g, F&& f) {
+#define MNK_BOARD_ROW(NWv, CNv, CKv, Cv) \
+  if (g.n == CNv && g.k == CKv && g.NW == NWv) return f(MnkBoard<NWv, CNv, CKv, Cv>{});
+  MNK_BUILTIN_BOARDS(MNK_BOARD_ROW)
+#undef MNK_BOARD_ROW
+  return false;
+}
+
+// __VA_ARGS__ with constexpr NW / CN / CK of g's row of MNK_BUILTIN_BOARDS, if there is one and it satisfies KEEP (a
+// constant expression in the row's type MnkRow_, e.g. MnkRow_::C <= 128); false = nothing launched.  (`if constexpr` in
+// the generic lambda: a row outside KEEP instantiates no kernel.)
+#define MNK_BUILTIN(g, KEEP, ...)                                           \
+  mnk_builtin_board(g, [&](auto row_) {                                     \
+    using MnkRow_ = decltype(row_);                                         \
+    if constexpr (KEEP) {                                                   \
+      constexpr int NW = MnkRow_::NW, CN = MnkRow_::CN, CK = MnkRow_::CK;   \
+      __VA_ARGS__;                                                          \
+    }                                                                       \
+    return bool(KEEP);                                                      \
+  })
+#define MNK_CASE(NWv, CNv, CKv, ...)                              \
+  {                                                               \
+    constexpr int NW = NWv, CN = CNv, CK = CKv;                   \
+    __VA_ARGS__;                                                  \
   }
-#define MNK_DISPATCH(g, ...)                                                          \
-  do {                                                                                \
-    if ((g).n == 9 && (g).k == 5 && (g).NW == 3) MNK_CASE(3, 9, 5, __VA_ARGS__)       \
-    else if ((g).n == 3 && (g).k == 3 && (g).NW == 1) MNK_CASE(1, 3, 3, __VA_ARGS__)  \
-    else if ((g).n == 13 && (g).k == 5 && (g).NW == 6) MNK_CASE(6, 13, 5, __VA_ARGS__) \
-    else if ((g).n == 15 && (g).k == 5 && (g).NW == 8) MNK_CASE(8, 15, 5, __VA_ARGS__) \
-    else if ((g).n == 19 && (g).k == 5 && (g).NW == 12) MNK_CASE(12, 19, 5, __VA_ARGS__) \
-    else if ((g).NW <= 2) MNK_CASE(2, 0, 0, __VA_ARGS__)                              \
-    else if ((g).NW <= 4) MNK_CASE(4, 0, 0, __VA_ARGS__)                              \
-    else if ((g).NW <= 8) MNK_CASE(8, 0, 0, __VA_ARGS__)                              \
-    else if ((g).NW <= 16) MNK_CASE(16, 0, 0, __VA_ARGS__)                            \
-    else MNK_CASE(32, 0, 0, __VA_ARGS__)                                              \
+#define MNK_DISPATCH(g, ...)                                      \
+  do {                                                            \
+    if (MNK_BUILTIN(g, true, __VA_ARGS__)) break;                 \
+    if ((g).NW <= 2) MNK_CASE(2, 0, 0, __VA_ARGS__)               \
+    else if ((g).NW <= 4) MNK_CASE(4, 0, 0, __VA_ARGS__)          \
+    else if ((g).NW <= 8) MNK_CASE(8, 0, 0, __VA_ARGS__)          \
+    else if ((g).NW <= 16) MNK_CASE(16, 0, 0, __VA_ARGS__)        \
+    else MNK_CASE(32, 0, 0, __VA_ARGS__)                          \
   } while (0)
 #define MNK_K(name) HIP_KERNEL_NAME(name<NW, CN, CK>)
 // the variants a board of more than 256 cells can have (MNK_ACT_U8P1, up to 512 cells): 19x19x5 and the generic 16- and
 // 32-word forms
-#define MNK_DISPATCH_LARGE(g, ...)                                                       \
-  do {                                                                                   \
-    if ((g).n == 19 && (g).k == 5 && (g).NW == 12) MNK_CASE(12, 19, 5, __VA_ARGS__)      \
-    else if ((g).NW <= 16) MNK_CASE(16, 0, 0, __VA_ARGS__)                               \
-    else MNK_CASE(32, 0, 0, __VA_ARGS__)                                                 \
+#define MNK_DISPATCH_LARGE(g, ...)                                \
+  do {                                                            \
+    if (MNK_BUILTIN(g, MnkRow_::C > 256, __VA_ARGS__)) break;     \
+    if ((g).NW <= 16) MNK_CASE(16, 0, 0, __VA_ARGS__)             \
+    else MNK_CASE(32, 0, 0, __VA_ARGS__)                          \
   } while (0)
 // the variants a board of at most 128 cells can have (the 7-bit action stream): 9x9x5, 3x3x3, generic up to 8 words
-#define MNK_DISPATCH_SMALL(g, ...)                                                    \
-  do {                                                                                \
-    if ((g).n == 9 && (g).k == 5 && (g).NW == 3) MNK_CASE(3, 9, 5, __VA_ARGS__)       \
-    else if ((g).n == 3 && (g).k == 3 && (g).NW == 1) MNK_CASE(1, 3, 3, __VA_ARGS__)  \
-    else if ((g).NW <= 2) MNK_CASE(2, 0, 0, __VA_ARGS__)                              \
-    else if ((g).NW <= 4) MNK_CASE(4, 0, 0, __VA_ARGS__)                              \
-    else MNK_CASE(8, 0, 0, __VA_ARGS__)                                               \
+#define MNK_DISPATCH_SMALL(g, ...)                                \
+  do {                                                            \
+    if (MNK_BUILTIN(g, MnkRow_::C <= 128, __VA_ARGS__)) break;    \
+    if ((g).NW <= 2) MNK_CASE(2, 0, 0, __VA_ARGS__)               \
+    else if ((g).NW <= 4) MNK_CASE(4, 0, 0, __VA_ARGS__)          \
+    else MNK_CASE(8, 0, 0, __VA_ARGS__)                           \
   } while (0)
-
 
 // may the one-lane rollout address its record stores with 32-bit lane offsets (SADDR form)?  Only while a wave is
 // alone on its SIMD (where it measured faster) and a launch's record rows stay below 4 GiB
@@ -184,7 +207,7 @@ inline bool mnk_rollout_saddr_ok(const MnkGeom& g, int64_t N, int T) {
 }
 
 // is `act` a log format this board can use?  (0 = no log)
-inline bool mnk_act_format_ok(int act, int C) {
+constexpr bool mnk_act_format_ok(int act, int C) {
   return act == 0 || act == MNK_ACT_U16 || (act == MNK_ACT_U8 && C <= 256) || (act == MNK_ACT_BITS7 && C <= 128) ||
          (act == MNK_ACT_U8P1 && C > 256 && C <= 512);  // (9 bits per action; only the boards that need it have kernel variants)
 }
@@ -211,22 +234,18 @@ void mnk_launch_rollout_ws(const MnkGeom& g, int ws, uint64_t* planes, uint32_t*
 // The rollout / replay kernels of boards with more than 16 register words per plane (planes of more than 512 bits) exist
 // as run-time specialisations only: their generic ahead-of-time forms took 20 minutes to compile for kernels nobody's
 // default board runs.  The API-level kernels keep a generic 32-word variant.
-#define MNK_DISPATCH16(g, ...)                                                        \
-  do {                                                                                \
-    if ((g).n == 9 && (g).k == 5 && (g).NW == 3) MNK_CASE(3, 9, 5, __VA_ARGS__)       \
-    else if ((g).n == 3 && (g).k == 3 && (g).NW == 1) MNK_CASE(1, 3, 3, __VA_ARGS__)  \
-    else if ((g).n == 13 && (g).k == 5 && (g).NW == 6) MNK_CASE(6, 13, 5, __VA_ARGS__) \
-    else if ((g).n == 15 && (g).k == 5 && (g).NW == 8) MNK_CASE(8, 15, 5, __VA_ARGS__) \
-    else if ((g).n == 19 && (g).k == 5 && (g).NW == 12) MNK_CASE(12, 19, 5, __VA_ARGS__) \
-    else if ((g).NW <= 2) MNK_CASE(2, 0, 0, __VA_ARGS__)                              \
-    else if ((g).NW <= 4) MNK_CASE(4, 0, 0, __VA_ARGS__)                              \
-    else if ((g).NW <= 8) MNK_CASE(8, 0, 0, __VA_ARGS__)                              \
-    else MNK_CASE(16, 0, 0, __VA_ARGS__)                                              \
+#define MNK_DISPATCH16(g, ...)                                    \
+  do {                                                            \
+    if (MNK_BUILTIN(g, true, __VA_ARGS__)) break;                 \
+    if ((g).NW <= 2) MNK_CASE(2, 0, 0, __VA_ARGS__)               \
+    else if ((g).NW <= 4) MNK_CASE(4, 0, 0, __VA_ARGS__)          \
+    else if ((g).NW <= 8) MNK_CASE(8, 0, 0, __VA_ARGS__)          \
+    else MNK_CASE(16, 0, 0, __VA_ARGS__)                          \
   } while (0)
-#define MNK_DISPATCH16_LARGE(g, ...)                                                     \
-  do {                                                                                   \
-    if ((g).n == 19 && (g).k == 5 && (g).NW == 12) MNK_CASE(12, 19, 5, __VA_ARGS__)      \
-    else MNK_CASE(16, 0, 0, __VA_ARGS__)                                                 \
+#define MNK_DISPATCH16_LARGE(g, ...)                              \
+  do {                                                            \
+    if (MNK_BUILTIN(g, MnkRow_::C > 256, __VA_ARGS__)) break;     \
+    MNK_CASE(16, 0, 0, __VA_ARGS__)                               \
   } while (0)
 hipFunction_t mnk_jit_replay_function(const MnkGeom& g, bool rec, int act);
 hipFunction_t mnk_jit_rollout_pair_function(const MnkGeom& g, bool rec, int act);
@@ -242,7 +261,7 @@ int mnk_jit_launch_rollout(hipFunction_t fn, MnkGeom g, uint64_t* planes, uint32
                            uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
                            void* act_log, void* stream);
 
-// two lanes per env with the board split by words (mnk_rollout_pairw.hip): 19x19x5 and 15x15x5
+// two lanes per env with the board split by words (mnk_rollout_pairw.hip): the five-in-a-row boards of MNK_BUILTIN_BOARDS
 bool mnk_rollout_pairw_supported(const MnkGeom& g);
 void mnk_launch_rollout_pairw(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
                               uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,

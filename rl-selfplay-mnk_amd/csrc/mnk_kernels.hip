@@ -346,14 +346,9 @@ int mnk_selfplay_pre(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, 
                      uint8_t* sp_flags, void* opp_obs, int obs_dtype, uint8_t* opp_mask, int32_t* err, uint32_t flags,
                      void* stream) {
   MnkSpArgs a;
-  int rc = mnk_sp_args_pre(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev, env_id0,
-                           rewards, terminated, sp_flags, opp_obs, obs_dtype, opp_mask, err, flags);
-  if (rc != MNK_OK) return rc;
-  if (!actions) return MNK_EINVAL;
-  if (N == 0) return MNK_OK;
-  if (!mnk_launch_sp_jit<MNK_SP_PRE>(a, actions, MnkSample{}, (hipStream_t)stream))
-    MNK_DISPATCH(a.g, mnk_launch_sp<MNK_SP_PRE, NW, CN, CK, NoDraw>(a, actions, MnkSample{}, (hipStream_t)stream));
-  return mnk_launch_status("selfplay_pre");
+  const int rc = mnk_sp_args_pre(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev,
+                                 env_id0, rewards, terminated, sp_flags, opp_obs, obs_dtype, opp_mask, err, flags);
+  return mnk_sp_step<MNK_SP_PRE>(rc, a, actions, stream, "selfplay_pre");
 }
 
 int mnk_selfplay_post(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, const int64_t* opp_actions,
@@ -361,14 +356,9 @@ int mnk_selfplay_post(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n,
                       uint8_t* pending, void* obs, int obs_dtype, uint8_t* legal_mask, uint64_t* packed_obs, int32_t* err,
                       float* ep_return, int32_t* ep_length, int64_t* ep_stats, uint32_t flags, void* stream) {
   MnkSpArgs a;
-  int rc = mnk_sp_args_post(&a, planes, meta, N, m, n, k, sp_flags, agent_side, rewards, terminated, pending, obs, obs_dtype,
-                            legal_mask, packed_obs, err, ep_return, ep_length, ep_stats, flags);
-  if (rc != MNK_OK) return rc;
-  if (!opp_actions) return MNK_EINVAL;
-  if (N == 0) return MNK_OK;
-  if (!mnk_launch_sp_jit<MNK_SP_POST>(a, opp_actions, MnkSample{}, (hipStream_t)stream))
-    MNK_DISPATCH(a.g, mnk_launch_sp<MNK_SP_POST, NW, CN, CK, NoDraw>(a, opp_actions, MnkSample{}, (hipStream_t)stream));
-  return mnk_launch_status("selfplay_post");
+  const int rc = mnk_sp_args_post(&a, planes, meta, N, m, n, k, sp_flags, agent_side, rewards, terminated, pending, obs,
+                                  obs_dtype, legal_mask, packed_obs, err, ep_return, ep_length, ep_stats, flags);
+  return mnk_sp_step<MNK_SP_POST>(rc, a, opp_actions, stream, "selfplay_post");
 }
 
 int mnk_selfplay_step_random(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, const int64_t* actions,
@@ -378,15 +368,10 @@ int mnk_selfplay_step_random(uint64_t* planes, uint32_t* meta, int64_t N, int m,
                              int32_t* err, float* ep_return, int32_t* ep_length, int64_t* ep_stats, uint32_t flags,
                              void* stream) {
   MnkSpArgs a;
-  int rc = mnk_sp_args_step_random(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev,
-                                   env_id0, rewards, terminated, obs, obs_dtype, legal_mask, packed_obs, err, ep_return,
-                                   ep_length, ep_stats, flags);
-  if (rc != MNK_OK) return rc;
-  if (!actions) return MNK_EINVAL;
-  if (N == 0) return MNK_OK;
-  if (!mnk_launch_sp_jit<MNK_SP_STEP_RANDOM>(a, actions, MnkSample{}, (hipStream_t)stream))
-    MNK_DISPATCH(a.g, mnk_launch_sp<MNK_SP_STEP_RANDOM, NW, CN, CK, NoDraw>(a, actions, MnkSample{}, (hipStream_t)stream));
-  return mnk_launch_status("selfplay_step_random");
+  const int rc = mnk_sp_args_step(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev,
+                                  env_id0, rewards, terminated, obs, obs_dtype, legal_mask, packed_obs, err, ep_return,
+                                  ep_length, ep_stats, flags);
+  return mnk_sp_step<MNK_SP_STEP_RANDOM>(rc, a, actions, stream, "selfplay_step_random");
 }
 
 int mnk_unpack_records(const uint64_t* rec_planes, const uint32_t* rec_meta, int64_t N, int T, int m, int n,

@@ -43,9 +43,7 @@ int mnk_rollout_random(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n
   // (MNK_ROLLOUT_PAIR=0/1 overrides, for A/B timing)
   const MnkConfig& cfg = mnk_config();  // environment knobs, read once (mnk_reload_config() re-reads them)
   const int pair_override = cfg.pair_override;
-  const bool pair_geom = (g.n == 9 && g.k == 5 && g.NW == 3) || (g.n == 3 && g.k == 3 && g.NW == 1) ||
-                         (g.n == 13 && g.k == 5 && g.NW == 6) || (g.n == 15 && g.k == 5 && g.NW == 8) ||
-                         (g.n == 19 && g.k == 5 && g.NW == 12);
+  const bool pair_geom = mnk_geom_builtin(g.n, g.k, g.NW);
   const bool w_fits = ((int64_t)T * g.NW + 1) * N * 8 < (1ll << 32);  // the two-lane forms' record stores use 32-bit byte offsets
   // (the 7-bit action stream exists in the one-lane form only: a launch that writes one never takes a two-lane form)
   const bool use_pair = pair_geom && w_fits && act_bytes != MNK_ACT_BITS7 &&
@@ -107,19 +105,11 @@ int mnk_rollout_random(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n
   // (N <= 65 536: the kernel is bound by its instruction count and this saves ~4 of ~150 per ply: 92.0 -> 88.5 us at
   // the headline size) and one launch's record rows fit 32-bit offsets; from 131 072 envs up the kernel is bound by
   // the HBM write rate and the 64-bit form measured faster (157 vs 166-184 us), so it stays there.
-  if (rec && pair_geom && mnk_rollout_saddr_ok(g, N, T)) {
-#define MNK_SADDR(NWv, CNv, CKv)                                                                                      \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random<NWv, CNv, CKv, true, 0, true>), grid, dim3(B), 0,               \
-                     (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta,          \
-                     (unsigned long long*)stats, act_log)
-    if (g.n == 9) MNK_SADDR(3, 9, 5);
-    else if (g.n == 3) MNK_SADDR(1, 3, 3);
-    else if (g.n == 13) MNK_SADDR(6, 13, 5);
-    else if (g.n == 15) MNK_SADDR(8, 15, 5);
-    else MNK_SADDR(12, 19, 5);
-#undef MNK_SADDR
+  if (rec && mnk_rollout_saddr_ok(g, N, T) &&
+      MNK_BUILTIN(g, true, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random<NW, CN, CK, true, 0, true>), grid, dim3(B), 0,
+                                              (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0, rec_planes,
+                                              rec_meta, (unsigned long long*)stats, act_log)))
     return mnk_launch_status("rollout_random");
-  }
 #define MNK_ROLLOUT(REC)                                                                                       \
   MNK_DISPATCH16(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random<NW, CN, CK, REC, 0>), grid, dim3(B), 0, \
                                      (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0,         \
@@ -158,31 +148,22 @@ int mnk_replay_actions(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n
     snprintf(g_launch_err, sizeof(g_launch_err), "replay_actions: no kernel for this board: %.200s", mnk_jit_last_error());
     return MNK_ELAUNCH;
   }
-#define MNK_REPLAY(REC, ACTB)                                                                                       \
-  MNK_DISPATCH16(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_replay_actions<NW, CN, CK, REC, ACTB>), grid, dim3(B), 0,    \
-                                     (hipStream_t)stream, g, planes, meta, N, T, act_log, REC ? rec_planes : nullptr, \
-                                     REC ? rec_meta : nullptr, err))
   const bool rec = rec_planes && rec_meta;
+  // (the U8P1 and 7-bit forms: as in mnk_launch_rollout_log)
+#define MNK_REPLAY(DISPATCH, REC, ACTB)                                                                              \
+  DISPATCH(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_replay_actions<NW, CN, CK, REC, ACTB>), grid, dim3(B), 0,          \
+                                 (hipStream_t)stream, g, planes, meta, N, T, act_log, REC ? rec_planes : nullptr,     \
+                                 REC ? rec_meta : nullptr, err))
   if (act_bytes == MNK_ACT_U8P1) {
-#define MNK_REPLAY9(REC)                                                                                               \
-  MNK_DISPATCH16_LARGE(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_replay_actions<NW, CN, CK, REC, 4>), grid, dim3(B), 0,    \
-                                           (hipStream_t)stream, g, planes, meta, N, T, act_log,                        \
-                                           REC ? rec_planes : nullptr, REC ? rec_meta : nullptr, err))
-    if (rec) MNK_REPLAY9(true);
-    else MNK_REPLAY9(false);
-#undef MNK_REPLAY9
+    if (rec) MNK_REPLAY(MNK_DISPATCH16_LARGE, true, 4);
+    else MNK_REPLAY(MNK_DISPATCH16_LARGE, false, 4);
   } else if (act_bytes == MNK_ACT_BITS7) {
-#define MNK_REPLAY7(REC)                                                                                               \
-  MNK_DISPATCH_SMALL(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_replay_actions<NW, CN, CK, REC, 3>), grid, dim3(B), 0,    \
-                                           (hipStream_t)stream, g, planes, meta, N, T, act_log,                        \
-                                           REC ? rec_planes : nullptr, REC ? rec_meta : nullptr, err))
-    if (rec) MNK_REPLAY7(true);
-    else MNK_REPLAY7(false);
-#undef MNK_REPLAY7
-  } else if (rec && act_bytes == 1) MNK_REPLAY(true, 1);
-  else if (rec) MNK_REPLAY(true, 2);
-  else if (act_bytes == 1) MNK_REPLAY(false, 1);
-  else MNK_REPLAY(false, 2);
+    if (rec) MNK_REPLAY(MNK_DISPATCH_SMALL, true, 3);
+    else MNK_REPLAY(MNK_DISPATCH_SMALL, false, 3);
+  } else if (rec && act_bytes == 1) MNK_REPLAY(MNK_DISPATCH16, true, 1);
+  else if (rec) MNK_REPLAY(MNK_DISPATCH16, true, 2);
+  else if (act_bytes == 1) MNK_REPLAY(MNK_DISPATCH16, false, 1);
+  else MNK_REPLAY(MNK_DISPATCH16, false, 2);
 #undef MNK_REPLAY
   return mnk_launch_status("replay_actions");
 }

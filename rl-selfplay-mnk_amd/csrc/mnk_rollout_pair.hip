@@ -29,25 +29,18 @@ void mnk_launch_rollout_pair(const MnkGeom& g, uint64_t* planes, uint32_t* meta,
                              uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
                              void* act_log, int act_bytes, void* stream) {
   const bool rec = rec_planes && rec_meta;
-    const dim3 pgrid((unsigned)((N + 31) / 32));
-#define MNK_PAIR(NWv, CNv, CKv, REC, ACTB)                                                                     \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random_pair<NWv, CNv, CKv, REC, ACTB>), pgrid, dim3(64), 0,     \
+  const dim3 pgrid((unsigned)((N + 31) / 32));
+  // (every board, 19x19 included, has the byte log: the launcher never asks for it there -- 361 cells -- but it stays built)
+#define MNK_PAIR(REC, ACTB)                                                                                    \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random_pair<NW, CN, CK, REC, ACTB>), pgrid, dim3(64), 0,        \
                      (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta,   \
                      (unsigned long long*)stats, act_log)
-#define MNK_PAIR_GEOM(REC, ACTB)                               \
-  do {                                                         \
-    if (g.n == 9) MNK_PAIR(3, 9, 5, REC, ACTB);                \
-    else if (g.n == 3) MNK_PAIR(1, 3, 3, REC, ACTB);           \
-    else if (g.n == 13) MNK_PAIR(6, 13, 5, REC, ACTB);         \
-    else if (g.n == 15) MNK_PAIR(8, 15, 5, REC, ACTB);         \
-    else MNK_PAIR(12, 19, 5, REC, ACTB);                       \
-  } while (0)
-    if (rec && act_bytes == 1) MNK_PAIR_GEOM(true, 1);
-    else if (rec && act_bytes == 2) MNK_PAIR_GEOM(true, 2);
-    else if (rec) MNK_PAIR_GEOM(true, 0);
-    else if (act_bytes == 1) MNK_PAIR_GEOM(false, 1);
-    else if (act_bytes == 2) MNK_PAIR_GEOM(false, 2);
-    else MNK_PAIR_GEOM(false, 0);
-#undef MNK_PAIR_GEOM
+  MNK_BUILTIN(g, true,
+              if (rec && act_bytes == 1) MNK_PAIR(true, 1);
+              else if (rec && act_bytes == 2) MNK_PAIR(true, 2);
+              else if (rec) MNK_PAIR(true, 0);
+              else if (act_bytes == 1) MNK_PAIR(false, 1);
+              else if (act_bytes == 2) MNK_PAIR(false, 2);
+              else MNK_PAIR(false, 0));
 #undef MNK_PAIR
 }

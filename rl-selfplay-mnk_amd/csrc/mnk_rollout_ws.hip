@@ -68,10 +68,12 @@ k_rollout_random_ws(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int 
               (unsigned long long)lds_stats[threadIdx.x]);
 }
 
-// ws = 2 or 4; geometry must be one of the boards below (mnk_rollout_ws_supported)
+// the boards this form has variants for: the 9x9x5 and 19x19x5 rows of MNK_BUILTIN_BOARDS
+#define MNK_WS_BOARD (MnkRow_::CN == 9 || MnkRow_::CN == 19)
+
+// ws = 2 or 4; geometry must be one of MNK_WS_BOARD (mnk_rollout_ws_supported)
 bool mnk_rollout_ws_supported(const MnkGeom& g, int act_bytes) {
-  if (act_bytes) return false;
-  return (g.n == 9 && g.k == 5 && g.NW == 3) || (g.n == 19 && g.k == 5 && g.NW == 12);
+  return !act_bytes && MNK_BUILTIN(g, MNK_WS_BOARD, (void)0);
 }
 
 void mnk_launch_rollout_ws(const MnkGeom& g, int ws, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
@@ -79,23 +81,18 @@ void mnk_launch_rollout_ws(const MnkGeom& g, int ws, uint64_t* planes, uint32_t*
                            void* act_log, int act_bytes, void* stream) {
   const bool rec = rec_planes && rec_meta;
   const dim3 grid((unsigned)((N + 63) / 64));
-#define MNK_WS(NWv, CNv, CKv, REC, ACTB, WSv)                                                                      \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random_ws<NWv, CNv, CKv, REC, ACTB, WSv>), grid, dim3(64 * WSv), 0, \
+#define MNK_WS(REC, WSv)                                                                                          \
+  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random_ws<NW, CN, CK, REC, 0, WSv>), grid, dim3(64 * WSv), 0,        \
                      (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta,       \
                      (unsigned long long*)stats, act_log)
-#define MNK_WS_BOARD(NWv, CNv, CKv)                         \
-  do {                                                      \
-    if (ws == 4) {                                          \
-      if (rec) MNK_WS(NWv, CNv, CKv, true, 0, 4);           \
-      else MNK_WS(NWv, CNv, CKv, false, 0, 4);              \
-    } else {                                                \
-      if (rec) MNK_WS(NWv, CNv, CKv, true, 0, 2);           \
-      else MNK_WS(NWv, CNv, CKv, false, 0, 2);              \
-    }                                                       \
-  } while (0)
-  (void)act_log; (void)act_bytes;
-  if (g.n == 9) MNK_WS_BOARD(3, 9, 5);
-  else MNK_WS_BOARD(12, 19, 5);
-#undef MNK_WS_BOARD
+  (void)act_bytes;
+  MNK_BUILTIN(g, MNK_WS_BOARD,
+              if (ws == 4) {
+                if (rec) MNK_WS(true, 4);
+                else MNK_WS(false, 4);
+              } else {
+                if (rec) MNK_WS(true, 2);
+                else MNK_WS(false, 2);
+              });
 #undef MNK_WS
 }

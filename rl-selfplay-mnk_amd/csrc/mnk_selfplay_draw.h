@@ -10,27 +10,30 @@ inline int mnk_sample_args_ok(const MnkSample& sa, int64_t N, int C) {
   return MNK_OK;
 }
 
-// Launches kernel WHICH with the draw folded in when the board has a compile-time draw shape (3x3x3, 9x9x5, 13x13x5,
-// 15x15x5, 19x19x5: the boards the reference trains on and the usual Gomoku sizes) or a run-time compiled variant of its own
-// (mnk_jit.hip: any other board, any row width); false = the caller takes two launches.
+// Launches kernel WHICH with the draw folded in when the board has a compile-time draw shape (the square boards of
+// MNK_BUILTIN_BOARDS: the boards the reference trains on and the usual Gomoku sizes) or a run-time compiled variant of its
+// own (mnk_jit.hip: any other board, any row width); false = the caller takes two launches.
 template <int WHICH>
 inline bool mnk_launch_sp_fused(const MnkSpArgs& a, const MnkSample& sa, hipStream_t s) {
-  const MnkGeom& g = a.g;
   if (mnk_launch_sp_jit<WHICH>(a, nullptr, sa, s)) return true;  // a board without a built-in variant, once it is hot
-  if (g.m != g.n) return false;
+  if (a.g.m != a.g.n) return false;
   const int lt = !sa.logits ? 2 : (sa.logits_dtype == MNK_LOGITS_BF16 ? 1 : 0);
-#define MNK_FUSED(NWv, CNv, CKv, Cv)                                                                            \
-  do {                                                                                                          \
-    if (lt == 0) mnk_launch_sp<WHICH, NWv, CNv, CKv, Draw<float, Cv>>(a, nullptr, sa, s);                       \
-    else if (lt == 1) mnk_launch_sp<WHICH, NWv, CNv, CKv, Draw<uint16_t, Cv>>(a, nullptr, sa, s);               \
-    else mnk_launch_sp<WHICH, NWv, CNv, CKv, Draw<void, Cv>>(a, nullptr, sa, s);                                \
-    return true;                                                                                                \
-  } while (0)
-  if (g.n == 9 && g.k == 5) MNK_FUSED(3, 9, 5, 81);
-  if (g.n == 3 && g.k == 3) MNK_FUSED(1, 3, 3, 9);
-  if (g.n == 13 && g.k == 5) MNK_FUSED(6, 13, 5, 169);
-  if (g.n == 15 && g.k == 5) MNK_FUSED(8, 15, 5, 225);
-  if (g.n == 19 && g.k == 5) MNK_FUSED(12, 19, 5, 361);
-#undef MNK_FUSED
-  return false;
+  return MNK_BUILTIN(a.g, true,
+                     if (lt == 0) mnk_launch_sp<WHICH, NW, CN, CK, Draw<float, MnkRow_::C>>(a, nullptr, sa, s);
+                     else if (lt == 1) mnk_launch_sp<WHICH, NW, CN, CK, Draw<uint16_t, MnkRow_::C>>(a, nullptr, sa, s);
+                     else mnk_launch_sp<WHICH, NW, CN, CK, Draw<void, MnkRow_::C>>(a, nullptr, sa, s));
+}
+
+// The body of the four logits forms of the step entry points: `rc` is the result of the argument builder that filled `a`;
+// a board without a compile-time draw shape takes the draw as a launch of its own, then `actions_form` (the actions form
+// of the same entry point, with sa.actions as its moves).
+template <int WHICH, typename F>
+inline int mnk_sp_step_logits(int rc, const MnkSpArgs& a, const MnkSample& sa, void* stream, const char* what,
+                              F&& actions_form) {
+  if (rc != MNK_OK) return rc;
+  if ((rc = mnk_sample_args_ok(sa, a.N, a.g.C)) != MNK_OK) return rc;
+  if (a.N == 0) return MNK_OK;
+  if (mnk_launch_sp_fused<WHICH>(a, sa, (hipStream_t)stream)) return mnk_launch_status(what);
+  if ((rc = mnk_launch_sample(sa, a.N, a.g.C, (hipStream_t)stream)) != MNK_OK) return rc;
+  return actions_form();
 }

@@ -31,7 +31,8 @@ struct MnkSpArgs {
 
 enum { MNK_SP_PRE = 0, MNK_SP_POST = 1, MNK_SP_STEP_RANDOM = 2, MNK_SP_STEP_TACTICAL = 3 };  // (TACTICAL: step_random's arguments)
 
-// argument checks + MnkSpArgs of the three entry points (shared by their actions and their logits forms)
+// argument checks + MnkSpArgs of the entry points (shared by their actions and their logits forms; mnk_sp_args_step:
+// step_random and step_tactical)
 inline int mnk_sp_args_pre(MnkSpArgs* a, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, const uint8_t* pending,
                            int64_t* agent_side, const int64_t* forced_side, uint64_t seed, uint64_t step,
                            const uint64_t* step_dev, int64_t env_id0, float* rewards, uint8_t* terminated, uint8_t* sp_flags,
@@ -65,11 +66,11 @@ inline int mnk_sp_args_post(MnkSpArgs* a, uint64_t* planes, uint32_t* meta, int6
   return MNK_OK;
 }
 
-inline int mnk_sp_args_step_random(MnkSpArgs* a, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, uint8_t* pending,
-                                   int64_t* agent_side, const int64_t* forced_side, uint64_t seed, uint64_t step,
-                                   const uint64_t* step_dev, int64_t env_id0, float* rewards, uint8_t* terminated, void* obs,
-                                   int obs_dtype, uint8_t* legal_mask, uint64_t* packed_obs, int32_t* err, float* ep_return,
-                                   int32_t* ep_length, int64_t* ep_stats, uint32_t flags) {
+inline int mnk_sp_args_step(MnkSpArgs* a, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, uint8_t* pending,
+                            int64_t* agent_side, const int64_t* forced_side, uint64_t seed, uint64_t step,
+                            const uint64_t* step_dev, int64_t env_id0, float* rewards, uint8_t* terminated, void* obs,
+                            int obs_dtype, uint8_t* legal_mask, uint64_t* packed_obs, int32_t* err, float* ep_return,
+                            int32_t* ep_length, int64_t* ep_stats, uint32_t flags) {
   memset(a, 0, sizeof(*a));
   int rc = mnk_check_geom(m, n, k, &a->g);
   if (rc != MNK_OK) return rc;
@@ -168,4 +169,16 @@ inline bool mnk_launch_sp_jit(const MnkSpArgs& a, const int64_t* moves, const Mn
                       moves, sa, a.pending, a.agent_side, a.forced_side, a.seed, a.step, a.step_dev, a.env_id0, a.rewards,
                       a.terminated, a.obs, a.obs_dtype, a.mask, a.packed_obs, a.err, a.ep, a.flags, vec_ok, B, span);
   return true;
+}
+
+// The body of the four actions forms of the step entry points: `rc` is the result of the argument builder that filled `a`.
+template <int WHICH>
+inline int mnk_sp_step(int rc, const MnkSpArgs& a, const int64_t* moves, void* stream, const char* what) {
+  if (rc != MNK_OK) return rc;
+  if (!moves) return MNK_EINVAL;
+  if (a.N == 0) return MNK_OK;
+  const hipStream_t s = (hipStream_t)stream;
+  if (!mnk_launch_sp_jit<WHICH>(a, moves, MnkSample{}, s))
+    MNK_DISPATCH(a.g, mnk_launch_sp<WHICH, NW, CN, CK, NoDraw>(a, moves, MnkSample{}, s));
+  return mnk_launch_status(what);
 }

@@ -13,15 +13,12 @@ extern "C" int mnk_selfplay_post_logits(uint64_t* planes, uint32_t* meta, int64_
                                         int32_t* err, float* ep_return, int32_t* ep_length, int64_t* ep_stats, uint32_t flags,
                                         void* stream) {
   MnkSpArgs a;
-  int rc = mnk_sp_args_post(&a, planes, meta, N, m, n, k, sp_flags, agent_side, rewards, terminated, pending, obs, obs_dtype,
-                            legal_mask, packed_obs, err, ep_return, ep_length, ep_stats, flags);
-  if (rc != MNK_OK) return rc;
+  const int rc = mnk_sp_args_post(&a, planes, meta, N, m, n, k, sp_flags, agent_side, rewards, terminated, pending, obs,
+                                  obs_dtype, legal_mask, packed_obs, err, ep_return, ep_length, ep_stats, flags);
   const MnkSample sa = {opp_logits, logits_dtype, opp_mask, sample_seed, sample_seed_dev, sample_step, sample_step_dev,
                         sample_env_id0, deterministic, opp_actions, opp_logp};
-  if ((rc = mnk_sample_args_ok(sa, N, a.g.C)) != MNK_OK) return rc;
-  if (N == 0) return MNK_OK;
-  if (mnk_launch_sp_fused<MNK_SP_POST>(a, sa, (hipStream_t)stream)) return mnk_launch_status("selfplay_post_logits");
-  if ((rc = mnk_launch_sample(sa, N, a.g.C, (hipStream_t)stream)) != MNK_OK) return rc;
-  return mnk_selfplay_post(planes, meta, N, m, n, k, opp_actions, sp_flags, agent_side, rewards, terminated, pending, obs,
-                           obs_dtype, legal_mask, packed_obs, err, ep_return, ep_length, ep_stats, flags, stream);
+  return mnk_sp_step_logits<MNK_SP_POST>(rc, a, sa, stream, "selfplay_post_logits", [&] {
+    return mnk_selfplay_post(planes, meta, N, m, n, k, opp_actions, sp_flags, agent_side, rewards, terminated, pending, obs,
+                             obs_dtype, legal_mask, packed_obs, err, ep_return, ep_length, ep_stats, flags, stream);
+  });
 }

@@ -12,16 +12,12 @@ extern "C" int mnk_selfplay_pre_logits(uint64_t* planes, uint32_t* meta, int64_t
                                        uint8_t* terminated, uint8_t* sp_flags, void* opp_obs, int obs_dtype, uint8_t* opp_mask,
                                        int32_t* err, uint32_t flags, void* stream) {
   MnkSpArgs a;
-  int rc = mnk_sp_args_pre(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev, env_id0,
-                           rewards, terminated, sp_flags, opp_obs, obs_dtype, opp_mask, err, flags);
-  if (rc != MNK_OK) return rc;
+  const int rc = mnk_sp_args_pre(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev,
+                                 env_id0, rewards, terminated, sp_flags, opp_obs, obs_dtype, opp_mask, err, flags);
   const MnkSample sa = {logits, logits_dtype, mask, sample_seed, sample_seed_dev, sample_step, sample_step_dev, sample_env_id0,
                         deterministic, actions, logp};
-  if ((rc = mnk_sample_args_ok(sa, N, a.g.C)) != MNK_OK) return rc;
-  if (N == 0) return MNK_OK;
-  if (mnk_launch_sp_fused<MNK_SP_PRE>(a, sa, (hipStream_t)stream)) return mnk_launch_status("selfplay_pre_logits");
-  // a board without a compile-time draw shape: the draw as a launch of its own, then the actions form
-  if ((rc = mnk_launch_sample(sa, N, a.g.C, (hipStream_t)stream)) != MNK_OK) return rc;
-  return mnk_selfplay_pre(planes, meta, N, m, n, k, actions, pending, agent_side, forced_side, seed, step, step_dev, env_id0,
-                          rewards, terminated, sp_flags, opp_obs, obs_dtype, opp_mask, err, flags, stream);
+  return mnk_sp_step_logits<MNK_SP_PRE>(rc, a, sa, stream, "selfplay_pre_logits", [&] {
+    return mnk_selfplay_pre(planes, meta, N, m, n, k, actions, pending, agent_side, forced_side, seed, step, step_dev, env_id0,
+                            rewards, terminated, sp_flags, opp_obs, obs_dtype, opp_mask, err, flags, stream);
+  });
 }

@@ -15,17 +15,14 @@ extern "C" int mnk_selfplay_step_random_logits(uint64_t* planes, uint32_t* meta,
                                                float* ep_return, int32_t* ep_length, int64_t* ep_stats, uint32_t flags,
                                                void* stream) {
   MnkSpArgs a;
-  int rc = mnk_sp_args_step_random(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev,
-                                   env_id0, rewards, terminated, obs, obs_dtype, legal_mask, packed_obs, err, ep_return,
-                                   ep_length, ep_stats, flags);
-  if (rc != MNK_OK) return rc;
+  const int rc = mnk_sp_args_step(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev,
+                                  env_id0, rewards, terminated, obs, obs_dtype, legal_mask, packed_obs, err, ep_return,
+                                  ep_length, ep_stats, flags);
   const MnkSample sa = {logits, logits_dtype, mask, sample_seed, sample_seed_dev, sample_step, sample_step_dev, sample_env_id0,
                         deterministic, actions, logp};
-  if ((rc = mnk_sample_args_ok(sa, N, a.g.C)) != MNK_OK) return rc;
-  if (N == 0) return MNK_OK;
-  if (mnk_launch_sp_fused<MNK_SP_STEP_RANDOM>(a, sa, (hipStream_t)stream)) return mnk_launch_status("selfplay_step_random_logits");
-  if ((rc = mnk_launch_sample(sa, N, a.g.C, (hipStream_t)stream)) != MNK_OK) return rc;
-  return mnk_selfplay_step_random(planes, meta, N, m, n, k, actions, pending, agent_side, forced_side, seed, step, step_dev,
-                                  env_id0, rewards, terminated, obs, obs_dtype, legal_mask, packed_obs, err, ep_return,
-                                  ep_length, ep_stats, flags, stream);
+  return mnk_sp_step_logits<MNK_SP_STEP_RANDOM>(rc, a, sa, stream, "selfplay_step_random_logits", [&] {
+    return mnk_selfplay_step_random(planes, meta, N, m, n, k, actions, pending, agent_side, forced_side, seed, step, step_dev,
+                                    env_id0, rewards, terminated, obs, obs_dtype, legal_mask, packed_obs, err, ep_return,
+                                    ep_length, ep_stats, flags, stream);
+  });
 }

@@ -13,15 +13,10 @@ int mnk_selfplay_step_tactical(uint64_t* planes, uint32_t* meta, int64_t N, int 
                                int32_t* err, float* ep_return, int32_t* ep_length, int64_t* ep_stats, uint32_t flags,
                                void* stream) {
   MnkSpArgs a;
-  int rc = mnk_sp_args_step_random(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev,
-                                   env_id0, rewards, terminated, obs, obs_dtype, legal_mask, packed_obs, err, ep_return,
-                                   ep_length, ep_stats, flags);
-  if (rc != MNK_OK) return rc;
-  if (!actions) return MNK_EINVAL;
-  if (N == 0) return MNK_OK;
-  if (!mnk_launch_sp_jit<MNK_SP_STEP_TACTICAL>(a, actions, MnkSample{}, (hipStream_t)stream))
-    MNK_DISPATCH(a.g, mnk_launch_sp<MNK_SP_STEP_TACTICAL, NW, CN, CK, NoDraw>(a, actions, MnkSample{}, (hipStream_t)stream));
-  return mnk_launch_status("selfplay_step_tactical");
+  const int rc = mnk_sp_args_step(&a, planes, meta, N, m, n, k, pending, agent_side, forced_side, seed, step, step_dev,
+                                  env_id0, rewards, terminated, obs, obs_dtype, legal_mask, packed_obs, err, ep_return,
+                                  ep_length, ep_stats, flags);
+  return mnk_sp_step<MNK_SP_STEP_TACTICAL>(rc, a, actions, stream, "selfplay_step_tactical");
 }
 
 int mnk_sample_tactical(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, uint64_t seed,
