@@ -120,6 +120,7 @@ extern "C" {
 #define MNK_STREAM_SIDE 2
 #define MNK_STREAM_SAMPLE 3
 #define MNK_STREAM_PLAYOUT 4 /* the random plies of the Monte Carlo player's playouts (mnk_sample_playouts) */
+#define MNK_STREAM_SEARCH 5  /* the random plies of the tree-search player's playouts (mnk_sample_search) */
 
 int mnk_abi_version(void);
 /* Developer knobs (MNK_ROLLOUT_PAIR, MNK_ROLLOUT_FORM, MNK_JIT, MNK_ROLLOUT_SADDR, MNK_EMIT_ENVS, MNK_EMIT_THREADS: A/B
@@ -343,6 +344,44 @@ int mnk_sample_playouts(const void* obs, int obs_dtype, int64_t N, int m, int n,
                         const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                         int deterministic, int64_t* actions, int32_t* counts, void* stream);
 #define MNK_PLAYOUTS_MAX 4096
+
+/* ---- the tree-search player (UCT): a fixed-strength opponent whose strength is set by an iteration budget I, with B
+ * random playouts per leaf.  Row i of obs is a canonical view as for mnk_sample_playouts (channel 0 = the side to move,
+ * "me"; f32 / bf16 / u8, a cell is a stone when its element is non-zero); C = m*n.  The root is the row's position; a node
+ * is the position after one more move.  Per node: visits n, and wins W and losses Lo counted from the view of the player
+ * who made the move into the node.  A node is terminal when its move leaves a run of >= k of its mover anywhere on that
+ * mover's plane (the env's whole-plane test: an overline counts, a run already on the board counts) or fills the board;
+ * a terminal node is never expanded.  Iteration it = 0 .. I-1:
+ *   selection: from the root, at a non-terminal node v: if v has a legal cell that is not yet a child, the first such
+ *     cell in action order is expanded and the new child is the leaf; otherwise go to the child of maximal
+ *     s = q + c * sqrt(n_v / n_child), q = (W - Lo) / n_child, evaluated in f32 with correctly rounded operations and no
+ *     contraction: s = fadd(fdiv(W - Lo, n_child), fmul(c, fsqrt(fdiv(n_v, n_child)))); ties go to the lowest cell.  A
+ *     terminal node reached this way is the leaf.
+ *   evaluation: a terminal leaf counts its own outcome B times and draws no random numbers.  Otherwise B playouts start
+ *     from the leaf with the Monte Carlo player's ply rule (pick_legal over the legal cells; the game ends at the first
+ *     ply that leaves a run of its mover, or on a full board).  Ply t of playout j draws
+ *       x = Philox(seed, env_id0 + i, u, MNK_STREAM_SEARCH),  u = (((step * I + it) * B + j) * C4) + t,  C4 = C rounded
+ *     up to a multiple of 4.  Range: q = u >> 2 must fit in 56 bits, i.e. (step + 1) * I * B * C4 <= 2^58; a host `step`
+ *     that breaks it is rejected (*step_dev is added on the device, unchecked).
+ *   backup: every node on the path from the root to the leaf gets n += B, and the wins and losses of the B outcomes, each
+ *     from that node's mover's view.
+ * All counts stay below 2^24 and so convert to f32 exactly.  The move: S = the root children of maximal n; the r-th cell
+ * of S in action order, r = mulhi32(x, |S|), x = Philox(seed, env_id0 + i, step [+ *step_dev], MNK_STREAM_SAMPLE) --
+ * TacticalPolicy's u32; deterministic: r = 0; no legal cell: the draw is over all C cells (no iterations run).  A cell
+ * that wins at once is a terminal child with W = n; the first |L| iterations expand every root child once (B visits
+ * each), so with I < |L| a winning cell may stay unexpanded and is not guaranteed to be played.  With I >= |L| every
+ * root child exists; a winning child keeps q = 1, the best value any child can have, but UCT may still spend more visits
+ * on another child, so even then the rule guarantees only that the win is in the tree (in practice, at c = 1 and
+ * I >= 2 |L|, it draws most of the visits).
+ * seed_dev (optional) REPLACES seed, step_dev (optional) is ADDED to step.  c: finite, >= 0.  actions int64[N]; stats
+ * (optional, NULL = off) int32[N][3][C] = the root children's n, then W, then Lo per cell, 0 on occupied cells and on
+ * cells never expanded.  iterations in [1, 2048], playouts in [1, 256].  One launch, one workgroup per row, the tree in
+ * LDS. */
+int mnk_sample_search(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, int playouts,
+                      float c, uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev,
+                      int64_t env_id0, int deterministic, int64_t* actions, int32_t* stats, void* stream);
+#define MNK_SEARCH_ITERS_MAX 2048
+#define MNK_SEARCH_PLAYOUTS_MAX 256
 
 /* ---- the random-policy rollout of BASELINE.json (RandomPolicy.act -> env.step -> env.reset(done)),
  * T plies per env in one launch with the state held in registers.

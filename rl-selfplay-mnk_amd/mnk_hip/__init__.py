@@ -22,8 +22,10 @@ OBS_F32, OBS_BF16, OBS_U8 = 0, 1, 2
 ACT_U8, ACT_U16, ACT_BITS7, ACT_U8P1 = 1, 2, 3, 4
 COMM_ID_BYTES = 128
 SP_NEED_OPP, SP_WAS_RESET = 1, 2
-STREAM_MOVE, STREAM_OPP, STREAM_SIDE, STREAM_SAMPLE, STREAM_PLAYOUT = 0, 1, 2, 3, 4
+STREAM_MOVE, STREAM_OPP, STREAM_SIDE, STREAM_SAMPLE, STREAM_PLAYOUT, STREAM_SEARCH = 0, 1, 2, 3, 4, 5
 PLAYOUTS_MAX = 4096  # MNK_PLAYOUTS_MAX: the largest playout count of mnk_sample_playouts
+SEARCH_ITERS_MAX = 2048  # MNK_SEARCH_ITERS_MAX: the largest iteration budget of mnk_sample_search
+SEARCH_PLAYOUTS_MAX = 256  # MNK_SEARCH_PLAYOUTS_MAX: the largest playout count per leaf of mnk_sample_search
 STATS_REPLICAS, STATS_STRIDE, STATS_COUNTERS = 64, 8, 5
 # run-time specialised API kernels (MNK_JIT_API_* of include/mnk_hip.h): bit numbers for jit_prepare()
 (JIT_API_STEP, JIT_API_STEP_DRAW, JIT_API_STEP_SUBSET, JIT_API_OBSERVE, JIT_API_SAMPLE_LEGAL, JIT_API_UNPACK_RECORDS,
@@ -80,6 +82,8 @@ SIGNATURES = {
     "mnk_sample_tactical": [_vp, _i, _i64, _i, _i, _i, _u64, _vp, _u64, _vp, _i64, _i, _vp, _vp, _vp],
     # obs, obs dtype, N, m, n, k, playouts, then the sampler block, actions, counts (int32 [N][2][C]), stream
     "mnk_sample_playouts": [_vp, _i, _i64, _i, _i, _i, _i, _u64, _vp, _u64, _vp, _i64, _i, _vp, _vp, _vp],
+    # obs, obs dtype, N, m, n, k, iterations, playouts, c, then the sampler block, actions, stats (int32 [N][3][C]), stream
+    "mnk_sample_search": [_vp, _i, _i64, _i, _i, _i, _i, _i, _f, _u64, _vp, _u64, _vp, _i64, _i, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],
     "mnk_action_log_words": [_i, _i],
     "mnk_replay_actions": [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp],

@@ -12,11 +12,15 @@
 ``MonteCarloPolicy`` the flat Monte Carlo player: for every legal cell P uniformly random playouts to the end of the game,
                    then a cell of best wins-minus-losses (``mnk_sample_playouts``); strength set by P, no training.  As a
                    wrapper opponent it goes through pre -> act -> post like any policy.
+``SearchPolicy``   the tree-search player (UCT): I iterations of selection, expansion, B random playouts from the leaf
+                   and backup, then a root child of most visits (``mnk_sample_search``); strength set by I, no training;
+                   hands out the root visit counts per cell.  As a wrapper opponent it goes through pre -> act -> post.
 ``FusedNNPolicy``  same distribution, but mask + softmax + draw run in ``mnk_sample_logits``
                    on the raw logits (the epilogue of cnn.py:69-79 fused with the sample).  As a wrapper opponent it is
                    recognised (``fused_logits``): the wrapper asks it for its logits only and the draw happens INSIDE
                    ``mnk_selfplay_post_logits`` -- same stream of random numbers, one launch fewer per step.
 """
+import math
 from abc import ABC, abstractmethod
 from typing import Dict
 
@@ -222,6 +226,49 @@ class MonteCarloPolicy(Policy):
             mnk_hip.call("mnk_sample_playouts", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, self.k,
                          self.playouts, *self._sampler.block(deterministic), mnk_hip.ptr(actions), mnk_hip.ptr(counts),
                          mnk_hip.stream_ptr(observation.device))
+        self._sampler.advance()
+        return actions
+
+
+class SearchPolicy(Policy):
+    """The tree-search player for k-in-a-row (the rule: include/mnk_hip.h, mnk_sample_search): UCT with ``iterations``
+    iterations per move, each of which expands one node (the first untried cell, in action order) or descends to the
+    child of maximal ``q + c * sqrt(n_parent / n_child)``, plays ``playouts`` uniformly random games from the leaf and
+    backs their outcomes up the path.  The move is drawn among the root children of most visits, in action order, from
+    one Philox u32 per row (the u32 ``TacticalPolicy`` draws; ``deterministic``: the first such cell).  Strength rises with
+    ``iterations`` and needs no training.  Reads only the observation (channel 0 = the side to move, any of float32 /
+    bfloat16 / uint8; the board size comes from its shape).  One launch per call, one workgroup per row, the tree in LDS.
+
+    As the opponent of ``TorchSelfPlayWrapper`` it is called through pre -> act -> post like any policy; it is not folded
+    into the one-launch step."""
+
+    def __init__(self, k: int, iterations: int = 256, playouts: int = 32, c: float = 0.05, seed=None):
+        self.k = int(k)
+        self.iterations = int(iterations)
+        self.playouts = int(playouts)
+        self.c = float(c)
+        if not 1 <= self.iterations <= mnk_hip.SEARCH_ITERS_MAX:
+            raise ValueError(f"iterations must lie in [1, {mnk_hip.SEARCH_ITERS_MAX}], got {iterations}")
+        if not 1 <= self.playouts <= mnk_hip.SEARCH_PLAYOUTS_MAX:
+            raise ValueError(f"playouts must lie in [1, {mnk_hip.SEARCH_PLAYOUTS_MAX}], got {playouts}")
+        if not (math.isfinite(self.c) and 0.0 <= self.c <= 3.0e38):
+            raise ValueError(f"c must be finite and >= 0, got {c}")
+        self._sampler = _HipSampler(seed)
+
+    def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, stats=None) -> torch.Tensor:
+        """``stats``: optional int32 ``[B, 3, m*n]`` tensor that receives each row's root visit counts (``[:, 0]``), and
+        the wins (``[:, 1]``) and losses (``[:, 2]``) of the side to move through each cell; 0 on occupied cells and on
+        cells the search never expanded"""
+        observation = _canonical_observation(obs)
+        b, _, m, n = observation.shape
+        actions = torch.empty(b, dtype=torch.long, device=observation.device)
+        if stats is not None and (stats.shape != (b, 3, m * n) or stats.dtype != torch.int32
+                                  or not stats.is_contiguous() or stats.device != observation.device):
+            raise ValueError(f"stats must be a contiguous int32 ({b}, 3, {m * n}) tensor on {observation.device}")
+        if b:
+            mnk_hip.call("mnk_sample_search", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, self.k,
+                         self.iterations, self.playouts, self.c, *self._sampler.block(deterministic),
+                         mnk_hip.ptr(actions), mnk_hip.ptr(stats), mnk_hip.stream_ptr(observation.device))
         self._sampler.advance()
         return actions
 
