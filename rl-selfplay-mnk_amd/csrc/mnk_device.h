@@ -73,6 +73,16 @@ __device__ __forceinline__ int geom_n(const MnkGeom& g) { return CN ? CN : g.n; 
 template <int CK>
 __device__ __forceinline__ int geom_k(const MnkGeom& g) { return CK ? CK : g.k; }
 
+// guard-column bit index (row * (n + 1) + col) -> cell (row * n + col), and back
+template <int CN>
+__device__ __forceinline__ int mnk_bit_cell(const MnkGeom& g, uint32_t bit) {
+  return (int)(bit - (CN ? bit / (uint32_t)(CN + 1) : mnk_div(bit, g.magic_stride)));
+}
+template <int CN>
+__device__ __forceinline__ uint32_t mnk_cell_bit(const MnkGeom& g, uint32_t cell) {
+  return cell + (CN ? cell / (uint32_t)CN : mnk_div(cell, g.magic_n));
+}
+
 // ---------------------------------------------------------------- multi-word bit strings
 // x >>= s for a wave-uniform s >= 0 (an immediate in the specialised kernels)
 template <int NW>
@@ -418,7 +428,7 @@ __device__ __forceinline__ int bs_pick_cell(const MnkGeom& g, uint32_t (&set)[NW
   for (int w = 0; w < NW; ++w) set[w] = nl ? set[w] : g.valid[w];
   const int r = (int)__umulhi(x, (uint32_t)(nl ? nl : g.C));
   const uint32_t bit = (uint32_t)bs_select<NW>(set, r);
-  return (int)(bit - (CN ? bit / (uint32_t)(CN + 1) : mnk_div(bit, g.magic_stride)));
+  return mnk_bit_cell<CN>(g, bit);
 }
 
 // uniform legal cell from one u32 (oracle/philox.py pick_legal; selfplay/policy.py:18-29)
@@ -486,7 +496,7 @@ __device__ __forceinline__ MnkPly env_play(const MnkGeom& g, MnkEnv<NW>& e, int6
     if (a64 < 0 || a64 >= C) { out.err = 1; return out; }
     a = (uint32_t)a64;
   }
-  const uint32_t bit = a + (CN ? a / (uint32_t)CN : mnk_div(a, g.magic_n));  // row*(n+1) + col
+  const uint32_t bit = mnk_cell_bit<CN>(g, a);
   const int wsel = (int)(bit >> 5);
   const uint32_t one = 1u << (bit & 31u);
   const uint32_t side = e.meta & 1u;

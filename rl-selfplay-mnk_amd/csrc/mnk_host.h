@@ -57,6 +57,22 @@ inline int mnk_geom_any_k(int m, int n, MnkGeom* g) {
   return MNK_OK;
 }
 
+// the opening checks of the mnk_sample_* players on a canonical observation: the board, then obs / actions / N / dtype
+inline int mnk_sample_check(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, const int64_t* actions,
+                            MnkGeom* g) {
+  const int rc = mnk_check_geom(m, n, k, g);
+  if (rc != MNK_OK) return rc;
+  return !obs || !actions || N < 0 || !mnk_obs_dtype_ok(obs_dtype) ? MNK_EINVAL : MNK_OK;
+}
+
+// the players that run a workgroup per row and play `games` random games per call and row on C cells, C4 = C rounded
+// up to a multiple of 4 Philox counters each: the position q = u >> 2 of the call's last ply must fit in 56 bits,
+// (step + 1) * games * C4 <= 2^58, and N in the grid's x dimension
+inline int mnk_rows_games_check(uint64_t step, uint64_t games, int C, int64_t N) {
+  if (step >= (1ull << 58) / (games * (uint64_t)((C + 3) & ~3))) return MNK_EINVAL;
+  return N > 0x7fffffff ? MNK_EINVAL : MNK_OK;
+}
+
 inline int mnk_launch_status(const char* what) {
   hipError_t e = hipGetLastError();
   if (e == hipSuccess) return MNK_OK;

@@ -74,7 +74,7 @@ k_sample_playouts(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int P, u
         uint32_t legal[NW];  // (rebuilt per item from the root rather than held across the loop: NW fewer VGPRs)
         env_legal<NW>(g, e, legal);
         const uint32_t bit = (uint32_t)bs_select<NW>(legal, li);
-        cell = (int)(bit - (CN ? bit / (uint32_t)(CN + 1) : mnk_div(bit, g.magic_stride)));
+        cell = mnk_bit_cell<CN>(g, bit);
         q0 = ((((uint64_t)step * (uint64_t)C + (uint64_t)cell) * (uint64_t)P + (uint64_t)j) * (uint64_t)C4) >> 2;
         t = -1;  // ply -1: "me" plays the cell
         live = true;
@@ -155,15 +155,11 @@ int mnk_sample_playouts(const void* obs, int obs_dtype, int64_t N, int m, int n,
                         const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                         int deterministic, int64_t* actions, int32_t* counts, void* stream) {
   MnkGeom g;
-  int rc = mnk_check_geom(m, n, k, &g);
+  int rc = mnk_sample_check(obs, obs_dtype, N, m, n, k, actions, &g);
   if (rc != MNK_OK) return rc;
-  if (!obs || !actions || N < 0 || !mnk_obs_dtype_ok(obs_dtype)) return MNK_EINVAL;
   if (playouts < 1 || playouts > MNK_PLAYOUTS_MAX) return MNK_EINVAL;
-  // the Philox position q = u >> 2 of the last ply of the call must fit in 56 bits: (step + 1) * C * P * C4 <= 2^58
-  const uint64_t per_step = (uint64_t)g.C * (uint64_t)playouts * (uint64_t)((g.C + 3) & ~3);  // < 2^32
-  if (step >= ((1ull << 58) / per_step)) return MNK_EINVAL;
-  if (N == 0) return MNK_OK;
-  if (N > 0x7fffffff) return MNK_EINVAL;  // (one workgroup per row: the grid's x dimension)
+  rc = mnk_rows_games_check(step, (uint64_t)g.C * (uint64_t)playouts, g.C, N);  // (C * P games)
+  if (rc != MNK_OK || N == 0) return rc;
   const dim3 grid((unsigned)N), block(256);
   const size_t lds = (size_t)2 * g.C * sizeof(uint32_t);
   hipStream_t s = (hipStream_t)stream;

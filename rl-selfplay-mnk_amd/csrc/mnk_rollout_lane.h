@@ -249,7 +249,7 @@ struct RolloutLane {
     }
     const int r = (int)__umulhi(x, (uint32_t)n);
     const uint32_t bit = (uint32_t)bs_select_hot<NW>(legal, r, hot);
-    return (int)(bit - (CN ? bit / (uint32_t)(CN + 1) : mnk_div(bit, g.magic_stride)));
+    return mnk_bit_cell<CN>(g, bit);
   }
 
   // field = position of this ply inside its group of four (= step & 3; a compile-time constant in
@@ -275,8 +275,7 @@ struct RolloutLane {
 
   // one ply with a known-good action (from an action log the sampler wrote)
   __device__ __forceinline__ void ply_action(int a) {
-    const uint32_t ua = (uint32_t)a;
-    ply_bit(a, ua + (CN ? ua / (uint32_t)CN : mnk_div(ua, g.magic_n)));
+    ply_bit(a, mnk_cell_bit<CN>(g, (uint32_t)a));
   }
 
   __device__ __forceinline__ void ply_bit(int a, uint32_t bit) {

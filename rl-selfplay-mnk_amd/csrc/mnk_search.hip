@@ -103,7 +103,7 @@ k_sample_search(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int
           uint32_t legal[NW];
           env_legal<NW>(g, e, legal);
           const uint32_t bit = (uint32_t)bs_select<NW>(legal, (int)nv.nexp);
-          const int cell = (int)(bit - (CN ? bit / (uint32_t)(CN + 1) : mnk_div(bit, g.magic_stride)));
+          const int cell = mnk_bit_cell<CN>(g, bit);
           const MnkPly ply = env_play<NW, CN, CK, true>(g, e, cell, false);
           const int ch = nodes++;
           if (lane == 0) {
@@ -160,7 +160,7 @@ k_sample_search(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int
       }
       for (int p = 1; p <= depth; ++p) {  // depth p odd: "me" (plane 0) moved into path[p]
         const int cell = node[path[p]].move;
-        const uint32_t bit = (uint32_t)cell + (CN ? (uint32_t)cell / (uint32_t)CN : mnk_div((uint32_t)cell, g.magic_n));
+        const uint32_t bit = mnk_cell_bit<CN>(g, (uint32_t)cell);
         const uint32_t one = 1u << (bit & 31u);
 #pragma unroll
         for (int w = 0; w < NW; ++w) {
@@ -252,17 +252,13 @@ int mnk_sample_search(const void* obs, int obs_dtype, int64_t N, int m, int n, i
                       float c, uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev,
                       int64_t env_id0, int deterministic, int64_t* actions, int32_t* stats, void* stream) {
   MnkGeom g;
-  int rc = mnk_check_geom(m, n, k, &g);
+  int rc = mnk_sample_check(obs, obs_dtype, N, m, n, k, actions, &g);
   if (rc != MNK_OK) return rc;
-  if (!obs || !actions || N < 0 || !mnk_obs_dtype_ok(obs_dtype)) return MNK_EINVAL;
   if (iterations < 1 || iterations > MNK_SEARCH_ITERS_MAX) return MNK_EINVAL;
   if (playouts < 1 || playouts > MNK_SEARCH_PLAYOUTS_MAX) return MNK_EINVAL;
   if (!(c >= 0.0f && c <= 3.0e38f)) return MNK_EINVAL;  // (finite and not negative; NaN fails both)
-  // the Philox position q = u >> 2 of the last ply of the call must fit in 56 bits: (step + 1) * I * B * C4 <= 2^58
-  const uint64_t per_step = (uint64_t)iterations * (uint64_t)playouts * (uint64_t)((g.C + 3) & ~3);  // < 2^30
-  if (step >= ((1ull << 58) / per_step)) return MNK_EINVAL;
-  if (N == 0) return MNK_OK;
-  if (N > 0x7fffffff) return MNK_EINVAL;  // (one workgroup per row: the grid's x dimension)
+  rc = mnk_rows_games_check(step, (uint64_t)iterations * (uint64_t)playouts, g.C, N);  // (I * B games)
+  if (rc != MNK_OK || N == 0) return rc;
   const dim3 grid((unsigned)N), block((unsigned)(64 * ((playouts + 63) / 64)));
   const int depth_max = iterations < g.C ? iterations : g.C;
   const size_t lds = (size_t)(iterations + 1) * sizeof(MnkSearchNode) + (size_t)(depth_max + 2) * sizeof(uint16_t);

@@ -23,9 +23,8 @@ int mnk_sample_tactical(const void* obs, int obs_dtype, int64_t N, int m, int n,
                         const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
                         int64_t* actions, uint8_t* candidates, void* stream) {
   MnkGeom g;
-  int rc = mnk_check_geom(m, n, k, &g);
+  const int rc = mnk_sample_check(obs, obs_dtype, N, m, n, k, actions, &g);
   if (rc != MNK_OK) return rc;
-  if (!obs || !actions || N < 0 || !mnk_obs_dtype_ok(obs_dtype)) return MNK_EINVAL;
   if (N == 0) return MNK_OK;
   const int B = 64;
   const dim3 grid((unsigned)((N + B - 1) / B));

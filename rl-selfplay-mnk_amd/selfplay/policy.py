@@ -150,27 +150,8 @@ class TacticalPolicy(Policy):
 
     def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, candidates=None) -> torch.Tensor:
         """``candidates``: optional uint8 / bool ``[B, m*n]`` tensor that receives the set each row drew from"""
-        observation = obs["observation"]
-        if observation.dim() == 3:
-            observation = observation.unsqueeze(0)
-        if observation.device.type != "cuda":
-            raise RuntimeError("mnk policies sample on the GPU; got an observation on " + str(observation.device))
-        if observation.dtype not in (torch.float32, torch.bfloat16, torch.uint8):
-            observation = observation.to(torch.float32)
-        observation = observation.contiguous()
-        b, two, m, n = observation.shape
-        if two != 2:
-            raise ValueError(f"expected an observation [B, 2, m, n], got {tuple(observation.shape)}")
-        actions = torch.empty(b, dtype=torch.long, device=observation.device)
-        if candidates is not None and (candidates.shape != (b, m * n) or candidates.dtype not in (torch.uint8, torch.bool)
-                                       or not candidates.is_contiguous() or candidates.device != observation.device):
-            raise ValueError(f"candidates must be a contiguous uint8 / bool ({b}, {m * n}) tensor on {observation.device}")
-        if b:
-            mnk_hip.call("mnk_sample_tactical", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, self.k,
-                         *self._sampler.block(deterministic), mnk_hip.ptr(actions), mnk_hip.ptr(candidates),
-                         mnk_hip.stream_ptr(observation.device))
-        self._sampler.advance()
-        return actions
+        return _play(self._sampler, "mnk_sample_tactical", obs, (self.k,), deterministic,
+                     "candidates", candidates, 1, (torch.uint8, torch.bool))
 
 
 def folds_tactical(policy) -> bool:
@@ -192,6 +173,26 @@ def _canonical_observation(obs):
     if observation.dim() != 4 or observation.shape[1] != 2:
         raise ValueError(f"expected an observation [B, 2, m, n], got {tuple(observation.shape)}")
     return observation
+
+
+def _play(sampler, entry, obs, args, deterministic, out_name, out, planes, out_dtypes):
+    """one call of the player ``entry`` on the canonical observation of ``obs``: ``args`` are its arguments after m, n
+    and before the sampler's; ``out`` (``out_name``), optional, is a contiguous ``[B, m*n]`` (``planes`` = 1) or
+    ``[B, planes, m*n]`` tensor of one of ``out_dtypes`` on the observation's device.  Returns the actions."""
+    observation = _canonical_observation(obs)
+    b, _, m, n = observation.shape
+    shape = (b, m * n) if planes == 1 else (b, planes, m * n)
+    if out is not None and (out.shape != shape or out.dtype not in out_dtypes or not out.is_contiguous()
+                            or out.device != observation.device):
+        kinds = " / ".join(str(d).replace("torch.", "") for d in out_dtypes)
+        raise ValueError(f"{out_name} must be a contiguous {kinds} {shape} tensor on {observation.device}")
+    actions = torch.empty(b, dtype=torch.long, device=observation.device)
+    if b:
+        mnk_hip.call(entry, mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, *args,
+                     *sampler.block(deterministic), mnk_hip.ptr(actions), mnk_hip.ptr(out),
+                     mnk_hip.stream_ptr(observation.device))
+    sampler.advance()
+    return actions
 
 
 class MonteCarloPolicy(Policy):
@@ -216,18 +217,8 @@ class MonteCarloPolicy(Policy):
     def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, counts=None) -> torch.Tensor:
         """``counts``: optional int32 ``[B, 2, m*n]`` tensor that receives each row's wins (``[:, 0]``) and losses
         (``[:, 1]``) per cell over its ``playouts`` games (draws = playouts - wins - losses; 0 on occupied cells)"""
-        observation = _canonical_observation(obs)
-        b, _, m, n = observation.shape
-        actions = torch.empty(b, dtype=torch.long, device=observation.device)
-        if counts is not None and (counts.shape != (b, 2, m * n) or counts.dtype != torch.int32
-                                   or not counts.is_contiguous() or counts.device != observation.device):
-            raise ValueError(f"counts must be a contiguous int32 ({b}, 2, {m * n}) tensor on {observation.device}")
-        if b:
-            mnk_hip.call("mnk_sample_playouts", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, self.k,
-                         self.playouts, *self._sampler.block(deterministic), mnk_hip.ptr(actions), mnk_hip.ptr(counts),
-                         mnk_hip.stream_ptr(observation.device))
-        self._sampler.advance()
-        return actions
+        return _play(self._sampler, "mnk_sample_playouts", obs, (self.k, self.playouts), deterministic,
+                     "counts", counts, 2, (torch.int32,))
 
 
 class SearchPolicy(Policy):
@@ -259,18 +250,8 @@ class SearchPolicy(Policy):
         """``stats``: optional int32 ``[B, 3, m*n]`` tensor that receives each row's root visit counts (``[:, 0]``), and
         the wins (``[:, 1]``) and losses (``[:, 2]``) of the side to move through each cell; 0 on occupied cells and on
         cells the search never expanded"""
-        observation = _canonical_observation(obs)
-        b, _, m, n = observation.shape
-        actions = torch.empty(b, dtype=torch.long, device=observation.device)
-        if stats is not None and (stats.shape != (b, 3, m * n) or stats.dtype != torch.int32
-                                  or not stats.is_contiguous() or stats.device != observation.device):
-            raise ValueError(f"stats must be a contiguous int32 ({b}, 3, {m * n}) tensor on {observation.device}")
-        if b:
-            mnk_hip.call("mnk_sample_search", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, self.k,
-                         self.iterations, self.playouts, self.c, *self._sampler.block(deterministic),
-                         mnk_hip.ptr(actions), mnk_hip.ptr(stats), mnk_hip.stream_ptr(observation.device))
-        self._sampler.advance()
-        return actions
+        return _play(self._sampler, "mnk_sample_search", obs, (self.k, self.iterations, self.playouts, self.c),
+                     deterministic, "stats", stats, 3, (torch.int32,))
 
 
 class NNPolicy(Policy):

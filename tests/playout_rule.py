@@ -14,23 +14,11 @@ next ply.  All games of a call are played together, vectorised over (row, cell, 
 end.
 """
 import numpy as np
-import torch
 
 from oracle import philox
+from tactical_rule import _DIRS, _as_bool, _shift
 
 STREAM_PLAYOUT = 4  # MNK_STREAM_PLAYOUT of include/mnk_hip.h
-_DIRS = ((0, 1), (1, 0), (1, 1), (1, -1))
-
-
-def _shift(a, dr, dc):
-    """out[:, r, c] = a[:, r + dr, c + dc], False outside the board"""
-    out = np.zeros_like(a)
-    _, m, n = a.shape
-    r0, r1 = max(0, -dr), min(m, m - dr)
-    c0, c1 = max(0, -dc), min(n, n - dc)
-    if r0 < r1 and c0 < c1:
-        out[:, r0:r1, c0:c1] = a[:, r0 + dr:r1 + dr, c0 + dc:c1 + dc]
-    return out
 
 
 def has_run(plane: np.ndarray, k: int) -> np.ndarray:
@@ -44,10 +32,31 @@ def has_run(plane: np.ndarray, k: int) -> np.ndarray:
     return hit
 
 
-def _as_bool(obs) -> np.ndarray:
-    if isinstance(obs, torch.Tensor):
-        obs = obs.float().cpu().numpy()
-    return np.asarray(obs) != 0
+def random_games(flat, side0, live, m: int, n: int, k: int, seed: int, env, base, stream: int):
+    """Plays the games ``live`` (indices into ``flat``, bool [G, 2, C], updated in place) to their ends, all together: at
+    its ply t a game's mover, side ``(side0 + t) & 1``, plays ``oracle.philox.pick_legal`` over the free cells with the
+    u32 of ``u = base + t`` on ``stream`` (``side0`` / ``env`` / ``base``: per game).  A game ends at the first ply after
+    which the mover has a run of >= k on its whole plane, or when the board is full; it leaves the batch then.
+    Returns (winner int64 [G]: 1 + the side that won, 0 for a draw or a game not played here; plies played)."""
+    C = m * n
+    winner = np.zeros(len(flat), np.int64)
+    t = played = 0
+    while len(live):
+        played += len(live)
+        sub = flat[live]
+        mover = (side0[live] + t) & 1
+        free = ~(sub[:, 0] | sub[:, 1])
+        x = philox.rand_u32(seed, env[live], base[live] + np.uint64(t), stream)
+        a = philox.pick_legal(free, x)
+        idx = np.arange(len(live))
+        sub[idx, mover, a] = True
+        flat[live] = sub
+        won = has_run(sub[idx, mover].reshape(len(live), m, n), k)
+        winner[live[won]] = 1 + mover[won]
+        full = sub[:, 0].sum(1) + sub[:, 1].sum(1) >= C
+        live = live[~won & ~full]
+        t += 1
+    return winner, played
 
 
 def playout_counts(obs, k: int, P: int, seed: int, step: int = 0, env_id0: int = 0, plies: list = None):
@@ -75,31 +84,16 @@ def playout_counts(obs, k: int, P: int, seed: int, step: int = 0, env_id0: int =
     planes = obs[g_row].copy()
     flat = planes.reshape(G, 2, C)
     flat[np.arange(G), 0, g_cell] = True
-    outcome = np.zeros(G, dtype=np.int64)                     # +1 win, -1 loss, 0 draw (for "me")
     won = has_run(planes[:, 0], k)
-    outcome[won] = 1
     full = flat[:, 0].sum(1) + flat[:, 1].sum(1) >= C
-    live = np.flatnonzero(~won & ~full)
-    t = 0
-    played = G
-    while len(live):
-        played += len(live)
-        mover = 1 if t % 2 == 0 else 0                        # t even: the other side, t odd: "me"
-        sub = flat[live]
-        free = ~(sub[:, 0] | sub[:, 1])
-        x = philox.rand_u32(seed, env[live], base[live] + np.uint64(t), STREAM_PLAYOUT)
-        a = philox.pick_legal(free, x)
-        sub[np.arange(len(live)), mover, a] = True
-        flat[live] = sub
-        won = has_run(sub[:, mover].reshape(len(live), m, n), k)
-        outcome[live[won]] = 1 if mover == 0 else -1
-        full = sub[:, 0].sum(1) + sub[:, 1].sum(1) >= C
-        live = live[~won & ~full]
-        t += 1
+    # t = 0: the other side (side 1) replies
+    winner, played = random_games(flat, np.ones(G, np.int64), np.flatnonzero(~won & ~full), m, n, k, seed, env, base,
+                                  STREAM_PLAYOUT)
+    winner[won] = 1
     if plies is not None:
-        plies.append(played)
-    np.add.at(wins, (g_row, g_cell), outcome == 1)
-    np.add.at(losses, (g_row, g_cell), outcome == -1)
+        plies.append(G + played)
+    np.add.at(wins, (g_row, g_cell), winner == 1)
+    np.add.at(losses, (g_row, g_cell), winner == 2)
     return wins, losses
 
 

@@ -7,14 +7,14 @@ it.  Depth d of a node = number of moves from the root; the mover into a node of
 Iteration it: every row walks from its root -- expanding the first untried legal cell of the first node that has one,
 else descending to the child of maximal ``q + c * sqrt(n_v / n_child)`` in numpy float32 (each operation rounded on its
 own), ties to the lowest cell -- then all rows' non-terminal leaves play their B random games together, vectorised over
-(row, playout), with ``oracle.philox.pick_legal`` and the u32 of ``u = (((step * I + it) * B + j) * C4) + t`` on stream
-SEARCH; the win test is ``playout_rule.has_run`` over the mover's whole plane.  Backup adds B visits and the outcomes to
-every node of the path.
+(row, playout), by ``playout_rule.random_games`` with the u32 of ``u = (((step * I + it) * B + j) * C4) + t`` on stream
+SEARCH.  Backup adds B visits and the outcomes to every node of the path.
 """
 import numpy as np
 
 from oracle import philox
-from playout_rule import _as_bool, has_run
+from playout_rule import has_run, random_games
+from tactical_rule import _as_bool
 
 STREAM_SEARCH = 5  # MNK_STREAM_SEARCH of include/mnk_hip.h
 
@@ -86,25 +86,8 @@ def _playouts(leaves, B, m, n, k, seed, env, base):
     G = L * B
     flat = np.stack([leaves[i][0] for i in g_leaf])     # [G, 2, C]
     side0 = np.array([leaves[i][1] & 1 for i in g_leaf])
-    g_env = env[g_leaf]
     g_base = base[g_leaf] + g_j * np.uint64(C4)
-    outcome = np.zeros(G, np.int64)                     # 1: "me" won, 2: the other side won, 0: a draw
-    live = np.arange(G)
-    t = 0
-    while len(live):
-        sub = flat[live]
-        mover = (side0[live] + t) & 1
-        free = ~(sub[:, 0] | sub[:, 1])
-        x = philox.rand_u32(seed, g_env[live], g_base[live] + np.uint64(t), STREAM_SEARCH)
-        a = philox.pick_legal(free, x)
-        idx = np.arange(len(live))
-        sub[idx, mover, a] = True
-        flat[live] = sub
-        won = has_run(sub[idx, mover].reshape(len(live), m, n), k)
-        outcome[live[won]] = 1 + mover[won]
-        full = sub[:, 0].sum(1) + sub[:, 1].sum(1) >= C
-        live = live[~won & ~full]
-        t += 1
+    outcome, _ = random_games(flat, side0, np.arange(G), m, n, k, seed, env[g_leaf], g_base, STREAM_SEARCH)
     np.add.at(wm, g_leaf, outcome == 1)
     np.add.at(wo, g_leaf, outcome == 2)
     return wm, wo

@@ -25,6 +25,12 @@ def _shift(a, dr, dc):
     return out
 
 
+def _as_bool(obs) -> np.ndarray:
+    if isinstance(obs, torch.Tensor):
+        obs = obs.float().cpu().numpy()
+    return np.asarray(obs) != 0
+
+
 def completions(stones: np.ndarray, empty: np.ndarray, k: int) -> np.ndarray:
     """bool [B, m, n]: the empty cells where one more stone of ``stones`` makes a run of >= k through that cell"""
     stones = np.asarray(stones, dtype=bool)
@@ -43,9 +49,7 @@ def completions(stones: np.ndarray, empty: np.ndarray, k: int) -> np.ndarray:
 def tactical_sets(obs, k: int):
     """obs: [B, 2, m, n] canonical view (channel 0 = the side to move; non-zero = stone), numpy or torch.
     Returns (S, W, B) as bool [B, C]"""
-    if isinstance(obs, torch.Tensor):
-        obs = obs.float().cpu().numpy()
-    obs = np.asarray(obs) != 0
+    obs = _as_bool(obs)
     b, _, m, n = obs.shape
     mine, theirs = obs[:, 0], obs[:, 1]
     legal = ~(mine | theirs)

@@ -13,36 +13,11 @@ from oracle import philox
 from oracle.env_torch import OracleVectorEnv
 from oracle.packing import pack_boards, unpack_boards
 from oracle.selfplay_torch import OracleSelfPlay
+from player_cases import DEV, hip  # noqa: F401 (hip: the fixture)
 from tactical_rule import PhiloxTacticalOpponent, random_positions, tactical_moves, tactical_sets
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 OBS_DTYPES = (torch.float32, torch.bfloat16, torch.uint8)
-
-
-@pytest.fixture(scope="module")
-def hip():
-    import __graft_entry__ as entry
-
-    entry.build_hip()
-    entry._ensure_path()
-    import mnk_hip
-    from alg.rollout_buffer import RolloutBuffer
-    from env.torch_vector_mnk_env import TorchVectorMnkEnv
-    from selfplay import graphed, policy, validation
-    from selfplay.torch_self_play_wrapper import TorchSelfPlayWrapper
-
-    mnk_hip.load()
-    assert torch.cuda.is_available()
-
-    class NS:
-        pass
-
-    ns = NS()
-    ns.lib, ns.Env, ns.Wrapper, ns.policy, ns.graphed, ns.validation = (mnk_hip, TorchVectorMnkEnv, TorchSelfPlayWrapper,
-                                                                        policy, graphed, validation)
-    ns.Buffer = RolloutBuffer
-    return ns
 
 
 @pytest.fixture

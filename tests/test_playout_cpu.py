@@ -3,33 +3,14 @@ own win test (tests/golden/tactical_positions.npz: a cell where the side to move
 always lies in S) and hand-built positions; the C ABI of ``mnk_sample_playouts`` (header, binding, host argument checks,
 which reject before anything is enqueued)."""
 import os
-import re
 
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from oracle import philox
 from oracle.packing import unpack_boards
+from player_cases import board, check_header_and_binding, header_constants, lib  # noqa: F401 (lib: the fixture)
 from playout_rule import STREAM_PLAYOUT, best_sets, has_run, playout_counts, playout_moves
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mnk_hip.h")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    entry.build_hip()
-    entry._ensure_path()
-    import mnk_hip
-
-    return mnk_hip
-
-
-def board(rows):
-    """canonical observation [1, 2, m, n] from strings: 'x' = side to move, 'o' = the other side, '.' = empty"""
-    a = np.array([list(r) for r in rows])
-    return np.stack([(a == "x"), (a == "o")]).astype(np.float32)[None]
 
 
 # ----------------------------------------------------------------------------- the rule against the reference
@@ -141,13 +122,9 @@ def test_tic_tac_toe_centre_is_best_on_an_empty_board():
 
 # ----------------------------------------------------------------------------- the C ABI
 def test_header_declares_mnk_sample_playouts_and_the_binding_matches(lib):
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    decl = re.search(r"\bint\s+mnk_sample_playouts\s*\(([^;]*?)\)\s*;", text, flags=re.S)
-    assert decl
-    assert len([a for a in decl.group(1).split(",") if a.strip()]) == len(lib.SIGNATURES["mnk_sample_playouts"])
-    assert hasattr(lib.load(), "mnk_sample_playouts")
-    assert lib.load().mnk_abi_version() == 6 and lib.ABI_VERSION == 6 and lib.JIT_API_COUNT == 24
-    consts = dict(re.findall(r"#define (MNK_\w+) (\d+)", open(HEADER).read()))
+    check_header_and_binding(lib, "mnk_sample_playouts")
+    assert lib.JIT_API_COUNT == 24
+    consts = header_constants()
     assert consts["MNK_STREAM_PLAYOUT"] == "4" == str(lib.STREAM_PLAYOUT)
     assert consts["MNK_PLAYOUTS_MAX"] == "4096" == str(lib.PLAYOUTS_MAX)
 

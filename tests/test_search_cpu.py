@@ -1,33 +1,12 @@
 """CPU: the tree-search player -- the numpy restatement of the rule in tests/search_rule.py on hand-built positions (wins
 in one, a forced block, the visit total, finished and full rows); the C ABI of ``mnk_sample_search`` (header, binding,
 host argument checks, which reject before anything is enqueued); ``SearchPolicy``'s argument checks."""
-import os
-import re
-
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from oracle import philox
+from player_cases import board, check_header_and_binding, header_constants, lib  # noqa: F401 (lib: the fixture)
 from search_rule import STREAM_SEARCH, search
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mnk_hip.h")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    entry.build_hip()
-    entry._ensure_path()
-    import mnk_hip
-
-    return mnk_hip
-
-
-def board(rows):
-    """canonical observation [1, 2, m, n] from strings: 'x' = side to move, 'o' = the other side, '.' = empty"""
-    a = np.array([list(r) for r in rows])
-    return np.stack([(a == "x"), (a == "o")]).astype(np.float32)[None]
 
 
 def legal_count(obs):
@@ -124,13 +103,8 @@ def test_deterministic_and_sampled_pick_from_the_most_visited():
 
 # ----------------------------------------------------------------------------- the C ABI
 def test_header_declares_mnk_sample_search_and_the_binding_matches(lib):
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    decl = re.search(r"\bint\s+mnk_sample_search\s*\(([^;]*?)\)\s*;", text, flags=re.S)
-    assert decl
-    assert len([a for a in decl.group(1).split(",") if a.strip()]) == len(lib.SIGNATURES["mnk_sample_search"])
-    assert hasattr(lib.load(), "mnk_sample_search")
-    assert lib.load().mnk_abi_version() == 6 and lib.ABI_VERSION == 6
-    consts = dict(re.findall(r"#define (MNK_\w+) (\d+)", open(HEADER).read()))
+    check_header_and_binding(lib, "mnk_sample_search")
+    consts = header_constants()
     assert consts["MNK_STREAM_SEARCH"] == "5" == str(lib.STREAM_SEARCH)
     assert consts["MNK_SEARCH_ITERS_MAX"] == "2048" == str(lib.SEARCH_ITERS_MAX)
     assert consts["MNK_SEARCH_PLAYOUTS_MAX"] == "256" == str(lib.SEARCH_PLAYOUTS_MAX)

@@ -7,29 +7,12 @@ import os
 import numpy as np
 import pytest
 
-import __graft_entry__ as entry
 from oracle import philox
 from oracle.packing import unpack_boards
+from player_cases import board, check_header_and_binding, header_constants, lib  # noqa: F401 (lib: the fixture)
 from tactical_rule import completions, tactical_moves, tactical_sets
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEADER = os.path.join(ROOT, "include", "mnk_hip.h")
 NEW = ("mnk_selfplay_step_tactical", "mnk_selfplay_step_tactical_logits", "mnk_sample_tactical")
-
-
-@pytest.fixture(scope="module")
-def lib():
-    entry.build_hip()
-    entry._ensure_path()
-    import mnk_hip
-
-    return mnk_hip
-
-
-def board(rows):
-    """canonical observation [1, 2, m, n] from strings: 'x' = side to move, 'o' = the other side, '.' = empty"""
-    a = np.array([list(r) for r in rows])
-    return np.stack([(a == "x"), (a == "o")]).astype(np.float32)[None]
 
 
 def cells(mask_row, n):
@@ -150,22 +133,13 @@ def test_completions_match_brute_force():
 
 # ----------------------------------------------------------------------------- the C ABI
 def test_header_declares_the_tactical_entry_points_and_the_binding_matches(lib):
-    import re
-
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
     for name in NEW:
-        decl = re.search(r"\bint\s+" + name + r"\s*\(([^;]*?)\)\s*;", text, flags=re.S)
-        assert decl, name
-        assert len([a for a in decl.group(1).split(",") if a.strip()]) == len(lib.SIGNATURES[name]), name
+        check_header_and_binding(lib, name)
     assert lib.SIGNATURES["mnk_selfplay_step_tactical"] == lib.SIGNATURES["mnk_selfplay_step_random"]
     assert lib.SIGNATURES["mnk_selfplay_step_tactical_logits"] == lib.SIGNATURES["mnk_selfplay_step_random_logits"]
-    handle = lib.load()
-    for name in NEW:
-        assert hasattr(handle, name)
-    assert handle.mnk_abi_version() == 6 and lib.ABI_VERSION == 6
     assert (lib.JIT_API_SP_TACTICAL, lib.JIT_API_SP_TACTICAL_DRAW, lib.JIT_API_SAMPLE_TACTICAL, lib.JIT_API_COUNT) == (19, 20, 23, 24)
     assert lib.jit_api_tactical_draw_kind(None) == 22
-    consts = dict(re.findall(r"#define (MNK_JIT_API_\w+) (\d+)", open(HEADER).read()))
+    consts = header_constants()
     assert consts["MNK_JIT_API_SP_TACTICAL"] == "19" and consts["MNK_JIT_API_SAMPLE_TACTICAL"] == "23"
     assert consts["MNK_JIT_API_COUNT"] == "24"
 
