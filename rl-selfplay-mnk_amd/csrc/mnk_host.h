@@ -263,19 +263,10 @@ void mnk_launch_rollout_ws(const MnkGeom& g, int ws, uint64_t* planes, uint32_t*
     if (MNK_BUILTIN(g, MnkRow_::C > 256, __VA_ARGS__)) break;     \
     MNK_CASE(16, 0, 0, __VA_ARGS__)                               \
   } while (0)
-hipFunction_t mnk_jit_replay_function(const MnkGeom& g, bool rec, int act);
-hipFunction_t mnk_jit_rollout_pair_function(const MnkGeom& g, bool rec, int act);
-int mnk_jit_launch_rollout_lanes(hipFunction_t fn, MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                                 uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                                 void* act_log, void* stream, int lanes_per_env);
-int mnk_jit_launch_replay(hipFunction_t fn, MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, const void* act_log,
-                          uint64_t* rec_planes, uint32_t* rec_meta, int32_t* err, void* stream);
 
-// run-time specialised rollout kernels (mnk_jit.hip, hiprtc): nullptr when the compile failed
-hipFunction_t mnk_jit_rollout_function(const MnkGeom& g, bool rec, int act, bool saddr);
-int mnk_jit_launch_rollout(hipFunction_t fn, MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                           uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                           void* act_log, void* stream);
+// run-time specialised rollout kernels (mnk_jit.hip, hiprtc): kind MNK_JIT_ROLLOUT / _REPLAY / _ROLLOUT_PAIR; nullptr when
+// the compile failed.  Launched with mnk_module_launch.
+hipFunction_t mnk_jit_rollout_function(const MnkGeom& g, int kind, bool rec, int act, bool saddr);
 
 // two lanes per env with the board split by words (mnk_rollout_pairw.hip): the five-in-a-row boards of MNK_BUILTIN_BOARDS
 bool mnk_rollout_pairw_supported(const MnkGeom& g);

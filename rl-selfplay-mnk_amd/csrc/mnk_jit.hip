@@ -30,11 +30,12 @@ struct Compiled {
   hipFunction_t fn = nullptr;
   size_t code_bytes = 0;
   bool failed = false;
+  uint64_t launches = 0, items = 0;  // (API kinds: how hot the kernel is, mnk_jit_api_function)
 };
 
 std::mutex g_mu;
-// (device, m, n, k, record, log format, saddr, kind: 0 rollout / 1 replay)
-std::map<std::tuple<int, int, int, int, int, int, int, int>, Compiled> g_cache;
+// (device, m, kernel template-id): every run-time kernel, rollout and API kinds alike; m keeps each board's own entry
+std::map<std::tuple<int, int, std::string>, Compiled> g_cache;
 thread_local char g_jit_err[2048] = "";
 
 // ---- code objects on disk -------------------------------------------------------------------------------------------
@@ -149,38 +150,45 @@ uint64_t compile_key(const char* program, const char* const* opts, int nopts, co
   return fnv1a(k, expr);
 }
 
-// compiles the rollout (kind 0) or the replay kernel (kind 1) for this geometry; code object bytes in `code` (no GPU
-// needed for this part)
-bool compile(const MnkGeom& g, bool rec, int act, bool saddr, std::vector<char>& code, int kind = 0) {
-  static const char* program =
-      "#include \"mnk_rollout_lane.h\"\n";
+// the two programs: each run-time kernel is a template of one of these embedded headers
+const char* const kRolloutProgram = "#include \"mnk_rollout_lane.h\"\n";
+const char* const kApiProgram = "#include \"mnk_selfplay_kernels.h\"\n";  // (includes mnk_api_kernels.h)
+
+// compiles the one kernel `name` names (a template-id, e.g. "k_step_full<5, 12, 5, false>") from `program`, as a hiprtc
+// name expression (no GPU needed): code object in `code`, mangled name in `lowered`
+bool compile(const char* program, const std::string& name, std::vector<char>& code, std::string& lowered) {
   hiprtcProgram prog = nullptr;
-  if (hiprtcCreateProgram(&prog, program, "mnk_jit_rollout.hip", MNK_JIT_HEADER_COUNT, mnk_jit_header_texts,
+  if (hiprtcCreateProgram(&prog, program, "mnk_jit.hip", MNK_JIT_HEADER_COUNT, mnk_jit_header_texts,
                           mnk_jit_header_names) != HIPRTC_SUCCESS) {
     snprintf(g_jit_err, sizeof(g_jit_err), "hiprtcCreateProgram failed");
     return false;
   }
-  const std::string d_nw = "-DMNK_JIT_NW=" + std::to_string(g.NW), d_cn = "-DMNK_JIT_CN=" + std::to_string(g.n),
-                    d_ck = "-DMNK_JIT_CK=" + std::to_string(g.k), d_rec = "-DMNK_JIT_REC=" + std::to_string(rec ? 1 : 0),
-                    d_act = "-DMNK_JIT_ACT=" + std::to_string(act), d_sa = "-DMNK_JIT_SADDR=" + std::to_string(saddr ? 1 : 0),
-                    d_kind = "-DMNK_JIT_KIND=" + std::to_string(kind);
-  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", d_nw.c_str(), d_cn.c_str(),
-                        d_ck.c_str(), d_rec.c_str(), d_act.c_str(), d_sa.c_str(), d_kind.c_str()};
+  const std::string expr = "&" + name;
+  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
   const int nopts = (int)(sizeof(opts) / sizeof(opts[0]));
-  const uint64_t key = compile_key(program, opts, nopts, "");
-  std::string no_name;
-  if (cache_load(key, code, no_name)) { hiprtcDestroyProgram(&prog); return true; }
-  const hiprtcResult rc = hiprtcCompileProgram(prog, nopts, opts);
-  if (rc != HIPRTC_SUCCESS) {
+  const uint64_t key = compile_key(program, opts, nopts, expr);
+  if (cache_load(key, code, lowered)) { hiprtcDestroyProgram(&prog); return true; }
+  bool ok = hiprtcAddNameExpression(prog, expr.c_str()) == HIPRTC_SUCCESS;
+  hiprtcResult rc = HIPRTC_SUCCESS;
+  if (ok) rc = hiprtcCompileProgram(prog, nopts, opts);
+  if (!ok || rc != HIPRTC_SUCCESS) {
     g_stat_failed++;
     size_t n = 0;
     hiprtcGetProgramLogSize(prog, &n);
     std::string log(n, '\0');
     if (n) hiprtcGetProgramLog(prog, &log[0]);
-    snprintf(g_jit_err, sizeof(g_jit_err), "hiprtc: %s\n%.1800s", hiprtcGetErrorString(rc), log.c_str());
+    snprintf(g_jit_err, sizeof(g_jit_err), "hiprtc (%s): %s\n%.1700s", expr.c_str(), ok ? hiprtcGetErrorString(rc) : "name expression rejected",
+             log.c_str());
     hiprtcDestroyProgram(&prog);
     return false;
   }
+  const char* lowered_name = nullptr;
+  if (hiprtcGetLoweredName(prog, expr.c_str(), &lowered_name) != HIPRTC_SUCCESS || !lowered_name) {
+    snprintf(g_jit_err, sizeof(g_jit_err), "hiprtcGetLoweredName(%s) failed", expr.c_str());
+    hiprtcDestroyProgram(&prog);
+    return false;
+  }
+  lowered = lowered_name;
   size_t n = 0;
   hiprtcGetCodeSize(prog, &n);
   code.resize(n);
@@ -188,26 +196,27 @@ bool compile(const MnkGeom& g, bool rec, int act, bool saddr, std::vector<char>&
   hiprtcDestroyProgram(&prog);
   if (n > 0) {
     g_stat_compiled++;
-    cache_store(key, code, no_name);
+    cache_store(key, code, lowered);
   }
   return n > 0;
 }
 
-}  // namespace
-
-// kernel of this geometry, compiled on first use; nullptr (and mnk_jit_last_error) when that failed -- the caller
-// then stays on the ahead-of-time generic kernel
-static hipFunction_t jit_function(const MnkGeom& g, bool rec, int act, bool saddr, int kind) {
-  int device = 0;
-  if (hipGetDevice(&device) != hipSuccess) return nullptr;  // a code object is loaded into one device's context
-  std::lock_guard<std::mutex> lock(g_mu);
-  Compiled& c = g_cache[std::make_tuple(device, g.m, g.n, g.k, rec ? 1 : 0, act, saddr ? 1 : 0, kind)];
-  if (c.fn || c.failed) return c.fn;
+// compiles (does not load) one kernel: code object size in bytes, or MNK_ELAUNCH (mnk_jit_last_error says why)
+int64_t compiled_size(const char* program, const std::string& name) {
   std::vector<char> code;
-  if (!compile(g, rec, act, saddr, code, kind)) { c.failed = true; return nullptr; }
+  std::string lowered;
+  return compile(program, name, code, lowered) ? (int64_t)code.size() : MNK_ELAUNCH;
+}
+
+// compile + load on the current device (g_mu held); nullptr (and mnk_jit_last_error) when that failed -- the entry then
+// stays failed, and the caller on the ahead-of-time kernel
+hipFunction_t build(Compiled& c, const char* program, const std::string& name) {
+  std::vector<char> code;
+  std::string lowered;
+  if (!compile(program, name, code, lowered)) { c.failed = true; return nullptr; }
   if (hipModuleLoadData(&c.module, code.data()) != hipSuccess ||
-      hipModuleGetFunction(&c.fn, c.module, kind == 1 ? "mnk_jit_replay" : (kind == 2 ? "mnk_jit_rollout_pair" : "mnk_jit_rollout")) != hipSuccess) {
-    snprintf(g_jit_err, sizeof(g_jit_err), "hipModuleLoadData / hipModuleGetFunction failed: %s",
+      hipModuleGetFunction(&c.fn, c.module, lowered.c_str()) != hipSuccess) {
+    snprintf(g_jit_err, sizeof(g_jit_err), "hipModuleLoadData / hipModuleGetFunction(%s) failed: %s", lowered.c_str(),
              hipGetErrorString(hipGetLastError()));
     c.failed = true;
     c.fn = nullptr;
@@ -217,42 +226,27 @@ static hipFunction_t jit_function(const MnkGeom& g, bool rec, int act, bool sadd
   return c.fn;
 }
 
-hipFunction_t mnk_jit_rollout_function(const MnkGeom& g, bool rec, int act, bool saddr) {
-  return jit_function(g, rec, act, saddr, 0);
+// the rollout-family kernel of this geometry: kind MNK_JIT_ROLLOUT (one lane per env; saddr: 32-bit record offsets),
+// MNK_JIT_REPLAY (act = the log format it reads) or MNK_JIT_ROLLOUT_PAIR (two lanes per env)
+std::string rollout_kernel_name(const MnkGeom& g, int kind, bool rec, int act, bool saddr) {
+  const std::string args = std::to_string(g.NW) + ", " + std::to_string(g.n) + ", " + std::to_string(g.k) + ", " +
+                           (rec ? "true, " : "false, ") + std::to_string(act);
+  if (kind == MNK_JIT_REPLAY) return "k_replay_actions<" + args + ">";
+  if (kind == MNK_JIT_ROLLOUT_PAIR) return "k_rollout_random_pair<" + args + ">";
+  return "k_rollout_random<" + args + (saddr ? ", true>" : ", false>");
 }
 
-// the two-lanes-per-env form of the rollout (batches of up to 32 768 envs; byte / 16-bit logs or none)
-hipFunction_t mnk_jit_rollout_pair_function(const MnkGeom& g, bool rec, int act) { return jit_function(g, rec, act, false, 2); }
+}  // namespace
 
-// the replay of an action log in format `act` (boards of more than 16 register words have no ahead-of-time variant)
-hipFunction_t mnk_jit_replay_function(const MnkGeom& g, bool rec, int act) { return jit_function(g, rec, act, false, 1); }
-
-int mnk_jit_launch_replay(hipFunction_t fn, MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, const void* act_log,
-                          uint64_t* rec_planes, uint32_t* rec_meta, int32_t* err, void* stream) {
-  void* args[] = {&g, &planes, &meta, &N, &T, &act_log, &rec_planes, &rec_meta, &err};
-  const unsigned grid = (unsigned)((N + 63) / 64);
-  if (hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess)
-    return mnk_launch_status("replay_actions (run-time specialised)");
-  return MNK_OK;
-}
-
-int mnk_jit_launch_rollout(hipFunction_t fn, MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                           uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                           void* act_log, void* stream) {
-  return mnk_jit_launch_rollout_lanes(fn, g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta, stats, act_log,
-                                      stream, 1);
-}
-
-// lanes_per_env: 1 (64 envs per workgroup) or 2 (the pair form: 32 envs per workgroup)
-int mnk_jit_launch_rollout_lanes(hipFunction_t fn, MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                                 uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                                 void* act_log, void* stream, int lanes_per_env) {
-  void* args[] = {&g, &planes, &meta, &N, &T, &seed, &step0, &env_id0, &rec_planes, &rec_meta, &stats, &act_log};
-  const int per_group = 64 / lanes_per_env;
-  const unsigned grid = (unsigned)((N + per_group - 1) / per_group);
-  if (hipModuleLaunchKernel(fn, grid, 1, 1, 64, 1, 1, 0, (hipStream_t)stream, args, nullptr) != hipSuccess)
-    return mnk_launch_status("rollout_random (run-time specialised)");
-  return MNK_OK;
+// rollout-family kernel of this geometry, compiled and loaded on first use (no hotness count, no capture check: the caller
+// decides when a board is worth it); nullptr (and mnk_jit_last_error) when that failed
+hipFunction_t mnk_jit_rollout_function(const MnkGeom& g, int kind, bool rec, int act, bool saddr) {
+  int device = 0;
+  if (hipGetDevice(&device) != hipSuccess) return nullptr;  // a code object is loaded into one device's context
+  const std::string name = rollout_kernel_name(g, kind, rec, act, saddr);
+  std::lock_guard<std::mutex> lock(g_mu);
+  Compiled& c = g_cache[std::make_tuple(device, g.m, name)];
+  return c.fn || c.failed ? c.fn : build(c, kRolloutProgram, name);
 }
 
 // ------------------------------------------------------------------ API-level kernels (round 4)
@@ -263,13 +257,6 @@ int mnk_jit_launch_rollout_lanes(hipFunction_t fn, MnkGeom g, uint64_t* planes, 
 // -- one kernel per program, named by a hiprtc name expression -- which also puts the board on the packed write-out
 // (mnk_emit.h) and lets the self-play step kernels fold the masked draw in for ANY row width (mnk_draw::Shape).
 namespace {
-
-struct ApiEntry {
-  Compiled c;
-  uint64_t launches = 0, items = 0;
-};
-// (device, m, n, k or 0, kind)
-std::map<std::tuple<int, int, int, int, int>, ApiEntry> g_api_cache;
 
 // the template-id of API kernel `kind` on this board, e.g. "k_step_full<5, 12, 5, false>"
 std::string api_kernel_name(const MnkGeom& g, int kind) {
@@ -296,73 +283,9 @@ std::string api_kernel_name(const MnkGeom& g, int kind) {
   return std::string(which[d % 3]) + "<" + geo + ", Draw<" + lts[d / 3] + ", " + std::to_string(g.C) + "> >";
 }
 
-// compiles API kernel `kind` for this geometry (no GPU needed): code object in `code`, mangled name in `lowered`
-bool compile_api(const MnkGeom& g, int kind, std::vector<char>& code, std::string& lowered) {
-  static const char* program = "#include \"mnk_selfplay_kernels.h\"\n";  // (includes mnk_api_kernels.h)
-  hiprtcProgram prog = nullptr;
-  if (hiprtcCreateProgram(&prog, program, "mnk_jit_api.hip", MNK_JIT_HEADER_COUNT, mnk_jit_header_texts,
-                          mnk_jit_header_names) != HIPRTC_SUCCESS) {
-    snprintf(g_jit_err, sizeof(g_jit_err), "hiprtcCreateProgram failed");
-    return false;
-  }
-  const std::string expr = "&" + api_kernel_name(g, kind);
-  const char* opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off"};
-  const int nopts = (int)(sizeof(opts) / sizeof(opts[0]));
-  const uint64_t key = compile_key(program, opts, nopts, expr);
-  if (cache_load(key, code, lowered)) { hiprtcDestroyProgram(&prog); return true; }
-  bool ok = hiprtcAddNameExpression(prog, expr.c_str()) == HIPRTC_SUCCESS;
-  hiprtcResult rc = HIPRTC_SUCCESS;
-  if (ok) rc = hiprtcCompileProgram(prog, nopts, opts);
-  if (!ok || rc != HIPRTC_SUCCESS) {
-    g_stat_failed++;
-    size_t n = 0;
-    hiprtcGetProgramLogSize(prog, &n);
-    std::string log(n, '\0');
-    if (n) hiprtcGetProgramLog(prog, &log[0]);
-    snprintf(g_jit_err, sizeof(g_jit_err), "hiprtc (%s): %s\n%.1700s", expr.c_str(), ok ? hiprtcGetErrorString(rc) : "name expression rejected",
-             log.c_str());
-    hiprtcDestroyProgram(&prog);
-    return false;
-  }
-  const char* name = nullptr;
-  if (hiprtcGetLoweredName(prog, expr.c_str(), &name) != HIPRTC_SUCCESS || !name) {
-    snprintf(g_jit_err, sizeof(g_jit_err), "hiprtcGetLoweredName(%s) failed", expr.c_str());
-    hiprtcDestroyProgram(&prog);
-    return false;
-  }
-  lowered = name;
-  size_t n = 0;
-  hiprtcGetCodeSize(prog, &n);
-  code.resize(n);
-  hiprtcGetCode(prog, code.data());
-  hiprtcDestroyProgram(&prog);
-  if (n > 0) {
-    g_stat_compiled++;
-    cache_store(key, code, lowered);
-  }
-  return n > 0;
-}
-
 bool api_kind_ok(const MnkGeom& g, int kind) {
   if (kind < 0 || kind >= MNK_JK_COUNT) return false;
   return kind < MNK_JK_SP_DRAW || g.C <= 1024;
-}
-
-// compile + load on the current device (g_mu held)
-hipFunction_t api_build(ApiEntry& e, const MnkGeom& g, int kind) {
-  std::vector<char> code;
-  std::string lowered;
-  if (!compile_api(g, kind, code, lowered)) { e.c.failed = true; return nullptr; }
-  if (hipModuleLoadData(&e.c.module, code.data()) != hipSuccess ||
-      hipModuleGetFunction(&e.c.fn, e.c.module, lowered.c_str()) != hipSuccess) {
-    snprintf(g_jit_err, sizeof(g_jit_err), "hipModuleLoadData / hipModuleGetFunction(%s) failed: %s", lowered.c_str(),
-             hipGetErrorString(hipGetLastError()));
-    e.c.failed = true;
-    e.c.fn = nullptr;
-    return nullptr;
-  }
-  e.c.code_bytes = code.size();
-  return e.c.fn;
 }
 
 }  // namespace
@@ -372,9 +295,10 @@ hipFunction_t mnk_jit_api_function(const MnkGeom& g, int kind, int64_t items, hi
   if (jit == 0 || mnk_geom_builtin(g.n, g.k, g.NW) || !api_kind_ok(g, kind)) return nullptr;
   int device = 0;
   if (hipGetDevice(&device) != hipSuccess) return nullptr;
+  const std::string name = api_kernel_name(g, kind);
   std::lock_guard<std::mutex> lock(g_mu);
-  ApiEntry& e = g_api_cache[std::make_tuple(device, g.m, g.n, mnk_jit_kind_any_k(kind) ? 0 : g.k, kind)];
-  if (e.c.fn || e.c.failed) return e.c.fn;
+  Compiled& e = g_cache[std::make_tuple(device, g.m, name)];
+  if (e.fn || e.failed) return e.fn;
   e.launches += 1;
   e.items += (uint64_t)(items > 0 ? items : 0);
   // not hot yet?  (A compilation costs 0.3-0.9 s and buys ~5 us per launch: it pays for itself after ~10^5 launches -- any
@@ -385,7 +309,7 @@ hipFunction_t mnk_jit_api_function(const MnkGeom& g, int kind, int64_t items, hi
     hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(stream, &st) != hipSuccess || st != hipStreamCaptureStatusNone) return nullptr;
   }
-  return api_build(e, g, kind);
+  return build(e, kApiProgram, name);
 }
 
 extern "C" {
@@ -397,10 +321,7 @@ int64_t mnk_jit_compile_api(int m, int n, int k, int kind) {
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
   if (!api_kind_ok(g, kind)) return MNK_EINVAL;
-  std::vector<char> code;
-  std::string lowered;
-  if (!compile_api(g, kind, code, lowered)) return MNK_ELAUNCH;
-  return (int64_t)code.size();
+  return compiled_size(kApiProgram, api_kernel_name(g, kind));
 }
 
 // Compiles and loads, on the current device, the board's own variants of the API kernels named by the bits of
@@ -420,16 +341,17 @@ int mnk_jit_prepare(int m, int n, int k, int64_t kinds) {
   int ready = 0;
   for (int kind = 0; kind < MNK_JK_COUNT; ++kind) {
     if (!api_kind_ok(g, kind)) continue;
-    const auto key = std::make_tuple(device, g.m, g.n, mnk_jit_kind_any_k(kind) ? 0 : g.k, kind);
+    const std::string name = api_kernel_name(g, kind);
+    const auto key = std::make_tuple(device, g.m, name);
     if (kinds == 0) {
-      auto it = g_api_cache.find(key);
-      if (it == g_api_cache.end() || (it->second.launches == 0 && !it->second.c.fn)) continue;
+      auto it = g_cache.find(key);
+      if (it == g_cache.end() || (it->second.launches == 0 && !it->second.fn)) continue;
     } else if (!((kinds >> kind) & 1)) {
       continue;
     }
-    ApiEntry& e = g_api_cache[key];
-    if (!e.c.fn && !e.c.failed) api_build(e, g, kind);
-    if (!e.c.fn) return MNK_ELAUNCH;
+    Compiled& e = g_cache[key];
+    if (!e.fn && !e.failed) build(e, kApiProgram, name);
+    if (!e.fn) return MNK_ELAUNCH;
     ++ready;
   }
   return ready;
@@ -442,8 +364,8 @@ int mnk_jit_api_ready(int m, int n, int k, int kind) {
   int device = 0;
   if (hipGetDevice(&device) != hipSuccess) return 0;
   std::lock_guard<std::mutex> lock(g_mu);
-  auto it = g_api_cache.find(std::make_tuple(device, g.m, g.n, mnk_jit_kind_any_k(kind) ? 0 : g.k, kind));
-  return it != g_api_cache.end() && it->second.c.fn ? 1 : 0;
+  auto it = g_cache.find(std::make_tuple(device, g.m, api_kernel_name(g, kind)));
+  return it != g_cache.end() && it->second.fn ? 1 : 0;
 }
 
 // what the run-time compiler has done in this process: out[0] programs compiled by hiprtc, out[1] code objects taken from
@@ -459,13 +381,7 @@ const char* mnk_jit_last_error(void) { return g_jit_err; }
 // Compiles (does not load) the rollout kernel of a geometry: code object size in bytes, or a negative MNK_E* code.
 // Needs no GPU -- the build check and the CPU test suite use it.
 int64_t mnk_jit_compile_rollout(int m, int n, int k, int record, int act_bytes) {
-  MnkGeom g;
-  const int rc = mnk_check_geom(m, n, k, &g);
-  if (rc != MNK_OK) return rc;
-  if (!mnk_act_format_ok(act_bytes, g.C)) return MNK_EINVAL;
-  std::vector<char> code;
-  if (!compile(g, record != 0, act_bytes, record != 0, code)) return MNK_ELAUNCH;  // the form a 65 536-env launch uses
-  return (int64_t)code.size();
+  return mnk_jit_compile_kernel(m, n, k, record, act_bytes, MNK_JIT_ROLLOUT);
 }
 
 // the same for any of the run-time specialised kernels: kind MNK_JIT_ROLLOUT (one lane per env), MNK_JIT_REPLAY
@@ -477,9 +393,8 @@ int64_t mnk_jit_compile_kernel(int m, int n, int k, int record, int act_bytes, i
   if (kind < MNK_JIT_ROLLOUT || kind > MNK_JIT_ROLLOUT_PAIR || !mnk_act_format_ok(act_bytes, g.C)) return MNK_EINVAL;
   if (kind == MNK_JIT_REPLAY && act_bytes == 0) return MNK_EINVAL;
   if (kind == MNK_JIT_ROLLOUT_PAIR && (act_bytes == MNK_ACT_BITS7 || act_bytes == MNK_ACT_U8P1)) return MNK_EINVAL;
-  std::vector<char> code;
-  if (!compile(g, record != 0, act_bytes, kind == MNK_JIT_ROLLOUT && record != 0, code, kind)) return MNK_ELAUNCH;
-  return (int64_t)code.size();
+  // (saddr on a one-lane rollout with records: the form a 65 536-env launch uses)
+  return compiled_size(kRolloutProgram, rollout_kernel_name(g, kind, record != 0, act_bytes, kind == MNK_JIT_ROLLOUT && record != 0));
 }
 
 }  // extern "C"

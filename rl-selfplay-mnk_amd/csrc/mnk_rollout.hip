@@ -4,24 +4,6 @@
 #include "mnk_host.h"
 #include "mnk_rollout_lane.h"
 
-// ------------------------------------------------------------------ replay of an action log
-// The receiving side of the multi-GPU exchange: a shard's rollout is fully determined by its
-// chunk-start state and its action log (1-2 bytes per ply), so that is what crosses xGMI; this
-// kernel re-plays the log and rebuilds the full packed records, bit-identical to the sender's.
-// ACTB = bytes per logged action (1 or 2), a template parameter like everything else that shapes the ply loop: four
-// plies per log word, unrolled with compile-time field positions (round 1 looped ply by ply with a run-time field
-// and a branch per ply: 1.2e11 env-steps/s, slower than producing the log); the next word is fetched while the
-// current four plies are played.
-// ACTB = 3 (MNK_ACT_BITS7): the log is a stream of 7-bit actions; the reader mirrors the writer of mnk_rollout_lane.h --
-// a 64-bit accumulator whose fill level is wave-uniform, one u32 word fetched (ahead) whenever fewer than 28 bits remain.
-// (the body lives in mnk_rollout_lane.h: boards of more than 16 register words get it compiled at run time, mnk_jit.hip)
-template <int NW, int CN, int CK, bool RECORD, int ACTB>
-__global__ void __launch_bounds__(64)
-k_replay_actions(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, const void* act_log,
-                 uint64_t* rec_planes, uint32_t* rec_meta, int32_t* err) {
-  replay_actions_body<NW, CN, CK, RECORD, ACTB>(g, planes, meta, N, T, act_log, rec_planes, rec_meta, err);
-}
-
 // ================================================================== C ABI
 extern "C" {
 
@@ -66,13 +48,20 @@ int mnk_rollout_random(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n
       // two lanes per env for small batches, like the compile-time boards (same threshold, same results): round 4
       const bool pair_ok = w_fits && act_bytes != MNK_ACT_BITS7 && act_bytes != MNK_ACT_U8P1 && cfg.form != MNK_FORM_LANE &&
                            (pair_override >= 0 ? pair_override != 0 : N <= 32768);
+      // (mnk_module_launch takes the parameter list from the kernel template; decltype instantiates no kernel here)
       if (pair_ok)
-        if (hipFunction_t fn = mnk_jit_rollout_pair_function(g, rec, act_bytes))
-          return mnk_jit_launch_rollout_lanes(fn, g, planes, meta, N, T, seed, step0, env_id0, rec ? rec_planes : nullptr,
-                                              rec ? rec_meta : nullptr, stats, act_log, stream, 2);
-      if (hipFunction_t fn = mnk_jit_rollout_function(g, rec, act_bytes, rec && mnk_rollout_saddr_ok(g, N, T)))
-        return mnk_jit_launch_rollout(fn, g, planes, meta, N, T, seed, step0, env_id0, rec ? rec_planes : nullptr,
-                                      rec ? rec_meta : nullptr, stats, act_log, stream);
+        if (hipFunction_t fn = mnk_jit_rollout_function(g, MNK_JIT_ROLLOUT_PAIR, rec, act_bytes, false)) {
+          mnk_module_launch(decltype(&k_rollout_random_pair<2, 0, 0, true, 0>)(nullptr), fn, dim3((unsigned)((N + 31) / 32)),
+                            dim3(64), 0, (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0,
+                            rec ? rec_planes : nullptr, rec ? rec_meta : nullptr, (unsigned long long*)stats, act_log);
+          return mnk_launch_status("rollout_random (run-time specialised)");
+        }
+      if (hipFunction_t fn = mnk_jit_rollout_function(g, MNK_JIT_ROLLOUT, rec, act_bytes, rec && mnk_rollout_saddr_ok(g, N, T))) {
+        mnk_module_launch(decltype(&k_rollout_random<2, 0, 0, true, 0>)(nullptr), fn, grid, dim3(B), 0, (hipStream_t)stream, g,
+                          planes, meta, N, T, seed, step0, env_id0, rec ? rec_planes : nullptr, rec ? rec_meta : nullptr,
+                          (unsigned long long*)stats, act_log);
+        return mnk_launch_status("rollout_random (run-time specialised)");
+      }
       if (must) {
         snprintf(g_launch_err, sizeof(g_launch_err), "rollout_random: no kernel for this board: %.200s", mnk_jit_last_error());
         return MNK_ELAUNCH;
@@ -142,9 +131,11 @@ int mnk_replay_actions(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n
   const dim3 grid((unsigned)((N + B - 1) / B));
   if (g.NW > 16) {  // planes of more than 512 bits: the run-time specialised kernel is the only one (mnk_host.h)
     const bool with_rec = rec_planes && rec_meta;
-    if (hipFunction_t fn = mnk_jit_replay_function(g, with_rec, act_bytes))
-      return mnk_jit_launch_replay(fn, g, planes, meta, N, T, act_log, with_rec ? rec_planes : nullptr,
-                                   with_rec ? rec_meta : nullptr, err, stream);
+    if (hipFunction_t fn = mnk_jit_rollout_function(g, MNK_JIT_REPLAY, with_rec, act_bytes, false)) {
+      mnk_module_launch(decltype(&k_replay_actions<2, 0, 0, true, 1>)(nullptr), fn, grid, dim3(B), 0, (hipStream_t)stream, g,
+                        planes, meta, N, T, act_log, with_rec ? rec_planes : nullptr, with_rec ? rec_meta : nullptr, err);
+      return mnk_launch_status("replay_actions (run-time specialised)");
+    }
     snprintf(g_launch_err, sizeof(g_launch_err), "replay_actions: no kernel for this board: %.200s", mnk_jit_last_error());
     return MNK_ELAUNCH;
   }

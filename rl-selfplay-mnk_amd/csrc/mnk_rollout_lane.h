@@ -512,7 +512,9 @@ __device__ __forceinline__ void rollout_random_pair_body(const MnkGeom& g, uint6
 // The receiving side of the multi-GPU exchange: a shard's rollout is fully determined by its chunk-start state and its
 // action log, so that is what crosses xGMI; this re-plays the log and rebuilds the full packed records, bit-identical to
 // the sender's.  ACTB = the log format (MNK_ACT_U8 / _U16 / _BITS7 / _U8P1), a template parameter like everything else
-// that shapes the ply loop.
+// that shapes the ply loop: four plies per log word, unrolled with compile-time field positions (round 1 looped ply by ply
+// with a run-time field and a branch per ply: 1.2e11 env-steps/s, slower than producing the log); the next word is
+// fetched while the current four plies are played.
 template <int NW, int CN, int CK, bool RECORD, int ACTB>
 __device__ __forceinline__ void replay_actions_body(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T,
                                                     const void* act_log, uint64_t* rec_planes, uint32_t* rec_meta,
@@ -626,33 +628,7 @@ __device__ __forceinline__ void replay_actions_body(const MnkGeom& g, uint64_t* 
 }
 
 
-#ifdef MNK_JIT_NW
-// run-time specialisation (mnk_jit.hip): this board's geometry arrives as macros on the hiprtc command line
-#if !defined(MNK_JIT_KIND) || MNK_JIT_KIND == 0
-extern "C" __global__ void __launch_bounds__(64)
-mnk_jit_rollout(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed, uint64_t step0,
-                int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, unsigned long long* stats, void* act_log) {
-  rollout_random_body<MNK_JIT_NW, MNK_JIT_CN, MNK_JIT_CK, MNK_JIT_REC != 0, MNK_JIT_ACT, MNK_JIT_SADDR != 0>(
-      g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta, stats, act_log);
-}
-#elif MNK_JIT_KIND == 2
-// the two-lanes-per-env form (scan directions split): 32 envs per wave, for batches of up to 32 768 envs
-extern "C" __global__ void __launch_bounds__(64)
-mnk_jit_rollout_pair(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed, uint64_t step0,
-                     int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, unsigned long long* stats, void* act_log) {
-  rollout_random_pair_body<MNK_JIT_NW, MNK_JIT_CN, MNK_JIT_CK, MNK_JIT_REC != 0, MNK_JIT_ACT>(
-      g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta, stats, act_log);
-}
-#else
-// MNK_JIT_KIND == 1: the replay of an action log in format MNK_JIT_ACT
-extern "C" __global__ void __launch_bounds__(64)
-mnk_jit_replay(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, const void* act_log, uint64_t* rec_planes,
-               uint32_t* rec_meta, int32_t* err) {
-  replay_actions_body<MNK_JIT_NW, MNK_JIT_CN, MNK_JIT_CK, MNK_JIT_REC != 0, MNK_JIT_ACT>(g, planes, meta, N, T, act_log,
-                                                                                         rec_planes, rec_meta, err);
-}
-#endif
-#else
+// ------------------------------------------------------------------ the kernels (mnk_jit.hip names them by name expression)
 template <int NW, int CN, int CK, bool RECORD, int ACT, bool SADDR = false>
 __global__ void __launch_bounds__(64)
 k_rollout_random(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed, uint64_t step0,
@@ -661,4 +637,20 @@ k_rollout_random(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, 
   rollout_random_body<NW, CN, CK, RECORD, ACT, SADDR>(g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta,
                                                       stats, act_log);
 }
-#endif
+
+// the two-lanes-per-env form (scan directions split): 32 envs per wave, for batches of up to 32 768 envs
+template <int NW, int CN, int CK, bool RECORD, int ACT>
+__global__ void __launch_bounds__(64)
+k_rollout_random_pair(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed, uint64_t step0,
+                      int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, unsigned long long* stats,
+                      void* act_log) {
+  rollout_random_pair_body<NW, CN, CK, RECORD, ACT>(g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta, stats,
+                                                    act_log);
+}
+
+template <int NW, int CN, int CK, bool RECORD, int ACTB>
+__global__ void __launch_bounds__(64)
+k_replay_actions(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, const void* act_log,
+                 uint64_t* rec_planes, uint32_t* rec_meta, int32_t* err) {
+  replay_actions_body<NW, CN, CK, RECORD, ACTB>(g, planes, meta, N, T, act_log, rec_planes, rec_meta, err);
+}

@@ -14,16 +14,8 @@
 // instructions per env, so it wins exactly while both lanes of every env fit one wave per SIMD (2N <= 65 536
 // lanes) and the launcher uses it only up to 32 768 envs.
 
-// (pair_plies and the kernel's body live in mnk_rollout_lane.h: boards without an ahead-of-time variant get this form
-// compiled at run time too, mnk_jit.hip)
-template <int NW, int CN, int CK, bool RECORD, int ACT>
-__global__ void __launch_bounds__(64)
-k_rollout_random_pair(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed, uint64_t step0,
-                      int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, unsigned long long* stats,
-                      void* act_log) {
-  rollout_random_pair_body<NW, CN, CK, RECORD, ACT>(g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta, stats,
-                                                    act_log);
-}
+// (the kernel and its body live in mnk_rollout_lane.h: boards without an ahead-of-time variant get this form compiled
+// at run time too, mnk_jit.hip)
 
 void mnk_launch_rollout_pair(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
                              uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
