@@ -383,6 +383,55 @@ int mnk_sample_search(const void* obs, int obs_dtype, int64_t N, int m, int n, i
 #define MNK_SEARCH_ITERS_MAX 2048
 #define MNK_SEARCH_PLAYOUTS_MAX 256
 
+/* ---- the PUCT search player: AlphaZero-style search guided by the caller's evaluator (normally a policy/value net),
+ * batched over rows, one env-side launch per evaluation.  Row i of obs is a canonical view [N][2][m][n] (f32 / bf16 / u8,
+ * channel 0 = the side to move, a cell is a stone when its element is non-zero); C = m*n; I = iterations in [1, 2048].
+ * Nodes: a node is a position with a visit count n (u32) and a value sum w (f32) from the view of the player who moved
+ * into it.  A node is terminal when its move leaves a run of >= k of its mover anywhere on that mover's plane (the env's
+ * whole-plane test, as in mnk_sample_search) or fills the board.  An evaluated node keeps the prior P[a] of each of its
+ * legal cells a exactly as the evaluator returned it (not renormalised; the priors of occupied cells are never read).
+ * Evaluation 0: the leaf is the root (the row itself, its legal cells as the mask).  Iterations it = 1 .. I, each a
+ * backup of the previous leaf, then a selection:
+ *   backup: v = the leaf's value from the view of its side to move -- the evaluator's value for that row when the leaf
+ *     is not terminal, -1 when the move into it won, 0 when it filled the board.  Every node on the path root .. leaf
+ *     (leaf at depth d) gets n += 1 and, at depth j, w += v when d - j is odd, w += -v when it is even: one add per node
+ *     and iteration, in iteration order, each a correctly rounded f32 add.
+ *   selection: from the root, at an evaluated node v take the legal cell a of maximal
+ *       s = fadd(q, fdiv(fmul(fmul(c, P[a]), fsqrt((float)n_v)), (float)(1 + n_a))),  q = n_a ? fdiv(w_a, n_a) : 0,
+ *     every operation correctly rounded, no contraction, ties to the lowest cell; n_a, w_a are the child's through a
+ *     (0 when it does not exist).  A child that does not exist yet is created and is the leaf; an existing terminal
+ *     child is the leaf; otherwise descend into it.
+ *   leaf output: the leaf's canonical observation (channel 0 = its side to move) into leaf_obs [N][2][m][n] of
+ *     leaf_dtype, its legal cells into leaf_mask u8 [N][C], for every row, terminal leaves included (the evaluator's
+ *     outputs for a terminal leaf are not read).
+ * A row creates at most one node per iteration (at most I + 1 nodes).  A row whose root has no legal cell runs no
+ * iterations (its leaf stays the root) and draws its move over all C cells, as the other players do.  The move, after
+ * the last backup: S = the root children of maximal n; temperature 0: the r-th cell of S in action order, r = mulhi32(x,
+ * |S|); temperature 1: the cell at which the root children's visits, accumulated in action order, first exceed r =
+ * mulhi32(x, sum n_a); deterministic: the first cell of S.  x = Philox(seed, env_id0 + i, step [+ *step_dev],
+ * MNK_STREAM_SAMPLE) -- TacticalPolicy's u32; seed_dev (optional) REPLACES seed, step_dev (optional) is ADDED to step.
+ * Outputs (optional, NULL = off): visits int32 [N][C] = the root children's n (0 elsewhere; they sum to I on a row with a
+ * legal cell); root_value f32 [N] = -w_root / n_root, the root's mean value for its side to move.  priors: f32 or bf16
+ * [N][C], values f32 or bf16 [N] (MNK_LOGITS_*; a bf16 element is read as its exact f32).  Non-finite priors or values
+ * give an unspecified result (not checked: a check would cost a synchronisation).  c: finite, >= 0.
+ * The tree lives in `workspace` (mnk_puct_workspace_bytes(N, m, n, I) bytes, about (I + 1) * 6 * C per row; its layout is
+ * private to the library) from mnk_puct_begin to the step with `last` set.  One act() = mnk_puct_begin, then I steps
+ * with last = 0 and one with last = 1 (I + 2 launches, I + 1 evaluations), all stream-ordered, no host synchronisation.
+ * Every host check runs before anything is enqueued. */
+int64_t mnk_puct_workspace_bytes(int64_t N, int m, int n, int iterations);  /* < 0: MNK_EINVAL / MNK_EGEOM */
+/* the roots into the tree; writes them as evaluation 0 (leaf_obs, leaf_mask) */
+int mnk_puct_begin(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, void* workspace,
+                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, void* stream);
+/* one backup of the evaluation (priors, values) of the pending leaves, then one selection that writes the next leaves;
+ * with last = 1 the backup, then the move (actions int64[N]), visits and root_value, and no new leaf (leaf_obs /
+ * leaf_mask may then be NULL) */
+int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iterations, const void* priors, int priors_dtype,
+                  const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
+                  const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
+                  void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
+                  float* root_value, void* stream);
+#define MNK_PUCT_ITERS_MAX 2048
+
 /* ---- the random-policy rollout of BASELINE.json (RandomPolicy.act -> env.step -> env.reset(done)),
  * T plies per env in one launch with the state held in registers.
  * rec_planes u64[T][R][N]: the position BEFORE each ply (record rows, see the top of this file);

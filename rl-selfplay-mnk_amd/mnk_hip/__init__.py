@@ -26,6 +26,7 @@ STREAM_MOVE, STREAM_OPP, STREAM_SIDE, STREAM_SAMPLE, STREAM_PLAYOUT, STREAM_SEAR
 PLAYOUTS_MAX = 4096  # MNK_PLAYOUTS_MAX: the largest playout count of mnk_sample_playouts
 SEARCH_ITERS_MAX = 2048  # MNK_SEARCH_ITERS_MAX: the largest iteration budget of mnk_sample_search
 SEARCH_PLAYOUTS_MAX = 256  # MNK_SEARCH_PLAYOUTS_MAX: the largest playout count per leaf of mnk_sample_search
+PUCT_ITERS_MAX = 2048  # MNK_PUCT_ITERS_MAX: the largest iteration budget of mnk_puct_begin / mnk_puct_step
 STATS_REPLICAS, STATS_STRIDE, STATS_COUNTERS = 64, 8, 5
 # run-time specialised API kernels (MNK_JIT_API_* of include/mnk_hip.h): bit numbers for jit_prepare()
 (JIT_API_STEP, JIT_API_STEP_DRAW, JIT_API_STEP_SUBSET, JIT_API_OBSERVE, JIT_API_SAMPLE_LEGAL, JIT_API_UNPACK_RECORDS,
@@ -84,6 +85,14 @@ SIGNATURES = {
     "mnk_sample_playouts": [_vp, _i, _i64, _i, _i, _i, _i, _u64, _vp, _u64, _vp, _i64, _i, _vp, _vp, _vp],
     # obs, obs dtype, N, m, n, k, iterations, playouts, c, then the sampler block, actions, stats (int32 [N][3][C]), stream
     "mnk_sample_search": [_vp, _i, _i64, _i, _i, _i, _i, _i, _f, _u64, _vp, _u64, _vp, _i64, _i, _vp, _vp, _vp],
+    # N, m, n, iterations -> bytes of the PUCT tree workspace (int64; < 0: an error code)
+    "mnk_puct_workspace_bytes": [_i64, _i, _i, _i],
+    # obs, obs dtype, N, m, n, k, iterations, workspace, leaf obs, leaf dtype, leaf mask, stream
+    "mnk_puct_begin": [_vp, _i, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
+    # workspace, N, m, n, k, iterations, priors, priors dtype, values, values dtype, c, last, temperature, then the
+    # sampler block, leaf obs, leaf dtype, leaf mask, actions, visits (int32 [N][C]), root value (f32 [N]), stream
+    "mnk_puct_step": [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i, _vp, _i,
+                      _vp, _vp, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],
     "mnk_action_log_words": [_i, _i],
     "mnk_replay_actions": [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp],
@@ -139,7 +148,8 @@ def load():
         fn.argtypes = argtypes
         if name in ("mnk_last_launch_error", "mnk_comm_last_error", "mnk_jit_last_error"):
             fn.restype = ctypes.c_char_p
-        elif name in ("mnk_jit_compile_rollout", "mnk_jit_compile_kernel", "mnk_jit_compile_api"):
+        elif name in ("mnk_jit_compile_rollout", "mnk_jit_compile_kernel", "mnk_jit_compile_api",
+                      "mnk_puct_workspace_bytes"):
             fn.restype = ctypes.c_int64
         else:
             fn.restype = ctypes.c_int
@@ -257,6 +267,14 @@ def jit_api_ready(m: int, n: int, k: int, kind: int) -> bool:
 
 def state_words(m, n):
     return load().mnk_state_words(m, n)
+
+
+def puct_workspace_bytes(N: int, m: int, n: int, iterations: int) -> int:
+    """bytes of the PUCT tree workspace of N rows (mnk_puct_workspace_bytes); MnkHipError on a bad board or budget"""
+    size = load().mnk_puct_workspace_bytes(N, m, n, iterations)
+    if size < 0:
+        raise MnkHipError(f"mnk_puct_workspace_bytes: {_STATUS.get(size, f'status {size}')}")
+    return size
 
 
 def record_words(m: int, n: int) -> int:

@@ -12,6 +12,9 @@
 ``MonteCarloPolicy`` the flat Monte Carlo player: for every legal cell P uniformly random playouts to the end of the game,
                    then a cell of best wins-minus-losses (``mnk_sample_playouts``); strength set by P, no training.  As a
                    wrapper opponent it goes through pre -> act -> post like any policy.
+``PUCTSearchPolicy`` AlphaZero-style search on a policy/value evaluator (a trained net): one launch per evaluation
+                   backs up the last one and selects the next leaves (``mnk_puct_step``); root visit counts as policy
+                   targets; capturable in a graph.  As a wrapper opponent it goes through pre -> act -> post.
 ``SearchPolicy``   the tree-search player (UCT): I iterations of selection, expansion, B random playouts from the leaf
                    and backup, then a root child of most visits (``mnk_sample_search``); strength set by I, no training;
                    hands out the root visit counts per cell.  As a wrapper opponent it goes through pre -> act -> post.
@@ -252,6 +255,114 @@ class SearchPolicy(Policy):
         cells the search never expanded"""
         return _play(self._sampler, "mnk_sample_search", obs, (self.k, self.iterations, self.playouts, self.c),
                      deterministic, "stats", stats, 3, (torch.int32,))
+
+
+def model_evaluator(model: nn.Module):
+    """the evaluator of a reference-style ``model(obs, mask) -> (dist, value)``: ``dist.probs`` and ``value.reshape(-1)``,
+    under ``torch.no_grad()``.  (Under graph capture the model must build its distribution without argument validation,
+    ``torch.distributions.Distribution.set_default_validate_args(False)``: the check is a host synchronisation.)"""
+
+    def evaluate(leaf_obs, leaf_mask):
+        with torch.no_grad():
+            dist, value = model(leaf_obs, leaf_mask)
+        return dist.probs, value.reshape(-1)
+
+    return evaluate
+
+
+class PUCTSearchPolicy(Policy):
+    """The PUCT search player (the rule: include/mnk_hip.h, mnk_puct_step): AlphaZero-style search on top of a
+    policy/value evaluator, ``iterations`` evaluations per move after the roots', batched over the rows.  Each iteration is
+    one launch that backs up the previous evaluation and selects every row's next leaf (child of maximal
+    ``q + c * P * sqrt(n_parent) / (1 + n_child)``), then one call of the evaluator on the whole batch of leaves.  The move
+    is drawn among the root children of most visits (``temperature=0``; ``deterministic``: the first of them), or in
+    proportion to the root visits (``temperature=1``), from one Philox u32 per row (the u32 ``TacticalPolicy`` draws).
+
+    ``evaluator(leaf_obs, leaf_mask) -> (priors [N, m*n], values [N])``: ``leaf_obs`` is a canonical view ``[N, 2, m, n]``
+    of ``leaf_dtype`` (channel 0 = the leaf's side to move), ``leaf_mask`` a bool ``[N, m*n]`` of its legal cells; priors
+    and values in float32 or bfloat16, the value from the view of the leaf's side to move.  Priors are used as returned
+    (not renormalised).  With ``model`` instead, ``model_evaluator(model)``.  The first evaluator call of every ``act`` is
+    always on the roots (the rows of ``obs`` themselves): an evaluator that mixes noise into the priors of that call
+    (Dirichlet root noise, say) only has to count its calls modulo ``iterations + 1``.  The rows of terminal leaves are
+    evaluated too (a fixed batch shape) and their outputs ignored.
+
+    The tree and the leaf buffers are allocated on the first ``act`` and reused while (N, m, n, iterations) stay; after
+    that an ``act`` allocates nothing of its own but its result and never synchronises with the host, so
+    ``torch.cuda.graph`` can capture it (with a capturable evaluator).  As the opponent of ``TorchSelfPlayWrapper`` it is
+    called through pre -> act -> post like any policy."""
+
+    def __init__(self, k: int, model=None, evaluator=None, iterations: int = 256, c: float = 1.25, temperature: int = 0,
+                 leaf_dtype=torch.float32, seed=None):
+        if (model is None) == (evaluator is None):
+            raise ValueError("PUCTSearchPolicy needs exactly one of model and evaluator")
+        self.k = int(k)
+        self.model = model
+        if model is not None:
+            model.eval()
+        self.evaluator = evaluator if evaluator is not None else model_evaluator(model)
+        self.iterations = int(iterations)
+        self.c = float(c)
+        self.temperature = temperature
+        if not 1 <= self.iterations <= mnk_hip.PUCT_ITERS_MAX:
+            raise ValueError(f"iterations must lie in [1, {mnk_hip.PUCT_ITERS_MAX}], got {iterations}")
+        if not (math.isfinite(self.c) and 0.0 <= self.c <= 3.0e38):
+            raise ValueError(f"c must be finite and >= 0, got {c}")
+        if temperature not in (0, 1):
+            raise ValueError(f"temperature must be 0 or 1, got {temperature}")
+        self.leaf_dtype = leaf_dtype
+        self._leaf_code = mnk_hip.obs_dtype_code(leaf_dtype)  # (TypeError for anything but float32 / bfloat16 / uint8)
+        self._sampler = _HipSampler(seed)
+        self._bufs = None  # (key, workspace, leaf_obs, leaf_mask)
+
+    def _buffers(self, b, m, n, device):
+        key = (b, m, n, self.iterations, device)
+        if self._bufs is None or self._bufs[0] != key:
+            size = mnk_hip.puct_workspace_bytes(b, m, n, self.iterations)
+            self._bufs = (key, torch.empty(size, dtype=torch.uint8, device=device),
+                          torch.empty((b, 2, m, n), dtype=self.leaf_dtype, device=device),
+                          torch.empty((b, m * n), dtype=torch.bool, device=device))
+        return self._bufs[1:]
+
+    def _evaluate(self, leaf_obs, leaf_mask, b, c):
+        priors, values = self.evaluator(leaf_obs, leaf_mask)
+        if priors.dtype not in (torch.float32, torch.bfloat16):
+            priors = priors.to(torch.float32)
+        if values.dtype not in (torch.float32, torch.bfloat16):
+            values = values.to(torch.float32)
+        priors, values = priors.reshape(b, c).contiguous(), values.reshape(b).contiguous()
+        if priors.device != leaf_obs.device or values.device != leaf_obs.device:
+            raise ValueError("the evaluator must return priors and values on the leaves' device")
+        code = {torch.float32: mnk_hip.LOGITS_F32, torch.bfloat16: mnk_hip.LOGITS_BF16}
+        return priors, code[priors.dtype], values, code[values.dtype]
+
+    def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, visits=None, root_value=None) -> torch.Tensor:
+        """``visits``: optional int32 ``[B, m*n]`` tensor that receives each row's root visit counts (an AlphaZero policy
+        target; they sum to ``iterations`` on a row with a legal cell); ``root_value``: optional float32 ``[B]`` tensor
+        that receives the root's mean value for the side to move"""
+        observation = _canonical_observation(obs)
+        b, _, m, n = observation.shape
+        dev = observation.device
+        for name, t, shape, dtype in (("visits", visits, (b, m * n), torch.int32),
+                                      ("root_value", root_value, (b,), torch.float32)):
+            if t is not None and (t.shape != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
+                raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {shape} tensor on {dev}")
+        actions = torch.empty(b, dtype=torch.long, device=dev)
+        if b:
+            ws, leaf_obs, leaf_mask = self._buffers(b, m, n, dev)
+            stream = mnk_hip.stream_ptr(dev)
+            I, k, code = self.iterations, self.k, self._leaf_code
+            mnk_hip.call("mnk_puct_begin", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k, I,
+                         mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask), stream)
+            for it in range(I + 1):
+                priors, pcode, values, vcode = self._evaluate(leaf_obs, leaf_mask, b, m * n)
+                last = it == I
+                mnk_hip.call("mnk_puct_step", mnk_hip.ptr(ws), b, m, n, k, I, mnk_hip.ptr(priors), pcode,
+                             mnk_hip.ptr(values), vcode, self.c, 1 if last else 0, self.temperature,
+                             *self._sampler.block(deterministic), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask),
+                             mnk_hip.ptr(actions) if last else None, mnk_hip.ptr(visits) if last else None,
+                             mnk_hip.ptr(root_value) if last else None, stream)
+        self._sampler.advance()
+        return actions
 
 
 class NNPolicy(Policy):
