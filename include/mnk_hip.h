@@ -566,6 +566,12 @@ int mnk_comm_version(void);
  * for the access pattern mnk_rollout_random is bound by. */
 int mnk_probe_record_writes(uint64_t* rec, int64_t N, int T, int rows, void* stream);
 
+/* Test aid: the r-th-set-bit select of the rollout kernels (bs_select_hot in csrc/mnk_device.h) on `count` strings of
+ * nw = 1, 3 or 12 u32 words (words u32[count][nw], ranks i32[count], each rank < the string's popcount): the bit index
+ * to bits i32[count] and the one-hot string to hot u32[count][nw]. */
+int mnk_probe_select_bits(const uint32_t* words, int nw, int64_t count, const int32_t* ranks, int32_t* bits, uint32_t* hot,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif

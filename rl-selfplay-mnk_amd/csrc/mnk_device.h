@@ -76,7 +76,10 @@ __device__ __forceinline__ int geom_k(const MnkGeom& g) { return CK ? CK : g.k; 
 // guard-column bit index (row * (n + 1) + col) -> cell (row * n + col), and back
 template <int CN>
 __device__ __forceinline__ int mnk_bit_cell(const MnkGeom& g, uint32_t bit) {
-  return (int)(bit - (CN ? bit / (uint32_t)(CN + 1) : mnk_div(bit, g.magic_stride)));
+  // CN known: x / (n + 1) as one v_mul_hi_u32 by ceil(2^32 / (n + 1)), exact for x * (magic * (n + 1) - 2^32) < 2^32 --
+  // every board bit (x < 1 024, the error term < n + 1) -- where the compiler's general form adds a shift
+  constexpr uint32_t magic = CN ? (uint32_t)((0x100000000ull + CN) / (uint32_t)(CN + 1)) : 0u;
+  return (int)(bit - (CN ? __umulhi(bit, magic) : mnk_div(bit, g.magic_stride)));
 }
 template <int CN>
 __device__ __forceinline__ uint32_t mnk_cell_bit(const MnkGeom& g, uint32_t cell) {
@@ -219,28 +222,33 @@ __device__ __forceinline__ void mnk_plane_completions(const MnkGeom& g, const ui
 //   nr   = umax(nr, t)                         t < 0  <=>  the bit lies above the field: rank -= count
 //   pos |= S & (t >> 31)                       ... and the position moves up
 // The last level looks at one bit: the answer is pos + 1 unless r == 0 and that bit is set.
+// select_bit32_nr takes the rank already negated (nr = ~r) and a start `base` whose low five bits are zero: the
+// field offsets of v_bfe and the shift that makes the one-hot read only the low five bits of pos, so the word's
+// bit offset in a multi-word string rides along in pos for free.
 #define MNK_SELECT_LEVEL(S)                        \
   "v_bfe_u32 %[t], %[x], %[pos], " #S "\n\t"       \
   "v_bcnt_u32_b32 %[t], %[t], %[nr]\n\t"          \
   "v_max_u32 %[nr], %[nr], %[t]\n\t"              \
   "v_ashrrev_i32 %[t], 31, %[t]\n\t"              \
   "v_and_or_b32 %[pos], %[t], " #S ", %[pos]\n\t"
-__device__ __forceinline__ int select_bit32(uint32_t x, int r) {
-  uint32_t nr = ~(uint32_t)r, pos, t;
+__device__ __forceinline__ uint32_t select_bit32_nr(uint32_t x, uint32_t nr, uint32_t base) {
+  uint32_t pos, t;
   asm("v_and_b32 %[t], 0xffff, %[x]\n\t"
       "v_bcnt_u32_b32 %[t], %[t], %[nr]\n\t"
       "v_max_u32 %[nr], %[nr], %[t]\n\t"
       "v_ashrrev_i32 %[t], 31, %[t]\n\t"
-      "v_and_b32 %[pos], 16, %[t]\n\t"
+      "v_and_or_b32 %[pos], %[t], 16, %[base]\n\t"
       MNK_SELECT_LEVEL(8) MNK_SELECT_LEVEL(4) MNK_SELECT_LEVEL(2)
       "v_bfe_u32 %[t], %[x], %[pos], 1\n\t"
       "v_bitop3_b32 %[t], %[nr], %[t], %[t] bitop3:0x3f\n\t"  // ~(nr & bit): bit 0 clear only if r == 0 and the bit is set
       "v_and_or_b32 %[pos], %[t], 1, %[pos]"
       : [pos] "=&v"(pos), [t] "=&v"(t), [nr] "+v"(nr)
-      : [x] "v"(x));
-  return (int)pos;
+      : [x] "v"(x), [base] "v"(base));
+  return pos;
 }
 #undef MNK_SELECT_LEVEL
+
+__device__ __forceinline__ int select_bit32(uint32_t x, int r) { return (int)select_bit32_nr(x, ~(uint32_t)r, 0u); }
 
 template <int NW>
 __device__ __forceinline__ int bs_popcount(const uint32_t (&x)[NW]) {
@@ -251,35 +259,33 @@ __device__ __forceinline__ int bs_popcount(const uint32_t (&x)[NW]) {
 }
 
 // bit index of the r-th set bit of the multi-word string (r < popcount), and the string with only
-// that bit set in `hot`.  The word is the last one whose prefix count is <= r: prefix counts never
-// decrease, so the per-word tests are independent of each other.
+// that bit set in `hot`.  With nr = ~r = -(r + 1) and pre[w] = popcount of words 0 .. w-1, t[w] = pre[w] + nr is
+// negative exactly when the bit lies in word w or above; prefix counts never decrease, so these tests are independent
+// of each other and their sign masks m[w] = t[w] >> 31 are monotone (m[w + 1] implies m[w]).  The rank inside the
+// chosen word is the largest t[w] as an unsigned number (a negative t[w] is larger than nr, a non-negative one is
+// smaller), one v_max3 per two words; the word and its bit offset are bit-field inserts on the masks; and the one-hot
+// is one & m[w] & ~m[w + 1] -- one logic op per word, no compare, no select.  (v_bitop3 truth tables are indexed by
+// src0 * 4 + src1 * 2 + src2.  Spelled as plain C++ the masks went back to v_cmp + v_cndmask: 3 more slots per ply.)
 template <int NW>
 __device__ __forceinline__ int bs_select_hot(const uint32_t (&x)[NW], int r_, uint32_t (&hot)[NW]) {
-  const uint32_t r = (uint32_t)r_;
-  uint32_t word = x[0], base = 0, before = 0, pre = 0;
-  bool past[NW + 1];
-  past[0] = true;
-  past[NW] = false;
+  const uint32_t nr = ~(uint32_t)r_;
+  uint32_t m[NW + 1], word = x[0], base = 0u, rank = nr, pre = 0u;
+  m[0] = ~0u;
+  m[NW] = 0u;
 #pragma unroll
   for (int w = 1; w < NW; ++w) {
     pre += (uint32_t)__popc(x[w - 1]);
-    past[w] = r >= pre;
-    word = past[w] ? x[w] : word;
-    base = past[w] ? 32u * w : base;
-    before = past[w] ? pre : before;
+    const uint32_t t = pre + nr;
+    m[w] = (uint32_t)((int32_t)t >> 31);
+    rank = rank > t ? rank : t;
+    word = __builtin_amdgcn_bitop3_b32(m[w], x[w], word, 0xca);  // m ? x[w] : word
+    base = __builtin_amdgcn_bitop3_b32(m[w], 32u * w, base, 0xca);    // m ? 32 w : base
   }
-  const uint32_t pos = (uint32_t)select_bit32(word, (int)(r - before));
-  const uint32_t one = 1u << pos;
-  // past[] is monotone (past[w + 1] implies past[w]): with a[w] = past[w] ? one : 0 the chosen word is where a[] drops,
-  // hot[w] = a[w] ^ a[w + 1] -- one select and one xor per word boundary instead of two selects
-  uint32_t a[NW + 1];
-  a[0] = one;
-  a[NW] = 0u;
+  const uint32_t pos = select_bit32_nr(word, rank, base);
+  const uint32_t one = 1u << (pos & 31u);
 #pragma unroll
-  for (int w = 1; w < NW; ++w) a[w] = past[w] ? one : 0u;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) hot[w] = a[w] ^ a[w + 1];
-  return (int)(base + pos);
+  for (int w = 0; w < NW; ++w) hot[w] = __builtin_amdgcn_bitop3_b32(one, m[w], m[w + 1], 0x40);  // one & m[w] & ~m[w + 1]
+  return (int)pos;
 }
 
 template <int NW>

@@ -139,6 +139,20 @@ __global__ void __launch_bounds__(64) k_probe_record_writes(uint64_t* rec, int64
     }
 }
 
+// the r-th-set-bit select on its own (tests/test_gpu_select.py checks it against a plain loop): one string per lane
+template <int NW>
+__global__ void __launch_bounds__(64) k_probe_select_bits(const uint32_t* words, int64_t count, const int32_t* ranks,
+                                                          int32_t* bits, uint32_t* hot) {
+  const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
+  if (i >= count) return;
+  uint32_t x[NW], h[NW];
+#pragma unroll
+  for (int w = 0; w < NW; ++w) x[w] = words[i * NW + w];
+  bits[i] = bs_select_hot<NW>(x, ranks[i], h);
+#pragma unroll
+  for (int w = 0; w < NW; ++w) hot[i * NW + w] = h[w];
+}
+
 // ================================================================== C ABI
 extern "C" {
 
@@ -148,6 +162,20 @@ int mnk_probe_record_writes(uint64_t* rec, int64_t N, int T, int rows, void* str
   hipLaunchKernelGGL(k_probe_record_writes, dim3((unsigned)((N + 63) / 64)), dim3(64), 0, (hipStream_t)stream, rec, N, T,
                      rows, 0x9E3779B97F4A7C15ull);
   return mnk_launch_status("probe_record_writes");
+}
+
+int mnk_probe_select_bits(const uint32_t* words, int nw, int64_t count, const int32_t* ranks, int32_t* bits, uint32_t* hot,
+                          void* stream) {
+  if (!words || !ranks || !bits || !hot || count < 0 || (nw != 1 && nw != 3 && nw != 12)) return MNK_EINVAL;
+  if (count == 0) return MNK_OK;
+  const dim3 grid((unsigned)((count + 63) / 64));
+  if (nw == 1)
+    hipLaunchKernelGGL(k_probe_select_bits<1>, grid, dim3(64), 0, (hipStream_t)stream, words, count, ranks, bits, hot);
+  else if (nw == 3)
+    hipLaunchKernelGGL(k_probe_select_bits<3>, grid, dim3(64), 0, (hipStream_t)stream, words, count, ranks, bits, hot);
+  else
+    hipLaunchKernelGGL(k_probe_select_bits<12>, grid, dim3(64), 0, (hipStream_t)stream, words, count, ranks, bits, hot);
+  return mnk_launch_status("probe_select_bits");
 }
 
 int mnk_abi_version(void) { return MNK_ABI_VERSION; }

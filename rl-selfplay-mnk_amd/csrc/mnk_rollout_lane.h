@@ -74,10 +74,11 @@ struct RolloutLane {
   uint32_t hi4 = 0, hiw = 0, hfill = 0;  // ACT 4: bit 8 of the group's actions, the word being filled, its fill (uniform)
   uint32_t lo = 0;         // ACT 3: the stream's accumulator: the bits of the word being filled ...
   uint32_t fill = 0;       // ... and how many of them are valid (wave-uniform: 0, 28, 24, ..., 4 between quads)
-  // per-lane statistics, one add each per ply (T <= 65535 per launch): draws = done - wins, black wins =
-  // wins - white wins; the summed length of the finished games needs no counter at all -- every ply adds one
-  // to `moves` and a finished game takes its length out, so it is moves(start) + T - moves(end)
-  uint32_t acc_done = 0, acc_win = 0, acc_white = 0;
+  // per-lane statistics (T <= 65535 per launch): finished games in the low half of acc_dw and wins in the high half,
+  // so one add counts both; draws = done - wins, black wins = wins - white wins; the summed length of the finished
+  // games needs no counter at all -- every ply adds one to `moves` and a finished game takes its length out, so it
+  // is moves(start) + T - moves(end)
+  uint32_t acc_dw = 0, acc_white = 0;
   uint32_t moves_in = 0;
   uint32_t moves_parity = 0;  // WS > 1: plies played by this launch (selects the verdict buffer)
 
@@ -338,8 +339,7 @@ struct RolloutLane {
         rm += N;
       }
     }
-    acc_done += done;
-    acc_win += win;
+    acc_dw += done | (win << 16);
     acc_white += win & side;
     // the other side is to move (:82) -- or a fresh game
 #pragma unroll
@@ -351,6 +351,9 @@ struct RolloutLane {
     side = done ? 0u : (side ^ 1u);
     if (!FAST) moves = done ? 0u : moves;
   }
+
+  __device__ __forceinline__ uint32_t acc_done() const { return acc_dw & 0xFFFFu; }
+  __device__ __forceinline__ uint32_t acc_win() const { return acc_dw >> 16; }
 
   // is this lane's game consistent (stones on the board == plies counted < C)?  -> the wave may take the FAST loop
   __device__ __forceinline__ bool consistent() const {
@@ -427,10 +430,10 @@ __device__ __forceinline__ void rollout_random_body(const MnkGeom& g, uint64_t* 
     L.store(planes, meta, i);
     if (stats) {
       const uint32_t len_sum = L.moves_in + (uint32_t)T - L.moves;
-      if (L.acc_done) atomicAdd(&lds_stats[0], L.acc_done);
-      if (L.acc_win - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win - L.acc_white);
+      if (L.acc_done()) atomicAdd(&lds_stats[0], L.acc_done());
+      if (L.acc_win() - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win() - L.acc_white);
       if (L.acc_white) atomicAdd(&lds_stats[2], L.acc_white);
-      if (L.acc_done - L.acc_win) atomicAdd(&lds_stats[3], L.acc_done - L.acc_win);
+      if (L.acc_done() - L.acc_win()) atomicAdd(&lds_stats[3], L.acc_done() - L.acc_win());
       if (len_sum) atomicAdd(&lds_stats[4], len_sum);
     }
   }
@@ -495,10 +498,10 @@ __device__ __forceinline__ void rollout_random_pair_body(const MnkGeom& g, uint6
     L.store(planes, meta, i);  // lane `role` stores plane `role`; the meta word is written by both
     if (stats && role == 0) {
       const uint32_t len_sum = L.moves_in + (uint32_t)T - L.moves;
-      if (L.acc_done) atomicAdd(&lds_stats[0], L.acc_done);
-      if (L.acc_win - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win - L.acc_white);
+      if (L.acc_done()) atomicAdd(&lds_stats[0], L.acc_done());
+      if (L.acc_win() - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win() - L.acc_white);
       if (L.acc_white) atomicAdd(&lds_stats[2], L.acc_white);
-      if (L.acc_done - L.acc_win) atomicAdd(&lds_stats[3], L.acc_done - L.acc_win);
+      if (L.acc_done() - L.acc_win()) atomicAdd(&lds_stats[3], L.acc_done() - L.acc_win());
       if (len_sum) atomicAdd(&lds_stats[4], len_sum);
     }
   }

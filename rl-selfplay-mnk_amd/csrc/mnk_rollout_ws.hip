@@ -54,10 +54,10 @@ k_rollout_random_ws(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int 
       L.store(planes, meta, i);
       if (stats) {
         const uint32_t len_sum = L.moves_in + (uint32_t)T - L.moves;
-        if (L.acc_done) atomicAdd(&lds_stats[0], L.acc_done);
-        if (L.acc_win - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win - L.acc_white);
+        if (L.acc_done()) atomicAdd(&lds_stats[0], L.acc_done());
+        if (L.acc_win() - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win() - L.acc_white);
         if (L.acc_white) atomicAdd(&lds_stats[2], L.acc_white);
-        if (L.acc_done - L.acc_win) atomicAdd(&lds_stats[3], L.acc_done - L.acc_win);
+        if (L.acc_done() - L.acc_win()) atomicAdd(&lds_stats[3], L.acc_done() - L.acc_win());
         if (len_sum) atomicAdd(&lds_stats[4], len_sum);
       }
     }
