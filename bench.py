@@ -15,11 +15,14 @@ keyframe + the logs since.  --keyframe 1 makes every message self-contained, --k
 state once before the first chunk (receivers must then replay every chunk to keep it current);
 --gather records all-gathers the 28 B packed records themselves.
 
-    python bench.py                       # 1 GPU, defaults finish in well under a minute
+    python bench.py                       # 1 GPU: set-up, warm-up, the timed steps, the line
+    python bench.py --full                # + repetitions, write ceiling, API paths, self-play, CPU baseline
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8
 
-Rank 0 prints ONE JSON line (driver contract) with `roofline` and `cpu_baseline` objects.
+Rank 0 prints ONE JSON line (driver contract) with a `roofline` object (from the timed steps' own HIP events) and a
+`cpu_baseline` object (null unless --full).  A plain run does only what `value` needs; whatever else the bench
+measures -- runs of their own beside the headline -- is behind --full.
 """
 import argparse
 import contextlib
@@ -65,11 +68,19 @@ def parse():
     ap.add_argument("--chunk", type=int, default=256,
                     help="plies per launch of the fused rollout kernel (256 = the reference's n_steps, train.py:246)")
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need, each in runs of its own after the timed steps: four "
+                         "more timed repetitions, and on one GPU the write ceiling of the records' store pattern, the API "
+                         "paths, the replay, action-log and self-play rates, the CPU baseline and the GPU's rocminfo "
+                         "identity; on several ranks the compute-only run, and both exchange forms timed alone also when "
+                         "--allgather pins one (under auto a plain run times them too: they decide `value`)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="0 = every CPU this process may use (affinity mask and cgroup quota)")
-    ap.add_argument("--no-api-path", action="store_true", help="skip the extra per-step-launch measurement")
+    ap.add_argument("--no-api-path", action="store_true",
+                    help="with --full: skip the extra GPU measurements of one-GPU runs (write ceiling, API paths, replay, "
+                         "action log, self-play)")
     ap.add_argument("--mode", choices=("rollout", "selfplay"), default="rollout",
                     help="rollout = the BASELINE.json metric (default); selfplay = BASELINE config 3: the wrapper loop "
                          "with a small conv policy as agent and an opponent pool (agent-steps/s, NN time dominates)")
@@ -406,15 +417,17 @@ def write_ceiling_GBps(dev, nenv, chunk, rows, seconds=0.05):
     return rec.numel() * 8 * k / (e0.elapsed_time(e1) * 1e-3) / 1e9
 
 
-def gpu_identity(dev):
-    """Identity of the device the numbers were taken on: torch's device properties plus what `rocminfo` (a child
-    process) says about the first gfx950 agent -- marketing name (empty on this pool's image), max clock, CUs."""
+def gpu_identity(dev, rocminfo=True):
+    """Identity of the device the numbers were taken on: torch's device properties plus, with ``rocminfo``, what
+    `rocminfo` (a child process) says about the first gfx950 agent -- marketing name, max clock, CUs."""
     import re
     import subprocess
 
     p = torch.cuda.get_device_properties(dev)
     out = {"name": p.name, "arch": getattr(p, "gcnArchName", None), "compute_units": p.multi_processor_count,
            "memory_GiB": round(p.total_memory / 2 ** 30, 1), "hip": torch.version.hip, "rocminfo": None}
+    if not rocminfo:
+        return out
     try:
         text = subprocess.run(["rocminfo"], capture_output=True, text=True, timeout=20).stdout
         for block in text.split("*******")[1:]:
@@ -1159,11 +1172,11 @@ def main():
     plies = args.steps * chunk
     value = world * nenv * plies / dt
     gather_ms = [a.elapsed_time(b) for a, b in gather_events]
-    # SURVEY.md section 8d asks for repetitions: four more timed regions of the same K steps (not part of `value`)
+    # SURVEY.md section 8d asks for repetitions: four more timed regions of the same K steps (--full; not part of `value`)
     reps = [value]
     timing[0] = False
     watchdog.enter("repetitions")
-    for _ in range(4):
+    for _ in range(4 if args.full else 0):
         barrier()
         r0 = time.perf_counter()
         run_steps(args.steps * chunk)
@@ -1174,9 +1187,9 @@ def main():
             dist.all_reduce(rmax, op=dist.ReduceOp.MAX)
             rdt = float(rmax.item())
         reps.append(world * nenv * plies / rdt)
-    # for the decomposition: the same K launches with the exchange step switched off (compute only)
+    # for the decomposition (--full): the same K launches with the exchange step switched off (compute only)
     compute_only = None
-    if mode != "none":
+    if mode != "none" and args.full:
         def run_compute_only(total):
             done = 0
             while done < total:
@@ -1212,7 +1225,8 @@ def main():
         "setup_launches": args.settle,
         "ms_per_step": dt * 1e3 / args.steps,
         "value_without_exchange": compute_only,
-        "repetitions": {"values": reps, "median": sorted(reps)[len(reps) // 2], "min": min(reps), "max": max(reps)},
+        "repetitions": ({"values": reps, "median": sorted(reps)[len(reps) // 2], "min": min(reps), "max": max(reps)}
+                        if args.full else None),
         "step_definition": f"one launch of the fused rollout kernel = {chunk} plies on each of {nenv} envs per GPU",
         "higher_is_better": True,
         "scaling": "weak",
@@ -1270,8 +1284,9 @@ def main():
         dist.all_reduce(worst, op=dist.ReduceOp.MAX)
         mean_ms = float(worst.item())
         step_ms = dt * 1e3 / args.steps
-        compute_ms = world * nenv * plies / compute_only * 1e3 / args.steps
-        exposed_ms = max(0.0, step_ms - compute_ms)
+        # (the decomposition needs the compute-only run: null in a plain run)
+        compute_ms = world * nenv * plies / compute_only * 1e3 / args.steps if compute_only else None
+        exposed_ms = max(0.0, step_ms - compute_ms) if compute_ms is not None else None
         out["exchange"] = {
             "what": {"actions": "the action log (7-bit stream up to 128 cells, a byte up to 256, a byte and a bit beyond)" +
                                 (f"; every {keyframe}th chunk's message also carries the chunk-start state (keyframe), "
@@ -1298,7 +1313,7 @@ def main():
             "xgmi_link_peak_GBps": 153.0,
             "compute_ms_per_chunk": compute_ms,
             "exposed_ms_per_chunk": exposed_ms,           # step time minus the compute-only step time
-            "overlap_fraction": max(0.0, 1.0 - exposed_ms * every / mean_ms) if mean_ms else None,
+            "overlap_fraction": max(0.0, 1.0 - exposed_ms * every / mean_ms) if mean_ms and exposed_ms is not None else None,
         }
     if args.rehearse_exchange and world == 1:
         out["rehearsal"] = "the multi-GPU code path on one GPU (a one-rank communicator): not a measurement"
@@ -1308,11 +1323,12 @@ def main():
                                         if exchange is not None and exchange.direct else
                                         "ncclAllGather" if exchange is not None else "all_gather_into_tensor")
     # both forms of the exchange step alone (rank 0's clock): the one of the timed loop first, the other one last and
-    # under a watchdog, because the driver's multi-GPU run is the first time it meets more than one GPU
+    # under a watchdog, because a first multi-GPU run is the first time it meets more than one GPU.  --allgather auto
+    # decides `value` on these numbers; with a pinned form they are --full's
     alone = None
     exchange_hung = None  # name of the exchange form that never finished, on ANY rank
     line[0] = out
-    if exchange is not None:
+    if exchange is not None and (args.full or args.allgather == "auto"):
         alone = {}
         store = dist.distributed_c10d._get_default_store()
         for form in ((False, True) if not exchange.direct else (True, False)):
@@ -1363,15 +1379,17 @@ def main():
                                             **{key: ex[key] for key in ("allgather_ms", "recv_GBps_per_rank", "per_link_GBps",
                                                                         "exposed_ms_per_chunk", "overlap_fraction")}}
                 out["value"], out["ms_per_step"] = dvalue, tried["ms_per_step"]
-                exposed = max(0.0, tried["ms_per_step"] - ex["compute_ms_per_chunk"])
+                exposed = (max(0.0, tried["ms_per_step"] - ex["compute_ms_per_chunk"])
+                           if ex["compute_ms_per_chunk"] is not None else None)
                 ex.update(allgather_ms=dmean, exposed_ms_per_chunk=exposed,
                           recv_GBps_per_rank=(world - 1) * ex["bytes_per_rank_per_chunk"] / (dmean * 1e-3) / 1e9 if dmean else None,
                           per_link_GBps=ex["bytes_per_rank_per_chunk"] / (dmean * 1e-3) / 1e9 if dmean else None,
-                          overlap_fraction=max(0.0, 1.0 - exposed / dmean) if dmean else None,
+                          overlap_fraction=max(0.0, 1.0 - exposed / dmean) if dmean and exposed is not None else None,
                           algorithm="one grouped ncclSend + ncclRecv per peer (mnk_allgather_records_direct)",
                           transport="mnk_allgather_records_direct (C ABI, RCCL)")
                 out["transport"] = ex["transport"]
-                out["repetitions"]["note"] = "the repetitions ran with ncclAllGather; `value` is the re-run with the direct form"
+                if out["repetitions"] is not None:
+                    out["repetitions"]["note"] = "the repetitions ran with ncclAllGather; `value` is the re-run with the direct form"
                 ex["auto"] = "switched to the direct form: faster alone and in the loop"
             else:
                 ex["with_direct_sendrecv"] = tried
@@ -1389,11 +1407,11 @@ def main():
             stats = roll.stats.tolist()
             out["rollout_stats"] = {"episodes": stats[0], "mean_plies": stats[4] / max(stats[0], 1),
                                     "draw_rate": stats[3] / max(stats[0], 1)}
-        out["gpu"] = gpu_identity(dev)
+        out["gpu"] = gpu_identity(dev, rocminfo=args.full)
         jit = mnk_hip.jit_stats()
         if jit["compiled"] or jit["cache_hits"] or jit["failed"]:  # a board without a built-in variant: what hiprtc did for it
             out["jit"] = jit
-        if not multi and not args.no_api_path:
+        if args.full and not multi and not args.no_api_path:
             out["roofline"]["measured_write_ceiling_GBps"] = write_ceiling_GBps(dev, nenv, chunk, rows)
             out["roofline"]["frac_of_measured_write_ceiling"] = achieved / out["roofline"]["measured_write_ceiling_GBps"]
             out["api_path_env_steps_per_s"] = api_path_rate(env, args.seed)
@@ -1428,7 +1446,7 @@ def main():
                                                                    "env_side_ms_per_step", "nn_and_sampling_ms_per_step",
                                                                    "buffer_add_copied_bytes_per_agent_step")}
             out["selfplay"]["config3"]["workload"] = c3["config"]["workload"]
-        if not multi and not args.no_cpu_baseline:
+        if args.full and not multi and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(env, args.cpu_seconds, args.cpu_threads)
         else:
             out["cpu_baseline"] = None

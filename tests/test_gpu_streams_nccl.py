@@ -358,8 +358,8 @@ def test_sharded_self_play_ppo_example_keeps_its_replicas_identical():
 def test_bench_multi_gpu_code_path_rehearsed_on_one_gpu(extra):
     """``bench.py --rehearse-exchange``: the code path the driver's multi-GPU run takes -- process group (RCCL), the C ABI's
     communicator, the exchange step on a side stream overlapping the next chunk, both exchange forms timed alone under a
-    watchdog -- with one rank on this box's GPU.  stdout must hold the ONE JSON line and nothing else (RCCL's version
-    banner goes to stderr)."""
+    watchdog -- with one rank on this box's GPU, with ``--full`` (the compute-only run and the forms alone whatever
+    ``--allgather`` says).  stdout must hold the ONE JSON line and nothing else (RCCL's version banner goes to stderr)."""
     import json
 
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -369,8 +369,9 @@ def test_bench_multi_gpu_code_path_rehearsed_on_one_gpu(extra):
     if force:  # --allgather auto's second timed region (taken when the direct form is faster alone), forced
         env["MNK_BENCH_FORCE_DIRECT"] = "1"
         extra = []
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rehearse-exchange", "--steps", "6", "--warmup", "2",
-                          "--settle", "8", "--envs", "8192"] + extra, env=env, capture_output=True, text=True, timeout=600)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--rehearse-exchange", "--steps", "6",
+                          "--warmup", "2", "--settle", "8", "--envs", "8192"] + extra, env=env, capture_output=True, text=True,
+                         timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, out.stdout[:2000]

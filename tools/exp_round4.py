@@ -114,7 +114,7 @@ def fused(m=9, n=9, k=5, nenv=65536):
                   f"{alg * nenv / rows[True] / 1e3 / 8000:.2f} of 8 TB/s]", flush=True)
 
 
-from bench import train_cadence as cadence_times  # noqa: E402  (the driver-run line carries the 384-env row of this)
+from bench import train_cadence as cadence_times  # noqa: E402  (bench.py --full carries the 384-env row of this)
 
 
 def cadence(*sizes):

@@ -19,7 +19,7 @@ def counters(d, kernel_substr):
 def phases(root, kern, bench):
     """The dominant kernel's dispatches of the kernel-trace pass, split by the phase of bench.py they belong to (in
     dispatch order: --settle set-up launches at ramping clocks, --warmup launches, the --steps launches of the timed
-    region, then the four repetitions): one average over all of them mixes the cold launches with the timed ones and
+    region, then with --full the four repetitions): one average over all of them mixes the cold launches with the timed ones and
     reads higher than the run's own ms_per_step."""
     files = sorted(glob.glob(os.path.join(root, "trace", "**", "*_kernel_trace.csv"), recursive=True), key=os.path.getmtime)
     if not files or not bench:
