@@ -201,6 +201,10 @@ int mnk_sample_legal(const uint64_t* planes, int64_t N, int m, int n, uint64_t s
  * from softmax(masked logits) with one Philox uniform per row (stream MNK_STREAM_SAMPLE).
  * All-masked row -> uniform over C (cnn.py:76-77).
  * logp (optional) = log-probability of the chosen action under the masked softmax (f32 arithmetic).
+ * For finite logits of any magnitude the drawn cell is legal and logp is finite, within f32 rounding of the
+ * differences logit - max (no error term in the size of the logits themselves); non-finite logits (+-inf, NaN) are
+ * unspecified.  The row's uniform is (top 24 bits of the Philox word + 0.5) * 2^-24 rounded to f32, so the top word
+ * gives exactly 1.0: that point is the end of the walk and takes the last cell with weight.
  * seed_dev (optional): device pointer to a u64 that REPLACES `seed` -- the sampler's Philox key in device memory, so a
  * sampler captured into a hipGraph can be re-keyed without a new capture (a fresh opponent before every rollout,
  * train.py:106-114).  Row i draws from Philox(seed, env_id0 + i, step [+ *step_dev], MNK_STREAM_SAMPLE). */

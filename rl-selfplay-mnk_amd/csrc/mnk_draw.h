@@ -10,11 +10,16 @@
 //   1. slab_to_lds: a workgroup's contiguous slab of rows -> LDS with full-width loads (16 B of logits + the matching
 //      mask bytes per lane), the mask applied on the way (illegal cell -> -inf): LDS holds one f32 per cell;
 //   2. draw_row: LPR lanes per row (an aligned group inside one wave), lane s owning the interleaved cells s, s + LPR,
-//      ...: row max by DPP butterfly, weights 2^((logit - max) * log2 e) (one FMA + one v_exp per cell; -inf gives an
-//      exact 0), an LPR-lane inclusive scan, the uniform picks the point u * total on the cumulative axis (cells
+//      ...: row max by DPP butterfly, weights 2^((logit - max) * log2 e) (a subtract, a multiply and a v_exp per cell;
+//      -inf gives an exact 0), an LPR-lane inclusive scan, the uniform picks the point u * total on the cumulative axis (cells
 //      ordered lane-major), a ballot finds the lane that holds it and a count of that lane's cells below the point
 //      finds the cell.  If rounding leaves the point beyond the last cell's cumulative weight the last legal cell of
 //      the last weighted lane is taken.
+// The difference logit - max is formed before the scale (it is exact near the max), so the log-probability carries no
+// error in the size of the logits: an FMA against a rounded -max * log2 e, the earlier form, scaled every weight of a row
+// by the same 2^delta, which the draw did not notice but the log-probability did (off by up to |max| * 2^-24 nats), and
+// from |max| ~ 1.5e9 on the weights of a row all overflowed or all underflowed (an all-zero row fell back to cell 0,
+// masked or not).  tests/test_gpu_draw_exact.py holds every draw to a float64 inverse CDF.
 #pragma once
 #include "mnk_device.h"
 
@@ -187,12 +192,15 @@ __device__ __forceinline__ Drawn draw_row(const float* lrow, int C, float u, int
     for (int j = 0; j < K; ++j) l[j] = none_legal ? ((sub + LPR * j < C) ? 0.0f : NEG) : l[j];
     rowmax = none_legal ? 0.0f : rowmax;
   }
-  const float bias = -rowmax * LOG2E;
+  // l - rowmax first, then the scale: the difference is exact near the max (Sterbenz), so the max cell's weight is exactly
+  // 1 and no rounding error of rowmax * log2 e scales every weight of the row (an FMA against a rounded -rowmax * log2 e
+  // did: harmless to the draw, but logp() was off by up to |rowmax| * 2^-24 nats, and from |rowmax| ~ 1.5e9 on the
+  // weights all overflowed or all underflowed)
   float w[K];
   float mine = 0.0f;
 #pragma unroll
   for (int j = 0; j < K; ++j) {
-    w[j] = __builtin_amdgcn_exp2f(__builtin_fmaf(l[j], LOG2E, bias));  // 2^(-inf) = 0 for masked cells
+    w[j] = __builtin_amdgcn_exp2f((l[j] - rowmax) * LOG2E);  // 2^(-inf) = 0 for masked cells
     mine += w[j];
   }
   const float total_w = group_sum<LPR>(mine);

@@ -12,7 +12,7 @@
 //      the way (illegal cell -> -inf), so LDS holds one f32 per cell and the mask is never looked at again;
 //      the first ROWS threads meanwhile draw the rows' uniforms (one Philox block per row, not per lane);
 //   2. LPR lanes per row, lane s owning the interleaved cells s, s + LPR, s + 2 LPR, ...: row max by DPP butterfly,
-//      weights 2^((logit - max) * log2 e) (one FMA + one v_exp per cell; -inf gives an exact 0), an LPR-lane
+//      weights 2^((logit - max) * log2 e) (a subtract, a multiply, a v_exp per cell; -inf gives an exact 0), an LPR-lane
 //      inclusive scan, the uniform picks the point u * total on the cumulative axis (cells ordered lane-major --
 //      any fixed order gives a draw from the same distribution), a ballot finds the lane that holds it and a
 //      count of that lane's cells below the point finds the cell.

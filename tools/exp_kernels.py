@@ -8,7 +8,7 @@ import mnk_hip
 from env.torch_vector_mnk_env import TorchVectorMnkEnv
 from selfplay.random_rollout import RandomRollout, unpack_records
 from selfplay.torch_self_play_wrapper import TorchSelfPlayWrapper
-from selfplay.policy import RandomPolicy
+from selfplay.policy import FusedNNPolicy, RandomPolicy
 
 DEV = "cuda:0"
 
@@ -91,6 +91,17 @@ def main(m=9, n=9, k=5, N=65536):
     lgb = lg.to(torch.bfloat16)
     report("sample_logits bf16", timeit(lambda: sm.draw(lgb, mask, False)), N * (3 * C + 8), N)
     report("sample uniform (mask only)", timeit(lambda: sm.draw(None, mask, False)), N * (C + 8), N)
+    # the opponent's draw folded into the post kernel (k_selfplay_post<..., Draw<float, C>>): a FusedNNPolicy opponent
+    class Head(torch.nn.Module):
+        def forward(self, x, action_mask=None):
+            class D:
+                pass
+            d = D()
+            d.logits = x.float().flatten(2).sum(1) * 0.5 - 1.0
+            return d, None
+    wrap.set_opponent(FusedNNPolicy(Head(), seed=4))
+    o, _ = wrap.reset()
+    report("wrapper.step FusedNN opp (post draws)", timeit(agent_step) - us_s, N * (2 * (S + 8 * W + 4) + 14 * C + 32), N)
 
 if __name__ == "__main__":
     if len(sys.argv) > 1:  # exp_kernels.py 9x9x5 262144 ...
