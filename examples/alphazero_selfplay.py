@@ -1,0 +1,141 @@
+"""AlphaZero on the HIP env: PUCT self-play into an outcome-labelled ring (``SearchSelfPlay``), minibatches with the
+board's symmetries (``SearchReplayBuffer.sample``), the loss -sum(pi * log p) + (v - z)^2 weighted by ``weight`` (0 for
+records of games still running), and validation of the greedy network against ``RandomPolicy`` and ``TacticalPolicy``.
+Root noise is an evaluator wrapper (``RootNoise``): Dirichlet noise mixed into the priors of the first evaluator call of
+every search, the one on the roots.
+
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12
+"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "rl-selfplay-mnk_amd")]
+
+import torch  # noqa: E402
+import torch.nn as nn  # noqa: E402
+
+import __graft_entry__ as entry  # noqa: E402
+
+
+class PolicyValueNet(nn.Module):
+    """a small MLP with a policy head (masked logits) and a tanh value head: ``model(obs, mask) -> (dist, value)``"""
+
+    def __init__(self, cells, width=128):
+        super().__init__()
+        self.body = nn.Sequential(nn.Flatten(), nn.Linear(2 * cells, width), nn.ReLU(), nn.Linear(width, width), nn.ReLU())
+        self.pi, self.v = nn.Linear(width, cells), nn.Linear(width, 1)
+
+    def logits(self, obs, mask=None):
+        h = self.body(obs.float())
+        logits = self.pi(h)
+        if mask is not None:
+            logits = logits.masked_fill(~mask.bool(), -1e9)
+        return logits, torch.tanh(self.v(h)).reshape(-1)
+
+    def forward(self, obs, mask=None):
+        logits, v = self.logits(obs, mask)
+        return torch.distributions.Categorical(logits=logits, validate_args=False), v
+
+
+class RootNoise:
+    """(1 - eps) * P + eps * Dirichlet(alpha) on the legal cells, in the first of every ``iterations + 1`` evaluator
+    calls (the roots of a search); the other calls pass through"""
+
+    def __init__(self, inner, iterations, alpha=0.3, eps=0.25):
+        self.inner, self.period, self.alpha, self.eps, self.calls = inner, iterations + 1, alpha, eps, 0
+
+    def __call__(self, leaf_obs, leaf_mask):
+        priors, values = self.inner(leaf_obs, leaf_mask)
+        root = self.calls % self.period == 0
+        self.calls += 1
+        if not root or self.eps == 0:
+            return priors, values
+        conc = torch.full(priors.shape, self.alpha, dtype=torch.float32, device=priors.device)
+        noise = torch.distributions.Dirichlet(conc, validate_args=False).sample() * leaf_mask
+        noise = noise / noise.sum(dim=1, keepdim=True).clamp(min=1e-12)
+        return (1 - self.eps) * priors.float() + self.eps * noise, values
+
+
+def greedy(net):
+    from selfplay.policy import Policy
+
+    class Greedy(Policy):
+        def act(self, obs, deterministic=False):
+            with torch.no_grad():
+                logits, _ = net.logits(obs["observation"], obs["action_mask"])
+            return logits.argmax(dim=1)
+
+    return Greedy()
+
+
+def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates=40, batch=512, lr=2e-3, seed=0,
+          noise=True, log=print):
+    """self-play and training rounds; returns the network"""
+    entry.build()
+    from selfplay.policy import model_evaluator
+    from selfplay.search_selfplay import SearchSelfPlay
+
+    torch.manual_seed(seed)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    C = m * n
+    net = PolicyValueNet(C).to(dev)
+    opt = torch.optim.Adam(net.parameters(), lr=lr)
+    evaluator = model_evaluator(net)
+    if noise:
+        evaluator = RootNoise(evaluator, iterations)
+    sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
+                        capacity=2 * C, seed=seed)
+    plies = C if plies is None else plies
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(seed)
+    for r in range(rounds):
+        net.eval()
+        sp.play(plies)
+        net.train()
+        for _ in range(updates):
+            b = sp.buffer.sample(batch, generator=gen)
+            logits, v = net.logits(b["observation"], b["action_mask"])
+            logp = torch.log_softmax(logits, dim=1)
+            loss_pi = -(b["policy"] * logp.masked_fill(~b["action_mask"], 0.0)).sum(dim=1)
+            loss = ((loss_pi + (v - b["value"]) ** 2) * b["weight"]).sum() / b["weight"].sum().clamp(min=1.0)
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+        stats = sp.pop_game_stats()
+        log(f"round {r}: games {stats['games']} black {stats['black_wins']} white {stats['white_wins']} "
+            f"draws {stats['draws']} mean length {stats['mean_length']:.2f} loss {loss.item():.4f}")
+    net.eval()
+    return net
+
+
+def validate(net, m, n, k, episodes=1024):
+    from selfplay.policy import RandomPolicy, TacticalPolicy
+    from selfplay.validation import validate_gpu
+
+    out = {}
+    for name, opp in (("random", RandomPolicy(m * n, seed=1)), ("tactical", TacticalPolicy(k, seed=2))):
+        res = validate_gpu(greedy(net), opp, (m, n, k), n_episodes=episodes)
+        out[name] = {key.split("/")[-1]: val for key, val in res.items()}
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--board", default="3x3x3", help="MxNxK")
+    ap.add_argument("--envs", type=int, default=256)
+    ap.add_argument("--iterations", type=int, default=32)
+    ap.add_argument("--rounds", type=int, default=12)
+    ap.add_argument("--updates", type=int, default=40)
+    ap.add_argument("--seed", type=int, default=0)
+    a = ap.parse_args()
+    m, n, k = (int(x) for x in a.board.lower().split("x"))
+    net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed)
+    for name, res in validate(net, m, n, k).items():
+        print(f"vs {name}: win {res['win_rate']:.3f} loss {res['loss_rate']:.3f} draw {res['draw_rate']:.3f} "
+              f"score {res['score_rate']:.3f}")
+
+
+if __name__ == "__main__":
+    main()

@@ -62,6 +62,8 @@ extern "C" {
 #define MNK_ERR_NONE 0
 #define MNK_ERR_ACTION_RANGE 1 /* action outside [-m*n, m*n): the reference raises IndexError (env/torch_vector_mnk_env.py:68) */
 #define MNK_ERR_ILLEGAL_MOVE 2 /* strict mode only: occupied cell, message of env/torch_vector_mnk_env.py:102-104 */
+#define MNK_ERR_SYMMETRY 3     /* mnk_search_gather: a symmetry id outside [0, 8), or >= 4 on a board that is not square */
+#define MNK_ERR_VISITS 4       /* mnk_search_selfplay_step: a row without a positive visit count on a free cell */
 
 /* flags for mnk_step and the mnk_selfplay_* functions */
 #define MNK_STEP_STRICT 1u /* refuse moves onto occupied cells (the behaviour tests/test_mnk_integration.py:68-81 expects) */
@@ -121,6 +123,7 @@ extern "C" {
 #define MNK_STREAM_SAMPLE 3
 #define MNK_STREAM_PLAYOUT 4 /* the random plies of the Monte Carlo player's playouts (mnk_sample_playouts) */
 #define MNK_STREAM_SEARCH 5  /* the random plies of the tree-search player's playouts (mnk_sample_search) */
+#define MNK_STREAM_SELFPLAY 6 /* the move of a search self-play ply (mnk_search_selfplay_step) */
 
 int mnk_abi_version(void);
 /* Developer knobs (MNK_ROLLOUT_PAIR, MNK_ROLLOUT_FORM, MNK_JIT, MNK_ROLLOUT_SADDR, MNK_EMIT_ENVS, MNK_EMIT_THREADS: A/B
@@ -435,6 +438,50 @@ int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iteration
                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
                   float* root_value, void* stream);
 #define MNK_PUCT_ITERS_MAX 2048
+
+/* ---- search self-play: the env side of an AlphaZero loop.  A ply = a search that writes every row's root visit counts
+ * (PUCTSearchPolicy.act(visits=...), mnk_puct_step), then ONE mnk_search_selfplay_step launch that plays every row's move
+ * from those counts, records the position in a ring of T plies, labels the records of every game that ends with its
+ * outcome, resets the finished games and writes the next roots.  No host synchronisation per ply.
+ * Ring (T plies of N rows; T >= C = m*n, so a game never wraps onto its own records):
+ *   ring_planes u64[T][2][W][N]  the position BEFORE the ply as packed planes, channel 0 = the side to move there
+ *                                (PackedRolloutBuffer's layout: 16*W B per record)
+ *   ring_visits u16[T][N][C]     the visits of the ply's search, min(max(v, 0), 65535) on free cells, 0 on occupied ones
+ *   ring_z      i8[T][N]         the outcome from the view of the record's side to move: +1 win, -1 loss, 0 draw,
+ *                                MNK_Z_UNKNOWN while the game is running
+ * Row i of the launch: p = step [+ *step_dev], t = p mod T, x = Philox(seed [or *seed_dev], env_id0 + i, p,
+ * MNK_STREAM_SELFPLAY), g = the row's move count, n_a = its ring visits above (in action order):
+ *   the move: with maxn = max n_a > 0, if g < temp_plies the cell at which the n_a, accumulated in action order, first
+ *     exceed mulhi32(x, sum n_a) (temperature 1), else the mulhi32(x, |S|)-th cell of S = the cells of n_a = maxn
+ *     (temperature 0) -- mnk_puct_step's two rules.  maxn = 0: MNK_ERR_VISITS, the env is not played (its ring row t is
+ *     still written, with z unknown, and its next root is its unchanged position).
+ *   ring row t: the planes, the visits, z = MNK_Z_UNKNOWN; then the ply (the env's win test).  When it ends the game (L =
+ *     g + 1 plies, the records t - d mod T for d = 0 .. L-1): a win writes z = +1 for even d and -1 for odd d, a draw 0;
+ *     stats (optional, the rollout's int64[MNK_STATS_REPLICAS][MNK_STATS_STRIDE]) gain {1 game, a black win / a white
+ *     win / a draw, L}; the env is reset.
+ *   the next root: the canonical view (channel 0 = the side to move) of the row's position after the ply (a fresh board
+ *   after a reset) into obs [N][2][m][n] of obs_dtype and (optional) legal_mask u8[N][C].
+ * visits int32 [N][C]; temp_plies >= 0.  One wave per row.  Every host check runs before anything is enqueued. */
+#define MNK_Z_UNKNOWN (-128)
+int mnk_search_selfplay_step(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, const int32_t* visits,
+                             int temp_plies, uint64_t seed, const uint64_t* seed_dev, uint64_t step,
+                             const uint64_t* step_dev, int64_t env_id0, int64_t T, uint64_t* ring_planes,
+                             uint16_t* ring_visits, int8_t* ring_z, void* obs, int obs_dtype, uint8_t* legal_mask,
+                             int64_t* stats, int32_t* err, void* stream);
+/* A minibatch of ring records: sample b is the flat id idx[b] = t*N + i (negative ids wrap, an id outside [0, T*N) sets
+ * MNK_ERR_ACTION_RANGE as in mnk_gather_obs and gives zero planes, policy, value and weight) under symmetry s = sym[b]
+ * (sym int8 [B] or NULL = the identity).  Output cell (r, c) reads source cell (r', c'): start from (r, c); if s & 4,
+ * (r, c) <- (c, r) (square boards only); if s & 1, r <- m-1-r; if s & 2, c <- n-1-c.  An id s outside [0, 8), or >= 4 on
+ * a board that is not square, sets MNK_ERR_SYMMETRY (err[1] = b), is read as the identity and gets weight 0.
+ *   obs [B][2][m][n] (obs_dtype) and legal_mask u8[B][C]: the record's planes under the map (what mnk_gather_obs writes
+ *     for s = 0);
+ *   policy f32[B][C]: fdiv((float)n_src, (float)sum n) over the record's ring visits (one correctly rounded division;
+ *     0 when the sum is 0);
+ *   value f32[B] = z, weight f32[B] = 1; value = weight = 0 where z = MNK_Z_UNKNOWN.
+ * Every output may be NULL. */
+int mnk_search_gather(const uint64_t* ring_planes, const uint16_t* ring_visits, const int8_t* ring_z, int64_t T,
+                      int64_t N, int m, int n, const int64_t* idx, const int8_t* sym, int64_t B, void* obs, int obs_dtype,
+                      uint8_t* legal_mask, float* policy, float* value, float* weight, int32_t* err, void* stream);
 
 /* ---- the random-policy rollout of BASELINE.json (RandomPolicy.act -> env.step -> env.reset(done)),
  * T plies per env in one launch with the state held in registers.

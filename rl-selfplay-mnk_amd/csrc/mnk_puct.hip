@@ -3,6 +3,7 @@
 // launch backs up the previous evaluation and selects the next leaf (mnk_puct_step), so an act() is mnk_puct_begin,
 // I + 1 evaluator calls and I + 1 steps with no host synchronisation.  The rule: include/mnk_hip.h.
 #include "mnk_host.h"
+#include "mnk_wave_rows.h"
 
 // One tree node (12 B).  w is from the view of the player who moved into the node.
 struct MnkPuctNode {
@@ -42,19 +43,6 @@ __host__ __device__ inline MnkPuctLayout mnk_puct_layout(int NWg, int C, int I) 
 #define MNK_PUCT_ROWS 4  // rows (waves) per 256-lane workgroup
 #define MNK_PUCT_NONE 0xFFFFu
 
-// the wave's own LDS traffic: make this wave's stores (LDS and global) visible to its other lanes
-__device__ __forceinline__ void puct_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
-}
-
-template <int CN>
-__device__ __forceinline__ bool puct_stone(const MnkGeom& g, const uint32_t* plane, int cell) {
-  const uint32_t bit = mnk_cell_bit<CN>(g, (uint32_t)cell);
-  return (plane[bit >> 5] >> (bit & 31u)) & 1u;
-}
-
 // fsqrt((float)n) correctly rounded for a visit count n < 2^24.  The compiler lowers the square root of a converted
 // integer to a bare v_sqrt_f32, which may be an ulp off; sqrt(n) is compared with the midpoints around that result
 // exactly in f64 (a midpoint has 25 significant bits, its square 50) and the result moved by an ulp when it lies
@@ -74,23 +62,6 @@ __device__ __forceinline__ float puct_read(const void* p, int dtype, int64_t q) 
   return dtype == MNK_LOGITS_BF16 ? __uint_as_float((uint32_t)((const uint16_t*)p)[q] << 16) : ((const float*)p)[q];
 }
 
-// the leaf's canonical observation (channel 0 = the leaf's side to move: plane `flip` of pos) and legal mask, row i
-template <int NW, int CN>
-__device__ __forceinline__ void puct_write_leaf(const MnkGeom& g, const uint32_t* pos, int flip, int64_t i, void* leaf_obs,
-                                                int leaf_dtype, uint8_t* leaf_mask, int lane) {
-  const int C = g.C;
-  for (int q = lane; q < 2 * C; q += 64) {
-    const int ch = q >= C, cell = q - (ch ? C : 0);
-    const bool s = puct_stone<CN>(g, pos + (ch ^ flip) * NW, cell);
-    const int64_t o = i * 2 * C + q;
-    if (leaf_dtype == MNK_OBS_F32) ((float*)leaf_obs)[o] = s ? 1.0f : 0.0f;
-    else if (leaf_dtype == MNK_OBS_BF16) ((uint16_t*)leaf_obs)[o] = s ? (uint16_t)0x3F80 : (uint16_t)0;
-    else ((uint8_t*)leaf_obs)[o] = s ? 1 : 0;
-  }
-  for (int a = lane; a < C; a += 64)
-    leaf_mask[i * C + a] = !(puct_stone<CN>(g, pos, a) || puct_stone<CN>(g, pos + NW, a));
-}
-
 // ------------------------------------------------------------------ evaluation 0: the roots
 // One wave per row: the row into bit planes (LDS), the root node, the roots as the first leaves.
 template <int NW, int CN, int CK>
@@ -104,7 +75,7 @@ k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsign
   const int C = g.C, NWg = g.NW;
   uint32_t* pos = lds_pos[wave];
   for (int q = lane; q < 2 * NW; q += 64) pos[q] = 0u;
-  puct_wave_sync();
+  row_wave_sync();
   const size_t eb = (size_t)mnk_obs_bytes(obs_dtype);
   const unsigned char* src = (const unsigned char*)obs + (size_t)i * 2 * C * eb;
   for (int q = lane; q < 2 * C; q += 64) {
@@ -118,7 +89,7 @@ k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsign
       atomicOr(&pos[pl * NW + (bit >> 5)], 1u << (bit & 31u));
     }
   }
-  puct_wave_sync();
+  row_wave_sync();
   int stones = 0;
 #pragma unroll
   for (int w = 0; w < NW; ++w) stones += __popc(pos[w] | pos[NW + w]);
@@ -142,7 +113,7 @@ k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsign
     r.n = 0u; r.w = 0.0f; r.info = 0u;
     *(MnkPuctNode*)(row + L.node) = r;
   }
-  puct_write_leaf<NW, CN>(g, pos, 0, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+  row_write_view<NW, CN>(g, pos, 0, i, leaf_obs, leaf_dtype, leaf_mask, lane);
 }
 
 // ------------------------------------------------------------------ one backup, then one selection (or the move)
@@ -178,7 +149,7 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
     const int pl = q >= NW, w = q - (pl ? NW : 0);
     pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
   }
-  puct_wave_sync();
+  row_wave_sync();
 
   // ---- backup of the pending evaluation
   if (state & 1u) {
@@ -192,7 +163,7 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
       float* pr = prior + (int64_t)lf * C;
       uint16_t* cl = child + (int64_t)lf * C;
       for (int a = lane; a < C; a += 64) {
-        const bool occ = puct_stone<CN>(g, pos, a) || puct_stone<CN>(g, pos + NW, a);
+        const bool occ = row_stone<CN>(g, pos, a) || row_stone<CN>(g, pos + NW, a);
         cl[a] = occ ? (uint16_t)MNK_PUCT_NONE : (uint16_t)0;
         if (!occ) pr[a] = puct_read(priors, priors_dtype, i * C + a);
       }
@@ -202,7 +173,7 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
       k->n += 1u;
       k->w = __fadd_rn(k->w, ((depth - p) & 1) ? v : -v);
     }
-    puct_wave_sync();
+    row_wave_sync();
   }
 
   if (last) {
@@ -224,54 +195,11 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
       tot += (uint32_t)__shfl_xor((int)tot, off, 64);
     }
     int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells
-    if (maxn) {
-      const bool by_count = temperature == 1 && !deterministic;
-      uint32_t r = 0u;
-      if (by_count) {
-        r = __umulhi(x, tot);
-      } else {
-        uint32_t ns = 0u;
-        for (int a0 = 0; a0 < C; a0 += 64) {
-          const int a = a0 + lane;
-          const uint32_t ch = a < C ? child[a] : 0u;
-          const bool in = ch != 0u && ch != MNK_PUCT_NONE && node[min((int)ch, nodes - 1)].n == maxn;
-          ns += (uint32_t)__popcll(__ballot(in));
-        }
-        r = __umulhi(x, ns);
-      }
-      uint32_t before = 0u;  // (by_count: the visits of the chunks before; else: the members of S before)
-      for (int a0 = 0; a0 < C; a0 += 64) {
-        const int a = a0 + lane;
+    if (maxn)
+      mnk_pick_by_visits(C, x, temperature == 1 && !deterministic, maxn, tot, lane, [&](int a) {
         const uint32_t ch = a < C ? child[a] : 0u;
-        const uint32_t na = (ch != 0u && ch != MNK_PUCT_NONE) ? node[min((int)ch, nodes - 1)].n : 0u;
-        uint64_t hit;
-        if (by_count) {
-          uint32_t cum = na;  // inclusive scan over the chunk
-#pragma unroll
-          for (int off = 1; off < 64; off <<= 1) {
-            const uint32_t o = (uint32_t)__shfl_up((int)cum, off, 64);
-            if (lane >= off) cum += o;
-          }
-          hit = __ballot(before + cum > r);
-          before += (uint32_t)__shfl((int)cum, 63, 64);
-        } else {
-          const uint64_t in = __ballot(na == maxn && na != 0u);
-          const uint32_t cnt = (uint32_t)__popcll(in);
-          if (r < before + cnt) {
-            uint64_t b = in;
-            for (uint32_t s = before; s < r; ++s) b &= b - 1;  // drop the members before the r-th
-            hit = b;
-          } else {
-            hit = 0;
-          }
-          before += cnt;
-        }
-        if (hit) {
-          move = a0 + (int)__ffsll((unsigned long long)hit) - 1;
-          break;
-        }
-      }
-    }
+        return (ch != 0u && ch != MNK_PUCT_NONE) ? node[min((int)ch, nodes - 1)].n : 0u;
+      }, move);
     if (lane == 0) {
       actions[i] = move;
       if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
@@ -373,9 +301,9 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
     hdr[1] = (uint32_t)d;
     hdr[2] = nstate;
   }
-  puct_wave_sync();
+  row_wave_sync();
   for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
-  puct_write_leaf<NW, CN>(g, pos, d & 1, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+  row_write_view<NW, CN>(g, pos, d & 1, i, leaf_obs, leaf_dtype, leaf_mask, lane);
 }
 
 // ------------------------------------------------------------------ the entry points

@@ -15,14 +15,15 @@ LIB_PATH = os.environ.get("MNK_HIP_LIB") or os.path.join(_HERE, "libmnk_hip.so")
 ABI_VERSION = 6
 
 MNK_OK = 0
-ERR_NONE, ERR_ACTION_RANGE, ERR_ILLEGAL_MOVE = 0, 1, 2
+ERR_NONE, ERR_ACTION_RANGE, ERR_ILLEGAL_MOVE, ERR_SYMMETRY, ERR_VISITS = 0, 1, 2, 3, 4
 STEP_STRICT, STEP_AUTORESET = 1, 2
 LOGITS_F32, LOGITS_BF16 = 0, 1
 OBS_F32, OBS_BF16, OBS_U8 = 0, 1, 2
 ACT_U8, ACT_U16, ACT_BITS7, ACT_U8P1 = 1, 2, 3, 4
 COMM_ID_BYTES = 128
 SP_NEED_OPP, SP_WAS_RESET = 1, 2
-STREAM_MOVE, STREAM_OPP, STREAM_SIDE, STREAM_SAMPLE, STREAM_PLAYOUT, STREAM_SEARCH = 0, 1, 2, 3, 4, 5
+STREAM_MOVE, STREAM_OPP, STREAM_SIDE, STREAM_SAMPLE, STREAM_PLAYOUT, STREAM_SEARCH, STREAM_SELFPLAY = 0, 1, 2, 3, 4, 5, 6
+Z_UNKNOWN = -128  # MNK_Z_UNKNOWN: the outcome of a ring record whose game is still running
 PLAYOUTS_MAX = 4096  # MNK_PLAYOUTS_MAX: the largest playout count of mnk_sample_playouts
 SEARCH_ITERS_MAX = 2048  # MNK_SEARCH_ITERS_MAX: the largest iteration budget of mnk_sample_search
 SEARCH_PLAYOUTS_MAX = 256  # MNK_SEARCH_PLAYOUTS_MAX: the largest playout count per leaf of mnk_sample_search
@@ -93,6 +94,12 @@ SIGNATURES = {
     # sampler block, leaf obs, leaf dtype, leaf mask, actions, visits (int32 [N][C]), root value (f32 [N]), stream
     "mnk_puct_step": [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i, _vp, _i,
                       _vp, _vp, _vp, _vp, _vp],
+    # planes, meta, N, m, n, k, visits (int32 [N][C]), temp_plies, then seed, seed_dev, step, step_dev, env_id0, T, ring
+    # planes, ring visits, ring z, obs, obs dtype, legal mask, stats, err, stream
+    "mnk_search_selfplay_step": [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _u64, _vp, _u64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
+                                 _i, _vp, _vp, _vp, _vp],
+    # ring planes, ring visits, ring z, T, N, m, n, idx, sym, B, obs, obs dtype, legal mask, policy, value, weight, err, stream
+    "mnk_search_gather": [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],
     "mnk_action_log_words": [_i, _i],
     "mnk_replay_actions": [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp],

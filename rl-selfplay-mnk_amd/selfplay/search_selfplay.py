@@ -1,0 +1,96 @@
+"""Search self-play: PUCT plays itself on N boards in lockstep and fills a ``SearchReplayBuffer`` with outcome-labelled
+records (AlphaZero / expert iteration; the rule: include/mnk_hip.h, mnk_search_selfplay_step).
+
+A ply is ``PUCTSearchPolicy.act(visits=...)`` on the current roots, then one ``mnk_search_selfplay_step`` launch that
+plays every row's move from its root visits (temperature 1 for the first ``temp_plies`` plies of a game, then 0), records
+the position and the visits in the ring, labels the records of every game that ends, resets it and writes the next roots.
+Nothing waits on the host: the ply counter is a device word (the buffer's ``plies``) that the search's sampler and the
+step kernel both read, and one more tiny kernel advances it, so ``torch.cuda.graph`` can capture ``play(1)`` once the
+buffers exist (after one eager ply) and the evaluator is capturable.
+
+Root noise (Dirichlet) stays an evaluator wrapper: the first evaluator call of every ``act`` is on the roots, so a wrapper
+that counts its calls modulo ``iterations + 1`` knows which call to perturb (examples/alphazero_selfplay.py).
+"""
+from typing import Dict
+
+import torch
+
+import mnk_hip
+from alg.search_replay_buffer import SearchReplayBuffer
+from env.torch_vector_mnk_env import TorchVectorMnkEnv
+from selfplay.policy import PUCTSearchPolicy
+
+
+class SearchSelfPlay:
+    def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
+                 c: float = 1.25, temp_plies: int = None, capacity: int = None, seed=None, leaf_dtype=torch.float32,
+                 device="cuda"):
+        self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
+        C = self.m * self.n
+        self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
+        if self.temp_plies < 0:
+            raise ValueError(f"temp_plies must be >= 0, got {temp_plies}")
+        if self.num_envs < 1:
+            raise ValueError(f"num_envs must be >= 1, got {num_envs}")
+        if not mnk_hip.geometry_supported(self.m, self.n, self.k) or self.n < 2:
+            raise ValueError(f"unsupported board {self.m}x{self.n} (k={self.k})")
+        capacity = 2 * C if capacity is None else int(capacity)
+        if capacity < C:
+            raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
+        # (the policy checks model / evaluator, iterations, c and leaf_dtype before anything touches the GPU)
+        self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
+                                       temperature=0, leaf_dtype=leaf_dtype, seed=seed)
+        self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
+        dev = self.env._dev
+        self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
+        self.sampler = self.policy._sampler
+        self.sampler.step_dev = self.buffer.plies  # the search and the step both draw at the ply counter
+        self.env.reset()
+        self.obs = torch.empty((self.num_envs, 2, self.m, self.n), dtype=torch.float32, device=dev)
+        self.mask = torch.empty((self.num_envs, C), dtype=torch.bool, device=dev)
+        self.env.observe_into(obs=self.obs, mask=self.mask)  # a fresh board: black to move, absolute = canonical
+        self.visits = torch.zeros((self.num_envs, C), dtype=torch.int32, device=dev)
+        self.stats = torch.zeros((mnk_hip.STATS_REPLICAS, mnk_hip.STATS_STRIDE), dtype=torch.int64, device=dev)
+        self._ones = torch.ones(1, dtype=torch.int64, device=dev)
+
+    def play(self, plies: int = 1) -> None:
+        """``plies`` self-play plies on every board; enqueues work only"""
+        env, buf = self.env, self.buffer
+        stream = mnk_hip.stream_ptr(env._dev)
+        for _ in range(int(plies)):
+            self.policy.act({"observation": self.obs, "action_mask": self.mask}, visits=self.visits)
+            seed, seed_dev, step, step_dev, env_id0, _ = self.sampler.block()
+            mnk_hip.call("mnk_search_selfplay_step", mnk_hip.ptr(env._planes), mnk_hip.ptr(env._meta), self.num_envs,
+                         self.m, self.n, self.k, mnk_hip.ptr(self.visits), self.temp_plies, seed, seed_dev, step, step_dev,
+                         env_id0, buf.capacity, mnk_hip.ptr(buf.planes), mnk_hip.ptr(buf.visits), mnk_hip.ptr(buf.z),
+                         mnk_hip.ptr(self.obs), mnk_hip.OBS_F32, mnk_hip.ptr(self.mask), mnk_hip.ptr(self.stats),
+                         mnk_hip.ptr(env._err), stream)
+            buf.plies.add_(self._ones)
+            buf.plies_host += 1
+
+    def note_replayed(self, plies: int) -> None:
+        """a captured graph of ``play`` has been replayed for ``plies`` plies in all: the host's count of written plies
+        (what ``buffer.sample`` checks for emptiness) follows; the device counter advanced by itself"""
+        self.buffer.plies_host += int(plies)
+
+    def pop_game_stats(self) -> Dict[str, float]:
+        """games finished since the last call: games, black wins, white wins, draws and mean length (one sync)"""
+        tot = self.stats.sum(dim=0).tolist()
+        self.stats.zero_()
+        self.env.check_errors()
+        games = int(tot[0])
+        return {"games": games, "black_wins": int(tot[1]), "white_wins": int(tot[2]), "draws": int(tot[3]),
+                "mean_length": tot[4] / games if games else 0.0}
+
+    def state_dict(self) -> Dict[str, object]:
+        """env, ring, ply counter and Philox key: a restored run continues bit-exactly"""
+        return {"env": self.env.state_dict(), "buffer": self.buffer.state_dict(), "seed": self.sampler.seed,
+                "temp_plies": self.temp_plies, "stats": self.stats.cpu()}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.env.load_state_dict(state["env"])
+        self.buffer.load_state_dict(state["buffer"])
+        self.sampler.seed = int(state["seed"])
+        self.temp_plies = int(state["temp_plies"])
+        self.stats.copy_(state["stats"])
+        self.env.observe_into(obs=self.obs, mask=self.mask, flip_side=(self.env._meta & 1).to(torch.int64))
