@@ -13,6 +13,8 @@ Files written
   selfplay_<..>_<opp>_s<seed>.npz  G3: TorchSelfPlayWrapper trace with a row-local deterministic opponent
   edges.npz                     G4: the hand-written scenarios of tests/scenarios.py
   masked_logits.npz             G6 (epilogue part): masked-categorical head of the reference nets
+  boards_*.npz                  (``--more-boards``) the same two kinds on boards without a built-in kernel variant
+  siblings_*.npz                (``--sibling-boards``) ... on non-square boards that share a built-in variant
 """
 import os
 import sys
@@ -62,6 +64,15 @@ MORE_ENV_CASES = [(5, 5, 4, 48, 60, (0,)), (6, 7, 4, 64, 90, (0,)), (12, 12, 5, 
                   (3, 33, 3, 24, 120, (0,))]
 MORE_SELFPLAY_CASES = [(6, 7, 4, 64, 90, "hash", 0), (12, 12, 5, 40, 220, "highest", 0), (5, 5, 4, 48, 60, "lowest", 0),
                        (10, 10, 5, 32, 180, "hash", 1)]
+
+# ``--sibling-boards``: NON-SQUARE boards that run a built-in kernel variant -- the host dispatch matches a row of
+# MNK_BUILTIN_BOARDS by (n, k, words per plane), never by m, so 8x3x3 runs <1,3,3>, 7x9x5 <3,9,5>, 16x15x5 <8,15,5> and
+# 18x19x5 <12,19,5> (tests/line_rule.py) -- and have no run-time compiled twin to be compared with.  A prefix of their own
+# again; no file larger than the largest older one of its kind:
+#   siblings_env_<m>x<n>x<k>_s0.npz, siblings_selfplay_<m>x<n>x<k>_<opp>_s0.npz
+SIBLING_ENV_CASES = [(8, 3, 3, 64, 60, (0,)), (7, 9, 5, 96, 130, (0,)), (16, 15, 5, 40, 260, (0,)), (18, 19, 5, 24, 300, (0,))]
+SIBLING_SELFPLAY_CASES = [(8, 3, 3, 64, 60, "lowest", 0), (7, 9, 5, 64, 120, "hash", 0), (16, 15, 5, 24, 240, "highest", 0),
+                          (18, 19, 5, 16, 300, "hash", 0)]
 
 
 def _state(env, m, n):
@@ -221,15 +232,15 @@ def make_masked_logits():
     return out
 
 
-def more_boards():
+def more_boards(prefix="boards", env_cases=MORE_ENV_CASES, selfplay_cases=MORE_SELFPLAY_CASES):
     RefEnv, RefWrap, _ = import_reference()
-    for (m, n, k, nenv, steps, seeds) in MORE_ENV_CASES:
+    for (m, n, k, nenv, steps, seeds) in env_cases:
         for seed in seeds:
-            path = os.path.join(OUT, f"boards_env_{m}x{n}x{k}_s{seed}.npz")
+            path = os.path.join(OUT, f"{prefix}_env_{m}x{n}x{k}_s{seed}.npz")
             np.savez_compressed(path, **make_env_log(RefEnv, m, n, k, nenv, steps, seed))
             print("wrote", os.path.basename(path), os.path.getsize(path))
-    for (m, n, k, nenv, steps, opp, seed) in MORE_SELFPLAY_CASES:
-        path = os.path.join(OUT, f"boards_selfplay_{m}x{n}x{k}_{opp}_s{seed}.npz")
+    for (m, n, k, nenv, steps, opp, seed) in selfplay_cases:
+        path = os.path.join(OUT, f"{prefix}_selfplay_{m}x{n}x{k}_{opp}_s{seed}.npz")
         np.savez_compressed(path, **make_selfplay_trace(RefEnv, RefWrap, m, n, k, nenv, steps, opp, seed))
         print("wrote", os.path.basename(path), os.path.getsize(path))
 
@@ -237,6 +248,8 @@ def more_boards():
 def main():
     if "--more-boards" in sys.argv:  # only the round-4 additions: the older files are left as they are
         return more_boards()
+    if "--sibling-boards" in sys.argv:  # only the sibling boards of the built-in variants
+        return more_boards("siblings", SIBLING_ENV_CASES, SIBLING_SELFPLAY_CASES)
     RefEnv, RefWrap, _ = import_reference()
     for (m, n, k, nenv, steps, seeds) in ENV_CASES:
         for seed in seeds:

@@ -77,6 +77,30 @@ def test_oracle_on_the_fixtures_of_more_boards(golden_dir):
         replay_selfplay_trace(wrap, log, _oracle_set_sides)
 
 
+def test_oracle_on_the_fixtures_of_sibling_boards(golden_dir):
+    """Env op-logs and wrapper traces recorded from the reference on NON-SQUARE boards that run a built-in kernel variant
+    (8x3x3, 7x9x5, 16x15x5, 18x19x5: the host dispatch matches a variant by width, run length and word count, never by the
+    row count; ``make_golden.py --sibling-boards``): the oracle replays them, tests/test_gpu_variant_siblings.py replays
+    the same files on the HIP kernels, which on these boards have no run-time compiled twin to disagree with."""
+    envs, traces = golden_files(golden_dir, "siblings_env_"), golden_files(golden_dir, "siblings_selfplay_")
+    assert len(envs) == 4 and len(traces) == 4
+    boards = set()
+    for path in envs:
+        log = np.load(path)
+        m, n, k, nenv, _ = (int(v) for v in log["geom"])
+        replay_env_log(OracleVectorEnv(m, n, k, nenv), log)
+        assert log["dones"].any() and log["rewards"].any()
+        boards.add((m, n, k))
+    assert boards == {(8, 3, 3), (7, 9, 5), (16, 15, 5), (18, 19, 5)}
+    for path in traces:
+        log = np.load(path)
+        m, n, k, nenv, _ = (int(v) for v in log["geom"])
+        wrap = _ReplayOracleSelfPlay(OracleVectorEnv(m, n, k, nenv))
+        wrap.set_opponent(OPP[path.split("_")[-2]]())
+        replay_selfplay_trace(wrap, log, _oracle_set_sides)
+        assert (m, n, k) in boards and log["terminated"].any()
+
+
 @pytest.mark.parametrize("name", sorted(SCENARIOS))
 def test_oracle_edge_scenarios(golden_dir, name):
     sc = SCENARIOS[name]
