@@ -494,6 +494,35 @@ int mnk_rollout_random(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n
                        uint64_t seed, uint64_t step0, int64_t env_id0,
                        uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
                        void* act_log, int act_bytes, void* stream);
+/* Which kernel mnk_rollout_random runs for a launch: every form computes the same bits, so this query is the only
+ * place the choice shows.  Needs no GPU; uses the configuration the launcher uses (mnk_reload_config re-reads it).
+ * `records` / `act_bytes`: whether the launch has record pointers / its log format (0: no log); `jit_failed`: the
+ * answer once the board's run-time compiled kernel has failed to compile.  Returns one of the forms below ORed with
+ * the flags, 0 when nothing would be launched (N or T is 0), or the negative status mnk_rollout_random gives for the
+ * same arguments (MNK_ELAUNCH: the board's only kernel is the compiled one, and it failed).
+ * The rules, first match wins.  builtin: one of the five boards with ahead-of-time variants; fits32: (T * R + 1) * N * 8
+ * < 2^32, the record rows of the launch fit 32-bit byte offsets; small: MNK_ROLLOUT_PAIR if set, else N <= 32 768.
+ *  1. MNK_ROLLOUT_FORM=ws2|ws4 on 9x9x5 / 19x19x5 without a log: that form, at any N (other launches ignore the knob).
+ *  2. not builtin, and the compiled kernel is wanted (R > 16: always, it is the only one -- else MNK_JIT if set, else
+ *     N * T >= 2^20) and has not failed: MNK_ROLLOUT_JIT, as PAIR when fits32, small, the log is none / U8 / U16 and
+ *     MNK_ROLLOUT_FORM is not `lane`, else as LANE; SADDR (of the LANE kernel, which is also the next try after a PAIR
+ *     kernel that does not compile) iff records, N <= 65 536, fits32 and not MNK_ROLLOUT_SADDR=0.
+ *  3. PAIRW on the five-in-a-row builtin boards when fits32, the log is none / U8 / U16 / U8P1, and either
+ *     MNK_ROLLOUT_FORM=pairw (any N) or small and n >= 13 -- unless MNK_ROLLOUT_FORM=pair and the log is not U8P1.
+ *  4. PAIR on builtin boards when fits32, small and the log is none / U8 / U16.
+ *  5. LANE otherwise; SADDR as in 2, on builtin boards only.  MNK_ROLLOUT_FORM=lane gets here only where 3 and 4 do
+ *     not apply: by itself it does NOT select the one-lane kernel on a builtin board at a small batch
+ *     (MNK_ROLLOUT_PAIR=0 does). */
+#define MNK_ROLLOUT_LANE 1   /* one lane per env */
+#define MNK_ROLLOUT_PAIR 2   /* two lanes per env, the scan directions split */
+#define MNK_ROLLOUT_PAIRW 3  /* two lanes per env, the board's words split */
+#define MNK_ROLLOUT_WS2 4    /* two / four waves per group of 64 envs */
+#define MNK_ROLLOUT_WS4 5
+#define MNK_ROLLOUT_FORM_MASK 0xF
+#define MNK_ROLLOUT_SADDR 0x10     /* the one-lane kernel's record stores use 32-bit offsets */
+#define MNK_ROLLOUT_JIT 0x20       /* the board's run-time compiled kernel is tried first */
+#define MNK_ROLLOUT_JIT_ONLY 0x40  /* (with MNK_ROLLOUT_JIT) and there is no ahead-of-time kernel behind it */
+int mnk_rollout_form(int64_t N, int m, int n, int k, int T, int records, int act_bytes, int jit_failed);
 
 /* Boards other than 3x3x3, 9x9x5, 13x13x5, 15x15x5 and 19x19x5 have no ahead-of-time specialisation of the rollout
  * kernel; mnk_rollout_random compiles one with hiprtc (about a second, once per board / record / log-width

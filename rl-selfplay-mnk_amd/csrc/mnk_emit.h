@@ -50,7 +50,7 @@ __host__ __device__ inline int mnk_seg_words(int NW, int n) {  // SW: words of o
 // its compile-time variant from hiprtc once it is hot (mnk_jit.hip).
 #define MNK_BUILTIN_BOARDS(X) X(3, 9, 5, 81) X(1, 3, 3, 9) X(6, 13, 5, 169) X(8, 15, 5, 225) X(12, 19, 5, 361)
 
-__host__ __device__ inline bool mnk_geom_builtin(int n, int k, int NW) {
+__host__ __device__ constexpr bool mnk_geom_builtin(int n, int k, int NW) {
 #define MNK_BUILTIN_ROW(NWv, CNv, CKv, Cv) || (n == CNv && k == CKv && NW == NWv)
   return false MNK_BUILTIN_BOARDS(MNK_BUILTIN_ROW);
 #undef MNK_BUILTIN_ROW

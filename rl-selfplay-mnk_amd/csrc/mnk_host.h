@@ -85,7 +85,7 @@ inline int mnk_launch_status(const char* what) {
 // mnk_reload_config() (C ABI; mnk_hip.reload_config() in Python) reads them again after the environment has changed.
 struct MnkConfig {
   int pair_override = -1;  // MNK_ROLLOUT_PAIR=0/1: never / always two lanes per env (unset: by batch size)
-  int form = 0;            // MNK_ROLLOUT_FORM=lane|pair|pairw|ws2|ws4 -> 1..5 (unset / unknown: 0)
+  int form = 0;            // MNK_ROLLOUT_FORM=lane|pair|pairw|ws2|ws4 -> MNK_ROLLOUT_LANE .. _WS4 (unset / unknown: 0)
   int jit = -1;            // MNK_JIT=0/1 (unset: run-time specialisation from 2^20 env-steps per launch)
   int jit_api = -1;        // MNK_JIT_API=0/1: the same for the API-level kernels alone (unset: what MNK_JIT says; both unset:
                            // a board's own variant is compiled once the kernel is hot, mnk_jit_api_function)
@@ -94,14 +94,13 @@ struct MnkConfig {
   int emit_threads = 0;    // MNK_EMIT_THREADS=64|128|256 (the kernels are __launch_bounds__(256); 0: by output set)
   int gae_depth = 0;       // MNK_GAE_DEPTH=8|16|32: steps of loads mnk_gae keeps in flight per batch (0: the default)
 };
-enum { MNK_FORM_NONE = 0, MNK_FORM_LANE, MNK_FORM_PAIR, MNK_FORM_PAIRW, MNK_FORM_WS2, MNK_FORM_WS4 };
 
 inline MnkConfig mnk_read_config() {
   MnkConfig c;
   if (const char* v = getenv("MNK_ROLLOUT_PAIR")) c.pair_override = atoi(v) != 0 ? 1 : 0;
   if (const char* v = getenv("MNK_ROLLOUT_FORM")) {
     static const char* names[] = {"", "lane", "pair", "pairw", "ws2", "ws4"};
-    for (int f = 1; f <= 5; ++f)
+    for (int f = MNK_ROLLOUT_LANE; f <= MNK_ROLLOUT_WS4; ++f)
       if (!strcmp(v, names[f])) c.form = f;
   }
   if (const char* v = getenv("MNK_JIT")) c.jit = atoi(v) != 0 ? 1 : 0;
@@ -198,30 +197,6 @@ inline bool mnk_builtin_board(const MnkGeom& g, F&& f) {
     else MNK_CASE(32, 0, 0, __VA_ARGS__)                          \
   } while (0)
 #define MNK_K(name) HIP_KERNEL_NAME(name<NW, CN, CK>)
-// the variants a board of more than 256 cells can have (MNK_ACT_U8P1, up to 512 cells): 19x19x5 and the generic 16- and
-// 32-word forms
-#define MNK_DISPATCH_LARGE(g, ...)                                \
-  do {                                                            \
-    if (MNK_BUILTIN(g, MnkRow_::C > 256, __VA_ARGS__)) break;     \
-    if ((g).NW <= 16) MNK_CASE(16, 0, 0, __VA_ARGS__)             \
-    else MNK_CASE(32, 0, 0, __VA_ARGS__)                          \
-  } while (0)
-// the variants a board of at most 128 cells can have (the 7-bit action stream): 9x9x5, 3x3x3, generic up to 8 words
-#define MNK_DISPATCH_SMALL(g, ...)                                \
-  do {                                                            \
-    if (MNK_BUILTIN(g, MnkRow_::C <= 128, __VA_ARGS__)) break;    \
-    if ((g).NW <= 2) MNK_CASE(2, 0, 0, __VA_ARGS__)               \
-    else if ((g).NW <= 4) MNK_CASE(4, 0, 0, __VA_ARGS__)          \
-    else MNK_CASE(8, 0, 0, __VA_ARGS__)                           \
-  } while (0)
-
-// may the one-lane rollout address its record stores with 32-bit lane offsets (SADDR form)?  Only while a wave is
-// alone on its SIMD (where it measured faster) and a launch's record rows stay below 4 GiB
-inline bool mnk_rollout_saddr_ok(const MnkGeom& g, int64_t N, int T) {
-  if (mnk_config().saddr_off) return false;  // MNK_ROLLOUT_SADDR=0 switches the form off (A/B timing)
-  return N <= 65536 && ((int64_t)T * g.NW + 1) * N * 8 < (1ll << 32);
-}
-
 // is `act` a log format this board can use?  (0 = no log)
 constexpr bool mnk_act_format_ok(int act, int C) {
   return act == 0 || act == MNK_ACT_U16 || (act == MNK_ACT_U8 && C <= 256) || (act == MNK_ACT_BITS7 && C <= 128) ||
@@ -230,49 +205,6 @@ constexpr bool mnk_act_format_ok(int act, int C) {
 
 // the draw as a launch of its own (mnk_sample.hip)
 int mnk_launch_sample(const MnkSample& sa, int64_t N, int C, hipStream_t s);
-
-// one-lane rollout variants that write the action log (mnk_rollout_log.hip); act_bytes is 1 or 2
-void mnk_launch_rollout_log(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                            uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                            void* act_log, int act_bytes, void* stream);
-
-// two-lanes-per-env rollout variants (mnk_rollout_pair.hip); geometry must be one of the compile-time boards
-void mnk_launch_rollout_pair(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                             uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                             void* act_log, int act_bytes, void* stream);
-
-// waves-per-env-group rollout variants (mnk_rollout_ws.hip); ws = 2 or 4
-bool mnk_rollout_ws_supported(const MnkGeom& g, int act_bytes);
-void mnk_launch_rollout_ws(const MnkGeom& g, int ws, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                           uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                           void* act_log, int act_bytes, void* stream);
-
-// The rollout / replay kernels of boards with more than 16 register words per plane (planes of more than 512 bits) exist
-// as run-time specialisations only: their generic ahead-of-time forms took 20 minutes to compile for kernels nobody's
-// default board runs.  The API-level kernels keep a generic 32-word variant.
-#define MNK_DISPATCH16(g, ...)                                    \
-  do {                                                            \
-    if (MNK_BUILTIN(g, true, __VA_ARGS__)) break;                 \
-    if ((g).NW <= 2) MNK_CASE(2, 0, 0, __VA_ARGS__)               \
-    else if ((g).NW <= 4) MNK_CASE(4, 0, 0, __VA_ARGS__)          \
-    else if ((g).NW <= 8) MNK_CASE(8, 0, 0, __VA_ARGS__)          \
-    else MNK_CASE(16, 0, 0, __VA_ARGS__)                          \
-  } while (0)
-#define MNK_DISPATCH16_LARGE(g, ...)                              \
-  do {                                                            \
-    if (MNK_BUILTIN(g, MnkRow_::C > 256, __VA_ARGS__)) break;     \
-    MNK_CASE(16, 0, 0, __VA_ARGS__)                               \
-  } while (0)
-
-// run-time specialised rollout kernels (mnk_jit.hip, hiprtc): kind MNK_JIT_ROLLOUT / _REPLAY / _ROLLOUT_PAIR; nullptr when
-// the compile failed.  Launched with mnk_module_launch.
-hipFunction_t mnk_jit_rollout_function(const MnkGeom& g, int kind, bool rec, int act, bool saddr);
-
-// two lanes per env with the board split by words (mnk_rollout_pairw.hip): the five-in-a-row boards of MNK_BUILTIN_BOARDS
-bool mnk_rollout_pairw_supported(const MnkGeom& g);
-void mnk_launch_rollout_pairw(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                              uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                              void* act_log, int act_bytes, void* stream);
 
 // dynamic LDS a launch may ask for without raising the function's limit (the packed write-out stage of a run-time
 // specialised kernel is larger than the table form's: launches that would not fit stay on the ahead-of-time kernels)
@@ -326,3 +258,161 @@ inline void mnk_module_launch(void (*signature)(P...), hipFunction_t fn, dim3 gr
   std::tuple<P...> params{static_cast<P>(a)...};
   (void)mnk_module_launch_impl(fn, grid, block, lds, s, params, std::index_sequence_for<P...>{});  // (mnk_launch_status reads the error)
 }
+
+// an ahead-of-time kernel or, with `fn`, the run-time compiled function of the same kernel template
+template <typename... P, typename... A>
+inline void mnk_launch(void (*kernel)(P...), hipFunction_t fn, dim3 grid, dim3 block, hipStream_t s, const A&... a) {
+  if (fn) mnk_module_launch(kernel, fn, grid, block, 0, s, a...);
+  else hipLaunchKernelGGL(kernel, grid, block, 0, s, a...);
+}
+
+// ================================================================== the random rollout and the replay of its log
+// (mnk_rollout*.hip).  Every rollout kernel takes one parameter list, MnkRolloutArgs; what each kernel form can do is
+// mnk_rollout_form_ok and which one a launch gets is mnk_rollout_plan -- pure functions, stated here once.
+struct MnkRolloutArgs {
+  MnkGeom g;
+  uint64_t* planes; uint32_t* meta;  // the state, updated in place
+  int64_t N; int T;
+  uint64_t seed, step0; int64_t env_id0;
+  uint64_t* rec_planes; uint32_t* rec_meta;  // records: both pointers or neither
+  int64_t* stats;
+  void* act_log; int act;  // the log and its format (MNK_ACT_*), 0 without a log
+  hipStream_t stream;
+  bool rec() const { return rec_planes != nullptr; }
+  dim3 grid(int envs_per_block) const { return dim3((unsigned)((N + envs_per_block - 1) / envs_per_block)); }
+};
+
+// (`kernel` alone: the ahead-of-time kernel; with `fn`: the module function, `kernel` any instantiation of its template)
+template <typename K>
+inline void mnk_rollout_launch(K kernel, hipFunction_t fn, dim3 grid, dim3 block, const MnkRolloutArgs& a) {
+  mnk_launch(kernel, fn, grid, block, a.stream, a.g, a.planes, a.meta, a.N, a.T, a.seed, a.step0, a.env_id0, a.rec_planes,
+             a.rec_meta, (unsigned long long*)a.stats, a.act_log);
+}
+
+// The (rec, act) ladder: f(std::bool_constant<REC>{}, std::integral_constant<int, ACT>{}) for the run-time (rec, act).
+// `keep(REC, ACT)`, a captureless lambda, names the combinations the caller has kernels for: f is instantiated for no
+// other, and false comes back when the run-time pair is not among them.
+template <bool REC, int ACT, typename Keep, typename F>
+inline bool mnk_rec_act_case(bool rec, int act, Keep keep, F& f) {
+  if constexpr (keep(REC, ACT)) {
+    if (rec == REC && act == ACT) {
+      f(std::bool_constant<REC>{}, std::integral_constant<int, ACT>{});
+      return true;
+    }
+  }
+  return false;
+}
+template <typename Keep, typename F, int... ACT>
+inline bool mnk_rec_act_cases(bool rec, int act, Keep keep, F& f, std::integer_sequence<int, ACT...>) {
+  return ((mnk_rec_act_case<true, ACT>(rec, act, keep, f) || mnk_rec_act_case<false, ACT>(rec, act, keep, f)) || ...);
+}
+template <typename Keep, typename F>
+inline bool mnk_rec_act(bool rec, int act, Keep keep, F&& f) {
+  return mnk_rec_act_cases(rec, act, keep, f, std::make_integer_sequence<int, MNK_ACT_U8P1 + 1>{});
+}
+
+// f(MnkBoard{}) for the ahead-of-time one-lane rollout / replay variant of g's board: its row of MNK_BUILTIN_BOARDS, else
+// the generic form of its word count (CN = CK = C = 0).  Boards with more than 16 register words per plane (planes of
+// more than 512 bits) have these kernels as run-time specialisations only: their generic ahead-of-time forms took 20
+// minutes to compile for kernels nobody's default board runs.  The API-level kernels keep a generic 32-word variant.
+template <typename F>
+inline void mnk_rollout_board(const MnkGeom& g, F&& f) {
+  if (mnk_builtin_board(g, [&](auto row) { f(row); return true; })) return;
+  if (g.NW <= 2) f(MnkBoard<2, 0, 0, 0>{});
+  else if (g.NW <= 4) f(MnkBoard<4, 0, 0, 0>{});
+  else if (g.NW <= 8) f(MnkBoard<8, 0, 0, 0>{});
+  else f(MnkBoard<16, 0, 0, 0>{});
+}
+// is that variant built with log format `act`?  The bit-packed logs only where a board that takes the variant can use
+// them: U8P1 (more than 256 cells) on 19x19 and the generic 16-word form, the 7-bit stream (at most 128 cells) on 9x9, 3x3
+// and the generic forms of up to 8 words (e.g. 11x11 = 121 cells, NW 5); bytes and 16 bits everywhere.
+template <typename Row>
+constexpr bool mnk_lane_built(int act) {
+  if (act == MNK_ACT_U8P1) return Row::CN ? Row::C > 256 : Row::NW == 16;
+  if (act == MNK_ACT_BITS7) return Row::CN ? Row::C <= 128 : Row::NW <= 8;
+  return true;
+}
+
+// ---- what each kernel form can do.  `form`: MNK_ROLLOUT_* of mnk_hip.h, or the run-time compiled pair kernel:
+enum { MNK_ROLLOUT_PAIR_JIT = MNK_ROLLOUT_WS4 + 1 };
+constexpr bool mnk_rollout_form_ok(int form, int n, int k, int NW, int C, int act) {
+  const bool builtin = mnk_geom_builtin(n, k, NW), bytes = act == 0 || act == MNK_ACT_U8 || act == MNK_ACT_U16;
+  switch (form) {
+    case MNK_ROLLOUT_LANE: return mnk_act_format_ok(act, C);
+    // (the direction split writes byte / 16-bit logs only; every row has them, 19x19's byte log included, which no launch
+    // asks for -- 361 cells -- but which stays built)
+    case MNK_ROLLOUT_PAIR: return builtin && bytes;
+    case MNK_ROLLOUT_PAIR_JIT: return bytes;
+    // the five-in-a-row rows: 9x9, 13x13, 15x15, 19x19.  Boards up to 256 cells log a byte per action; 19x19 = 361 needs
+    // two, or a byte and a bit
+    case MNK_ROLLOUT_PAIRW: return builtin && k == 5 && (bytes || (act == MNK_ACT_U8P1 && C > 256));
+    case MNK_ROLLOUT_WS2:
+    case MNK_ROLLOUT_WS4: return builtin && (n == 9 || n == 19) && act == 0;
+  }
+  return false;
+}
+template <typename Row>
+constexpr bool mnk_rollout_row_ok(int form, int act) {
+  return mnk_rollout_form_ok(form, Row::CN, Row::CK, Row::NW, Row::C, act);
+}
+
+// do the record rows of one launch fit 32-bit byte offsets?  (what the two-lane forms and the SADDR stores address with)
+constexpr bool mnk_rollout_fits32(int NW, int64_t N, int T) { return ((int64_t)T * NW + 1) * N * 8 < (1ll << 32); }
+
+// ---- which kernel a launch gets
+enum { MNK_PLAN_AOT = 0, MNK_PLAN_JIT_TRY, MNK_PLAN_JIT_ONLY };
+struct MnkRolloutPlan {
+  int form;    // MNK_ROLLOUT_LANE .. _WS4; 0: nothing to launch, `status` says why
+  bool saddr;  // the one-lane kernel stores its records as `uniform base + 32-bit lane offset` (mnk_rollout_lane.h)
+  int jit;     // MNK_PLAN_*: the ahead-of-time kernel / the board's run-time compiled one, with / without one behind it
+  int status = MNK_OK;
+};
+
+// The rules of mnk_hip.h (mnk_rollout_form), in their order.  No HIP call, no environment, no allocation.
+inline MnkRolloutPlan mnk_rollout_plan(const MnkGeom& g, int64_t N, int T, bool rec, int act, const MnkConfig& cfg,
+                                       bool jit_failed) {
+  const auto ok = [&](int form) { return mnk_rollout_form_ok(form, g.n, g.k, g.NW, g.C, act); };
+  const bool fits32 = mnk_rollout_fits32(g.NW, N, T);
+  // two lanes per env only while both lanes of every env still fit one wave per SIMD (2N <= 65 536 lanes: 9x9x5 106 vs
+  // 135 us per 256 plies at 32 768 envs, 164 vs 135 at 36 864; tools/exp_pair_threshold.py)
+  const bool small = cfg.pair_override >= 0 ? cfg.pair_override != 0 : N <= 32768;
+  // 32-bit record offsets while a wave is alone on its SIMD (N <= 65 536: the kernel is bound by its instruction count and
+  // this saves ~4 of ~150 per ply: 92.0 -> 88.5 us at the headline size); from 131 072 envs up the kernel is bound by the
+  // HBM write rate and the 64-bit form measured faster (157 vs 166-184 us), so it stays there
+  const bool saddr = rec && !cfg.saddr_off && N <= 65536 && fits32;
+  // 1. a forced waves-per-group form (A/B timing, parity tests), where the board has it
+  if ((cfg.form == MNK_ROLLOUT_WS2 || cfg.form == MNK_ROLLOUT_WS4) && ok(cfg.form)) return {cfg.form, false, MNK_PLAN_AOT};
+  // 2. a board without ahead-of-time variants gets its own at run time (mnk_jit.hip) once a launch is large enough to pay
+  // for the ~1 s of compilation: 2^20 env-steps (4 096 envs x 256 plies).  Two lanes per env for small batches, like the
+  // built-in boards; the compiled one-lane kernel is also the next try after a pair kernel that does not compile.
+  if (!mnk_geom_builtin(g.n, g.k, g.NW)) {
+    const bool only = g.NW > 16;  // (mnk_rollout_board)
+    const bool want = only || (cfg.jit >= 0 ? cfg.jit != 0 : N * (int64_t)T >= (1ll << 20));
+    if (want && !jit_failed) {
+      const bool pair = ok(MNK_ROLLOUT_PAIR_JIT) && fits32 && small && cfg.form != MNK_ROLLOUT_LANE;
+      return {pair ? MNK_ROLLOUT_PAIR : MNK_ROLLOUT_LANE, saddr, only ? MNK_PLAN_JIT_ONLY : MNK_PLAN_JIT_TRY};
+    }
+    if (only) return {0, false, MNK_PLAN_AOT, MNK_ELAUNCH};
+  }
+  // 3. two lanes per env split by WORDS on the boards where that measured faster (us per 256 plies at 32 768 envs, by
+  // directions / by words: 19x19 216 / 164, 15x15 155 / 135, 13x13 127 / 117; 9x9 86 / 98 stays split by directions).
+  // A forced `pair` yields to it for the log only the word split writes.
+  if (ok(MNK_ROLLOUT_PAIRW) && fits32 &&
+      (cfg.form == MNK_ROLLOUT_PAIRW || (small && g.n >= 13 && !(cfg.form == MNK_ROLLOUT_PAIR && ok(MNK_ROLLOUT_PAIR)))))
+    return {MNK_ROLLOUT_PAIRW, false, MNK_PLAN_AOT};
+  // 4. split by directions
+  if (ok(MNK_ROLLOUT_PAIR) && fits32 && small) return {MNK_ROLLOUT_PAIR, false, MNK_PLAN_AOT};
+  // 5. one lane per env (the 7-bit log exists in this form only); generic boards address records with 64-bit pointers
+  return {MNK_ROLLOUT_LANE, saddr && mnk_geom_builtin(g.n, g.k, g.NW), MNK_PLAN_AOT};
+}
+
+// the launchers of the forms, one translation unit each (they compile in parallel); the plan has checked mnk_rollout_form_ok
+void mnk_launch_rollout_lane(const MnkRolloutArgs& a, bool saddr);  // without a log (mnk_rollout.hip)
+void mnk_launch_rollout_log(const MnkRolloutArgs& a, bool saddr);   // one lane, with one (mnk_rollout_log.hip)
+void mnk_launch_rollout_pair(const MnkRolloutArgs& a);
+void mnk_launch_rollout_pairw(const MnkRolloutArgs& a);
+void mnk_launch_rollout_ws(const MnkRolloutArgs& a, int ws);  // ws = 2 or 4
+
+// run-time specialised rollout kernels (mnk_jit.hip, hiprtc): kind MNK_JIT_ROLLOUT / _REPLAY / _ROLLOUT_PAIR; nullptr when
+// the compile failed.  Launched with mnk_launch.
+hipFunction_t mnk_jit_rollout_function(const MnkGeom& g, int kind, bool rec, int act, bool saddr);

@@ -390,9 +390,9 @@ int64_t mnk_jit_compile_kernel(int m, int n, int k, int record, int act_bytes, i
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
-  if (kind < MNK_JIT_ROLLOUT || kind > MNK_JIT_ROLLOUT_PAIR || !mnk_act_format_ok(act_bytes, g.C)) return MNK_EINVAL;
-  if (kind == MNK_JIT_REPLAY && act_bytes == 0) return MNK_EINVAL;
-  if (kind == MNK_JIT_ROLLOUT_PAIR && (act_bytes == MNK_ACT_BITS7 || act_bytes == MNK_ACT_U8P1)) return MNK_EINVAL;
+  if (kind < MNK_JIT_ROLLOUT || kind > MNK_JIT_ROLLOUT_PAIR || (kind == MNK_JIT_REPLAY && act_bytes == 0)) return MNK_EINVAL;
+  if (!mnk_act_format_ok(act_bytes, g.C)) return MNK_EINVAL;
+  if (kind == MNK_JIT_ROLLOUT_PAIR && !mnk_rollout_form_ok(MNK_ROLLOUT_PAIR_JIT, g.n, g.k, g.NW, g.C, act_bytes)) return MNK_EINVAL;
   // (saddr on a one-lane rollout with records: the form a 65 536-env launch uses)
   return compiled_size(kRolloutProgram, rollout_kernel_name(g, kind, record != 0, act_bytes, kind == MNK_JIT_ROLLOUT && record != 0));
 }

@@ -12,27 +12,18 @@
 // and the state update are done redundantly by both lanes (cheaper than exchanging them).  Results are
 // bit-identical to the one-lane kernel (all compile-time board geometries).  The pair form executes 1.6x the
 // instructions per env, so it wins exactly while both lanes of every env fit one wave per SIMD (2N <= 65 536
-// lanes) and the launcher uses it only up to 32 768 envs.
+// lanes): the batch-size rule of mnk_rollout_plan (mnk_host.h).
 
 // (the kernel and its body live in mnk_rollout_lane.h: boards without an ahead-of-time variant get this form compiled
 // at run time too, mnk_jit.hip)
 
-void mnk_launch_rollout_pair(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                             uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                             void* act_log, int act_bytes, void* stream) {
-  const bool rec = rec_planes && rec_meta;
-  const dim3 pgrid((unsigned)((N + 31) / 32));
-  // (every board, 19x19 included, has the byte log: the launcher never asks for it there -- 361 cells -- but it stays built)
-#define MNK_PAIR(REC, ACTB)                                                                                    \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random_pair<NW, CN, CK, REC, ACTB>), pgrid, dim3(64), 0,        \
-                     (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta,   \
-                     (unsigned long long*)stats, act_log)
-  MNK_BUILTIN(g, true,
-              if (rec && act_bytes == 1) MNK_PAIR(true, 1);
-              else if (rec && act_bytes == 2) MNK_PAIR(true, 2);
-              else if (rec) MNK_PAIR(true, 0);
-              else if (act_bytes == 1) MNK_PAIR(false, 1);
-              else if (act_bytes == 2) MNK_PAIR(false, 2);
-              else MNK_PAIR(false, 0));
-#undef MNK_PAIR
+void mnk_launch_rollout_pair(const MnkRolloutArgs& a) {
+  mnk_builtin_board(a.g, [&](auto row) {
+    using Row = decltype(row);
+    return mnk_rec_act(a.rec(), a.act, [](bool, int act) { return mnk_rollout_row_ok<Row>(MNK_ROLLOUT_PAIR, act); },
+                       [&](auto rec, auto act) {
+                         mnk_rollout_launch(k_rollout_random_pair<Row::NW, Row::CN, Row::CK, decltype(rec)::value, decltype(act)::value>,
+                                            nullptr, a.grid(32), dim3(64), a);
+                       });
+  });
 }

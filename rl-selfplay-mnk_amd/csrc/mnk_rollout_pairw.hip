@@ -354,32 +354,13 @@ k_rollout_random_pairw(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, i
 
 }  // namespace
 
-// the boards this form has variants for: the five-in-a-row rows of MNK_BUILTIN_BOARDS (9x9, 13x13, 15x15, 19x19)
-#define MNK_PAIRW_BOARD (MnkRow_::CK == 5)
-
-bool mnk_rollout_pairw_supported(const MnkGeom& g) { return MNK_BUILTIN(g, MNK_PAIRW_BOARD, (void)0); }
-
-void mnk_launch_rollout_pairw(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                              uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                              void* act_log, int act_bytes, void* stream) {
-  const bool rec = rec_planes && rec_meta;
-  const dim3 pgrid((unsigned)((N + 31) / 32));
-#define MNK_PW(REC, ACTB)                                                                                       \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random_pairw<NW, CN, CK, REC, ACTB>), pgrid, dim3(64), 0,        \
-                     (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta,    \
-                     (unsigned long long*)stats, act_log)
-  // boards up to 256 cells log a byte per action; 19x19 = 361 needs two, or a byte and a bit (MNK_ACT_U8P1)
-  MNK_BUILTIN(g, MNK_PAIRW_BOARD,
-              if (act_bytes == MNK_ACT_U8P1) {
-                if constexpr (mnk_act_format_ok(MNK_ACT_U8P1, MnkRow_::C)) {
-                  if (rec) MNK_PW(true, 4);
-                  else MNK_PW(false, 4);
-                }
-              } else if (rec && act_bytes == 1) MNK_PW(true, 1);
-              else if (rec && act_bytes == 2) MNK_PW(true, 2);
-              else if (rec) MNK_PW(true, 0);
-              else if (act_bytes == 1) MNK_PW(false, 1);
-              else if (act_bytes == 2) MNK_PW(false, 2);
-              else MNK_PW(false, 0));
-#undef MNK_PW
+void mnk_launch_rollout_pairw(const MnkRolloutArgs& a) {
+  mnk_builtin_board(a.g, [&](auto row) {
+    using Row = decltype(row);
+    return mnk_rec_act(a.rec(), a.act, [](bool, int act) { return mnk_rollout_row_ok<Row>(MNK_ROLLOUT_PAIRW, act); },
+                       [&](auto rec, auto act) {
+                         mnk_rollout_launch(k_rollout_random_pairw<Row::NW, Row::CN, Row::CK, decltype(rec)::value, decltype(act)::value>,
+                                            nullptr, a.grid(32), dim3(64), a);
+                       });
+  });
 }

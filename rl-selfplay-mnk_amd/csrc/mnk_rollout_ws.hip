@@ -68,31 +68,14 @@ k_rollout_random_ws(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int 
               (unsigned long long)lds_stats[threadIdx.x]);
 }
 
-// the boards this form has variants for: the 9x9x5 and 19x19x5 rows of MNK_BUILTIN_BOARDS
-#define MNK_WS_BOARD (MnkRow_::CN == 9 || MnkRow_::CN == 19)
-
-// ws = 2 or 4; geometry must be one of MNK_WS_BOARD (mnk_rollout_ws_supported)
-bool mnk_rollout_ws_supported(const MnkGeom& g, int act_bytes) {
-  return !act_bytes && MNK_BUILTIN(g, MNK_WS_BOARD, (void)0);
-}
-
-void mnk_launch_rollout_ws(const MnkGeom& g, int ws, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed,
-                           uint64_t step0, int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, int64_t* stats,
-                           void* act_log, int act_bytes, void* stream) {
-  const bool rec = rec_planes && rec_meta;
-  const dim3 grid((unsigned)((N + 63) / 64));
-#define MNK_WS(REC, WSv)                                                                                          \
-  hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_random_ws<NW, CN, CK, REC, 0, WSv>), grid, dim3(64 * WSv), 0,        \
-                     (hipStream_t)stream, g, planes, meta, N, T, seed, step0, env_id0, rec_planes, rec_meta,       \
-                     (unsigned long long*)stats, act_log)
-  (void)act_bytes;
-  MNK_BUILTIN(g, MNK_WS_BOARD,
-              if (ws == 4) {
-                if (rec) MNK_WS(true, 4);
-                else MNK_WS(false, 4);
-              } else {
-                if (rec) MNK_WS(true, 2);
-                else MNK_WS(false, 2);
-              });
-#undef MNK_WS
+// ws = 2 or 4; the boards of mnk_rollout_form_ok(MNK_ROLLOUT_WS2 / _WS4), no log
+void mnk_launch_rollout_ws(const MnkRolloutArgs& a, int ws) {
+  mnk_builtin_board(a.g, [&](auto row) {
+    using Row = decltype(row);
+    return mnk_rec_act(a.rec(), 0, [](bool, int act) { return mnk_rollout_row_ok<Row>(MNK_ROLLOUT_WS2, act); }, [&](auto rec, auto) {
+      constexpr bool REC = decltype(rec)::value;
+      if (ws == 4) mnk_rollout_launch(k_rollout_random_ws<Row::NW, Row::CN, Row::CK, REC, 0, 4>, nullptr, a.grid(64), dim3(256), a);
+      else mnk_rollout_launch(k_rollout_random_ws<Row::NW, Row::CN, Row::CK, REC, 0, 2>, nullptr, a.grid(64), dim3(128), a);
+    });
+  });
 }

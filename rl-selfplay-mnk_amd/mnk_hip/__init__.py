@@ -35,6 +35,9 @@ STATS_REPLICAS, STATS_STRIDE, STATS_COUNTERS = 64, 8, 5
 JIT_API_SP_TACTICAL, JIT_API_SP_TACTICAL_DRAW, JIT_API_SAMPLE_TACTICAL = 19, 20, 23  # (TACTICAL_DRAW + logits form)
 JIT_API_COUNT = 24
 REC_ACTION_MASK, REC_REWARD_SHIFT, REC_DONE_BIT, REC_SIDE_BIT = 0xFFFF, 16, 24, 25
+# what rollout_form() returns: one of the kernel forms (MNK_ROLLOUT_* of include/mnk_hip.h), ORed with the flags
+ROLLOUT_LANE, ROLLOUT_PAIR, ROLLOUT_PAIRW, ROLLOUT_WS2, ROLLOUT_WS4 = 1, 2, 3, 4, 5
+ROLLOUT_SADDR, ROLLOUT_JIT, ROLLOUT_JIT_ONLY = 0x10, 0x20, 0x40
 
 _vp, _i, _i64, _u64, _u32, _f = (ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_uint32,
                                  ctypes.c_float)
@@ -101,6 +104,7 @@ SIGNATURES = {
     # ring planes, ring visits, ring z, T, N, m, n, idx, sym, B, obs, obs dtype, legal mask, policy, value, weight, err, stream
     "mnk_search_gather": [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],
+    "mnk_rollout_form": [_i64, _i, _i, _i, _i, _i, _i, _i],
     "mnk_action_log_words": [_i, _i],
     "mnk_replay_actions": [_vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp],
     "mnk_unpack_records": [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp],
@@ -228,6 +232,14 @@ def reload_config() -> None:
     """The library reads its developer knobs (MNK_ROLLOUT_PAIR / _FORM / _SADDR, MNK_JIT, MNK_EMIT_ENVS / _THREADS) from
     the environment once; call this after changing ``os.environ`` to make it read them again."""
     call("mnk_reload_config")
+
+
+def rollout_form(N: int, m: int, n: int, k: int, T: int, records: bool = True, act_bytes: int = 0,
+                 jit_failed: bool = False) -> int:
+    """Which kernel ``mnk_rollout_random`` runs for such a launch under the current knobs: ROLLOUT_LANE / _PAIR / _PAIRW /
+    _WS2 / _WS4, ORed with ROLLOUT_SADDR / _JIT / _JIT_ONLY; 0 when nothing would be launched, a negative status for
+    arguments the launch rejects.  Needs no GPU (the rules: include/mnk_hip.h, mnk_rollout_form)."""
+    return load().mnk_rollout_form(N, m, n, k, T, int(bool(records)), act_bytes, int(bool(jit_failed)))
 
 
 def jit_api_draw_kind(which: int, logits_dtype=None) -> int:

@@ -183,6 +183,43 @@ def _force_form(param):
     return saved
 
 
+_KNOB = {"one lane per env": "lane", "two lanes per env": "pair", "two lanes per env, words split": "pairw",
+         "two waves per env group": "ws2", "four waves per env group": "ws4"}
+# the forms of the boards with compile-time variants (csrc/mnk_host.h, mnk_rollout_form_ok); every other board: one lane
+BOARD_FORMS = {(3, 3, 3): ("lane", "pair"), (9, 9, 5): ("lane", "pair", "pairw", "ws2", "ws4"),
+               (13, 13, 5): ("lane", "pair", "pairw"), (15, 15, 5): ("lane", "pair", "pairw"),
+               (19, 19, 5): ("lane", "pair", "pairw", "ws2", "ws4")}
+
+
+def assert_rollout_reaches(lib, param, forms, m, n, k, nenv, plies, fmt=0, records=True):
+    """``mnk_rollout_random`` reports (``mnk_rollout_form``) the kernel this small launch takes under ``_force_form(param)``:
+    the forced form where the board has it (``forms``, the caller's table) and it writes log format ``fmt`` -- else the
+    fallback, named here.  Every form computes the same bits, so nothing else would notice a test that ran another one.
+      two lanes forced, 7-bit log (one-lane form only) or a board without two-lane forms: one lane
+      words split forced, the board lacks it (3x3x3): split by directions; directions forced, U8P1 log: split by words
+      waves forced, the board lacks them or there is a log: one lane (those cases run with MNK_ROLLOUT_PAIR=0)
+    One lane on a board with compile-time variants stores records with 32-bit offsets (SADDR) at these batch sizes."""
+    want, builtin = _KNOB[param], "pair" in forms
+    if want in ("pair", "pairw"):
+        if fmt == lib.ACT_BITS7 or not builtin:
+            reach = "lane"
+        elif want == "pairw":
+            reach = "pairw" if "pairw" in forms else "pair"
+        else:
+            reach = "pairw" if fmt == lib.ACT_U8P1 else "pair"
+    elif want in ("ws2", "ws4"):
+        reach = want if want in forms and not fmt else "lane"
+    else:
+        reach = "lane"
+    code = {"lane": lib.ROLLOUT_LANE, "pair": lib.ROLLOUT_PAIR, "pairw": lib.ROLLOUT_PAIRW, "ws2": lib.ROLLOUT_WS2,
+            "ws4": lib.ROLLOUT_WS4}[reach]
+    if reach == "lane" and records and builtin:
+        code |= lib.ROLLOUT_SADDR
+    assert nenv <= 32768 and nenv * plies < 1 << 20  # (what "small launch" means: no batch-size rule, nothing compiled)
+    got = lib.rollout_form(nenv, m, n, k, plies, records, fmt or 0)
+    assert got == code, f"{m}x{n}x{k} N={nenv} T={plies} log {fmt}: labelled '{param}', expected {reach} ({code:#x}), runs {got:#x}"
+
+
 def _reload_knobs():
     """the library reads its environment knobs once; tell it the environment has changed"""
     import __graft_entry__ as entry
@@ -215,8 +252,9 @@ def lane_or_pair(request):
 def lanes_per_env(request):
     """The launcher picks the rollout kernel form by board and batch size; MNK_ROLLOUT_PAIR / MNK_ROLLOUT_FORM (read
     on every call) force one, so small test batches reach every form.  Boards without a compile-time specialisation
-    have the one-lane form only; the waves-per-group forms exist for 9x9x5 and 19x19x5 (others fall through to the
-    launcher's own choice)."""
+    have the one-lane form only and run it under every label; 3x3x3 has no word split and runs the direction split
+    instead; the waves-per-group forms exist for 9x9x5 and 19x19x5, and every other board runs one lane per env under
+    those two labels (``assert_rollout_reaches`` holds the tests to this)."""
     saved = _force_form(request.param)
     yield request.param
     _restore_form(saved)
@@ -272,6 +310,7 @@ def test_rollout_matches_oracle(hip, m, n, k, nenv, chunks, lanes_per_env):
     total = np.zeros(5, dtype=np.int64)
     step0 = 0
     for t in chunks:
+        assert_rollout_reaches(hip.lib, lanes_per_env, BOARD_FORMS.get((m, n, k), ("lane",)), m, n, k, nenv, t)
         rec = roll.run(t)
         planes, meta, stats = random_rollout(ora, seed=5, step0=step0, steps=t, env_id0=12345)
         total += stats

@@ -710,6 +710,7 @@ def test_rollout_in_every_form_the_board_has(hip, board, form, nenv):
             total = np.zeros(5, dtype=np.int64)
             for j, (t, (planes, meta, stats, final, cp, mc)) in enumerate(zip(_chunks(c), want)):
                 where = f"{board} {form} N={nenv} log {fmt} chunk {j}"
+                ge.assert_rollout_reaches(hip.lib, FORMS[form], forms_of(board), m, n, k, nenv, t, fmt)
                 if fmt is None:
                     rec = roll.run(t)
                 else:
@@ -743,7 +744,11 @@ def test_replayed_logs_equal_the_oracles_replay(hip, board):
     for form in [f for f in forms_of(board) if not f.startswith("ws")]:
         saved = ge._force_form(FORMS[form])
         try:
-            ge.test_action_log_replay_rebuilds_the_records(hip, m, n, k, 33, min(m * n + 6, 150), FORMS[form])
+            steps = min(m * n + 6, 150)
+            for fmt in log_formats(hip, m * n, "lane"):  # every format of the board: the form, or its fallback for that log
+                for chunk in (steps - steps % 4, steps):
+                    ge.assert_rollout_reaches(hip.lib, FORMS[form], forms_of(board), m, n, k, 33, chunk, fmt)
+            ge.test_action_log_replay_rebuilds_the_records(hip, m, n, k, 33, steps, FORMS[form])
         finally:
             ge._restore_form(saved)
 
@@ -766,6 +771,8 @@ def test_a_launch_above_32768_envs_takes_the_one_lane_default(hip, board, nenv, 
     through ``mnk_step_random``"""
     for key in ("MNK_ROLLOUT_PAIR", "MNK_ROLLOUT_FORM", "MNK_ROLLOUT_SADDR"):
         assert os.environ.get(key) is None
+    assert hip.lib.rollout_form(nenv, *board, plies, records=True) == hip.lib.ROLLOUT_LANE | hip.lib.ROLLOUT_SADDR
+    assert hip.lib.rollout_form(nenv, *board, warm, records=False) == hip.lib.ROLLOUT_LANE
     ge.test_full_size_rollout_equals_the_oracle_ply_for_ply(hip, *board, nenv, warm, plies)
 
 

@@ -34,4 +34,6 @@ for rep in range(int(os.environ.get("AB_REPS", "2"))):
             env["MNK_HIP_LIB"] = lib
         else:
             env.pop("MNK_HIP_LIB", None)
-        subprocess.run([sys.executable, "-c", CHILD], env=env, check=False)
+        rc = subprocess.run([sys.executable, "-c", CHILD], env=env, check=False).returncode
+        if rc:  # a child that failed may have faulted the card: start nothing after it
+            sys.exit(f"child exited with status {rc}: stopping")
