@@ -2,9 +2,11 @@
 board's symmetries (``SearchReplayBuffer.sample``), the loss -sum(pi * log p) + (v - z)^2 weighted by ``weight`` (0 for
 records of games still running), and validation of the greedy network against ``RandomPolicy`` and ``TacticalPolicy``.
 Root noise is an evaluator wrapper (``RootNoise``): Dirichlet noise mixed into the priors of the first evaluator call of
-every search, the one on the roots.
+every search, the one on the roots.  ``--reuse`` keeps every search tree from ply to ply (the subtree of the move that
+was played starts the next search; the roots' priors, and so the noise, are renewed every ply) and drops the trees after
+each training round, since their statistics are the old weights'.
 
-    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse]
 """
 import argparse
 import os
@@ -71,7 +73,7 @@ def greedy(net):
 
 
 def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates=40, batch=512, lr=2e-3, seed=0,
-          noise=True, log=print):
+          noise=True, reuse=False, log=print):
     """self-play and training rounds; returns the network"""
     entry.build()
     from selfplay.policy import model_evaluator
@@ -86,7 +88,7 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
     if noise:
         evaluator = RootNoise(evaluator, iterations)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
-                        capacity=2 * C, seed=seed)
+                        capacity=2 * C, seed=seed, reuse=reuse)
     plies = C if plies is None else plies
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
@@ -103,6 +105,8 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
             opt.zero_grad(set_to_none=True)
             loss.backward()
             opt.step()
+        if reuse:
+            sp.reset_trees()  # the kept visits and values are the old weights': search afresh with the new ones
         stats = sp.pop_game_stats()
         log(f"round {r}: games {stats['games']} black {stats['black_wins']} white {stats['white_wins']} "
             f"draws {stats['draws']} mean length {stats['mean_length']:.2f} loss {loss.item():.4f}")
@@ -129,9 +133,11 @@ def main():
     ap.add_argument("--rounds", type=int, default=12)
     ap.add_argument("--updates", type=int, default=40)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--reuse", action="store_true", help="keep the subtree of the move played for the next search")
     a = ap.parse_args()
     m, n, k = (int(x) for x in a.board.lower().split("x"))
-    net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed)
+    net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed,
+                reuse=a.reuse)
     for name, res in validate(net, m, n, k).items():
         print(f"vs {name}: win {res['win_rate']:.3f} loss {res['loss_rate']:.3f} draw {res['draw_rate']:.3f} "
               f"score {res['score_rate']:.3f}")

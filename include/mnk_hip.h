@@ -418,13 +418,14 @@ int mnk_sample_search(const void* obs, int obs_dtype, int64_t N, int m, int n, i
  * mulhi32(x, sum n_a); deterministic: the first cell of S.  x = Philox(seed, env_id0 + i, step [+ *step_dev],
  * MNK_STREAM_SAMPLE) -- TacticalPolicy's u32; seed_dev (optional) REPLACES seed, step_dev (optional) is ADDED to step.
  * Outputs (optional, NULL = off): visits int32 [N][C] = the root children's n (0 elsewhere; they sum to I on a row with a
- * legal cell); root_value f32 [N] = -w_root / n_root, the root's mean value for its side to move.  priors: f32 or bf16
- * [N][C], values f32 or bf16 [N] (MNK_LOGITS_*; a bf16 element is read as its exact f32).  Non-finite priors or values
+ * legal cell whose tree mnk_puct_begin set up, to n_root - 1 = the carried visits + the iterations run on a tree that
+ * mnk_puct_rebase carried over whole); root_value f32 [N] = -w_root / n_root, the root's mean value for its side to
+ * move.  priors: f32 or bf16 [N][C], values f32 or bf16 [N] (MNK_LOGITS_*; a bf16 element is read as its exact f32).  Non-finite priors or values
  * give an unspecified result (not checked: a check would cost a synchronisation).  c: finite, >= 0.
  * The tree lives in `workspace` (mnk_puct_workspace_bytes(N, m, n, I) bytes, about (I + 1) * 6 * C per row; its layout is
- * private to the library) from mnk_puct_begin to the step with `last` set.  One act() = mnk_puct_begin, then I steps
- * with last = 0 and one with last = 1 (I + 2 launches, I + 1 evaluations), all stream-ordered, no host synchronisation.
- * Every host check runs before anything is enqueued. */
+ * private to the library) from mnk_puct_begin to the step with `last` set, and on to the next mnk_puct_rebase.  One
+ * act() = mnk_puct_begin, then I steps with last = 0 and one with last = 1 (I + 2 launches, I + 1 evaluations), all
+ * stream-ordered, no host synchronisation.  Every host check runs before anything is enqueued. */
 int64_t mnk_puct_workspace_bytes(int64_t N, int m, int n, int iterations);  /* < 0: MNK_EINVAL / MNK_EGEOM */
 /* the roots into the tree; writes them as evaluation 0 (leaf_obs, leaf_mask) */
 int mnk_puct_begin(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, void* workspace,
@@ -438,6 +439,29 @@ int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iteration
                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
                   float* root_value, void* stream);
 #define MNK_PUCT_ITERS_MAX 2048
+/* mnk_puct_begin for a search that keeps the subtree of the position that was reached (optional; a workspace that only
+ * ever sees mnk_puct_begin behaves as above).  The workspace is that of tree_iterations (tree_iterations + 1 nodes; the
+ * same number goes to mnk_puct_workspace_bytes and to every mnk_puct_step) and must start out as zeros.  An act() that
+ * runs J iterations = mnk_puct_rebase, J steps with last = 0, one with last = 1; the host keeps
+ * 1 <= keep_nodes <= tree_iterations + 1 - J, so the tree cannot fill during the act.
+ * The rule is by position.  R0, R1 = the stored root's planes (R0 = its side to move), O0, O1 = the channels of row i of
+ * obs.  The row CONTINUES the stored tree iff the row's tree is live (it has a node, its root had a legal cell) and
+ * exactly one of
+ *   O0 = R0 and O1 = R1                                                  (the same position: the path is empty),
+ *   O1 = R0 + one cell a1 and O0 = R1                                    (one ply on: the path is [a1]),
+ *   O0 = R0 + one cell a1 and O1 = R1 + one cell a2                      (two plies on: the path is [a1, a2])
+ * holds, and every step of the path leads to a child that exists and is not terminal.  Any other row -- a workspace of
+ * zeros, a game that was reset, an unrelated position -- is FRESH: it gets exactly what mnk_puct_begin writes.
+ * A row that continues keeps the subtree of the node the path ends in: its nodes in their order of creation (the new
+ * root is node 0), the first keep_nodes of them when there are more; a kept node keeps n, w, its move, its terminal kind,
+ * its priors and its children, and a child that was dropped becomes "none yet".  w stays the view of the mover into the
+ * node.  Evaluation 0 is the roots for every row (leaf_obs, leaf_mask as mnk_puct_begin writes them).  The step that
+ * follows backs it up as ever on a fresh row; on a row that continues it only replaces the root's priors on its free
+ * cells -- no n or w changes, no child is touched -- so an evaluator that perturbs the priors of evaluation 0 still acts on
+ * every root.  The visits of such a row sum to n_root - 1 when nothing of the root's children was dropped.
+ * carried (optional) int32 [N][2] = {nodes kept, the new root's n}, {0, 0} on a fresh row. */
+int mnk_puct_rebase(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int tree_iterations, int keep_nodes,
+                    void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried, void* stream);
 
 /* ---- search self-play: the env side of an AlphaZero loop.  A ply = a search that writes every row's root visit counts
  * (PUCTSearchPolicy.act(visits=...), mnk_puct_step), then ONE mnk_search_selfplay_step launch that plays every row's move

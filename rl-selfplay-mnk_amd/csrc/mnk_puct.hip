@@ -1,7 +1,8 @@
 // mnk_puct.hip -- the PUCT search player (gfx950 / MI355X only): AlphaZero-style search guided by a caller's evaluator
 // (normally a policy/value network), batched over rows.  The tree lives in a device workspace between launches; each
 // launch backs up the previous evaluation and selects the next leaf (mnk_puct_step), so an act() is mnk_puct_begin,
-// I + 1 evaluator calls and I + 1 steps with no host synchronisation.  The rule: include/mnk_hip.h.
+// I + 1 evaluator calls and I + 1 steps with no host synchronisation.  mnk_puct_rebase in the place of mnk_puct_begin
+// carries the subtree of the position that was reached into the next search.  The rule: include/mnk_hip.h.
 #include "mnk_host.h"
 #include "mnk_wave_rows.h"
 
@@ -9,13 +10,17 @@
 struct MnkPuctNode {
   uint32_t n;
   float w;
-  uint32_t info;  // the move into the node | term << 16 (0: not terminal; 1: the move won; 2: it filled the board)
+  uint32_t info;  // the move into the node | term << 16 (0: not terminal; 1: the move won; 2: it filled the board) |
+                  // the parent's id << 18 (what k_puct_rebase marks a subtree by; the root's is 0)
 };
+#define MNK_PUCT_TERM(info) (((info) >> 16) & 3u)
+#define MNK_PUCT_PARENT(info) ((info) >> 18)
 static_assert(sizeof(MnkPuctNode) == 12, "node record");
 
 // The workspace of one row, at row * L.row bytes (every part 16-byte aligned, the row 256-byte aligned):
-//   header   u32[4]          nodes created, leaf depth, state (bit 0: a backup is pending; bits 1-2: the leaf's term),
-//                            live (the root has a legal cell)
+//   header   u32[4]          nodes created, leaf depth, state (bit 0: a backup is pending; bits 1-2: the leaf's term;
+//                            bit 3: the pending evaluation is of a root that k_puct_rebase carried over -- it only
+//                            renews the root's priors), live (the root has a legal cell)
 //   root     u32[2][NWg]     the root's guard-column bit planes (plane 0 = the root's side to move), NWg = MnkGeom::NW
 //   leaf     u32[2][NWg]     the pending leaf's planes
 //   path     u16[I + 2]      node ids root .. leaf
@@ -63,17 +68,11 @@ __device__ __forceinline__ float puct_read(const void* p, int dtype, int64_t q) 
 }
 
 // ------------------------------------------------------------------ evaluation 0: the roots
-// One wave per row: the row into bit planes (LDS), the root node, the roots as the first leaves.
-template <int NW, int CN, int CK>
-__global__ void __launch_bounds__(256)
-k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsigned char* ws, void* leaf_obs,
-             int leaf_dtype, uint8_t* leaf_mask) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  const int C = g.C, NWg = g.NW;
-  uint32_t* pos = lds_pos[wave];
+// row i of obs into guard-column bit planes in LDS (pos[2 * NW], the wave's own); returns its stone count
+template <int NW, int CN>
+__device__ __forceinline__ int puct_row_planes(const MnkGeom& g, const void* obs, int obs_dtype, int64_t i, uint32_t* pos,
+                                               int lane) {
+  const int C = g.C;
   for (int q = lane; q < 2 * NW; q += 64) pos[q] = 0u;
   row_wave_sync();
   const size_t eb = (size_t)mnk_obs_bytes(obs_dtype);
@@ -93,8 +92,13 @@ k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsign
   int stones = 0;
 #pragma unroll
   for (int w = 0; w < NW; ++w) stones += __popc(pos[w] | pos[NW + w]);
-  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I);
-  unsigned char* row = ws + i * L.row;
+  return stones;
+}
+
+// pos as the row's root planes and as its pending leaf's
+template <int NW>
+__device__ __forceinline__ void puct_row_root(unsigned char* row, const MnkPuctLayout& L, const uint32_t* pos, int NWg,
+                                              int lane) {
   uint32_t* root = (uint32_t*)(row + L.root);
   uint32_t* leaf = (uint32_t*)(row + L.leaf);
   for (int q = lane; q < 2 * NWg; q += 64) {
@@ -102,16 +106,229 @@ k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsign
     root[q] = v;
     leaf[q] = v;
   }
+}
+
+// a fresh tree: the root node alone, its evaluation pending
+template <int NW>
+__device__ __forceinline__ void puct_row_fresh(unsigned char* row, const MnkPuctLayout& L, const uint32_t* pos, int NWg,
+                                               bool legal, int lane) {
+  puct_row_root<NW>(row, L, pos, NWg, lane);
   if (lane == 0) {
     uint32_t* hdr = (uint32_t*)row;
     hdr[0] = 1u;                     // the root
     hdr[1] = 0u;                     // the leaf is the root
     hdr[2] = 1u;                     // its evaluation is pending, not terminal
-    hdr[3] = stones < C ? 1u : 0u;   // a legal cell
+    hdr[3] = legal ? 1u : 0u;        // a legal cell
     ((uint16_t*)(row + L.path))[0] = 0;
     MnkPuctNode r;
     r.n = 0u; r.w = 0.0f; r.info = 0u;
     *(MnkPuctNode*)(row + L.node) = r;
+  }
+}
+
+// One wave per row: the row into bit planes (LDS), the root node, the roots as the first leaves.
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsigned char* ws, void* leaf_obs,
+             int leaf_dtype, uint8_t* leaf_mask) {
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  const int C = g.C, NWg = g.NW;
+  uint32_t* pos = lds_pos[wave];
+  const int stones = puct_row_planes<NW, CN>(g, obs, obs_dtype, i, pos, lane);
+  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I);
+  puct_row_fresh<NW>(ws + i * L.row, L, pos, NWg, stones < C, lane);
+  row_write_view<NW, CN>(g, pos, 0, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+}
+
+// ------------------------------------------------------------------ evaluation 0 of a search that keeps its tree
+// One wave per row.  The row is matched against the stored root (the rule: include/mnk_hip.h, mnk_puct_rebase); a row
+// that continues it keeps the subtree of the node it reached, compacted in place to ids 0 .. kept - 1 in creation order:
+//   1. marking: a pass over the node records in chunks of 64.  A node is in the subtree when it is the new root or its
+//      parent (info >> 18, always a lower id) is: parents of earlier chunks are read from the LDS table, parents inside
+//      the chunk by pointer jumping over the lanes (at most 6 rounds).  The first `keep` marked nodes get new ids by a
+//      ballot rank; map[old] = new id or NONE, inv[new] = old id, both in LDS.
+//   2. the node records move in chunks of 64 new ids (every load of a chunk before its stores: lane j's destination j may
+//      be a lower lane's source), the prior and child rows eight nodes at a time, a cell per lane.  new <= old, and a
+//      destination slot was itself moved or dropped before, so no second workspace is needed; a cell's column of the
+//      prior and child rows is only ever touched by the one lane that owns the cell.
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_puct_rebase(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int keep, unsigned char* ws, void* leaf_obs,
+              int leaf_dtype, uint8_t* leaf_mask, int32_t* carried) {
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
+  __shared__ uint32_t lds_new[MNK_PUCT_ROWS][2 * NW];  // the stones the row has and the stored root has not
+  __shared__ uint16_t lds_map[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];
+  __shared__ uint16_t lds_inv[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  const int C = g.C, NWg = g.NW;
+  uint32_t* pos = lds_pos[wave];
+  uint32_t* ext = lds_new[wave];
+  uint16_t* map = lds_map[wave];
+  uint16_t* inv = lds_inv[wave];
+  const int stones = puct_row_planes<NW, CN>(g, obs, obs_dtype, i, pos, lane);
+  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I);
+  unsigned char* row = ws + i * L.row;
+  uint32_t* hdr = (uint32_t*)row;
+  const uint32_t* root = (const uint32_t*)(row + L.root);
+  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
+  float* prior = (float*)(row + L.prior);
+  uint16_t* child = (uint16_t*)(row + L.child);
+  // (clamped, as in k_puct_step: whatever the workspace holds, no id leaves the row)
+  const int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
+  const bool live = hdr[3] != 0u;
+
+  // ---- the match (wave-uniform): same[x][y] = the row's plane x is the stored plane y; more[x][y] = it is that plane and
+  // one cell more
+  bool same00 = true, same11 = true, same01 = true, sup00 = true, sup11 = true, sup10 = true;
+  int n00 = 0, n11 = 0, n10 = 0;
+  for (int w = 0; w < NWg; ++w) {
+    const uint32_t r0 = root[w], r1 = root[NWg + w], o0 = pos[w], o1 = pos[NW + w];
+    same00 &= o0 == r0;
+    same11 &= o1 == r1;
+    same01 &= o0 == r1;
+    sup00 &= (r0 & ~o0) == 0u;
+    sup11 &= (r1 & ~o1) == 0u;
+    sup10 &= (r0 & ~o1) == 0u;
+    n00 += __popc(o0 & ~r0);
+    n11 += __popc(o1 & ~r1);
+    n10 += __popc(o1 & ~r0);
+  }
+  int plies = -1;  // the length of the path from the stored root, -1: the row does not continue it
+  if (nodes >= 1 && live) {
+    if (same00 && same11) plies = 0;
+    else if (same01 && sup10 && n10 == 1) plies = 1;
+    else if (sup00 && n00 == 1 && sup11 && n11 == 1) plies = 2;
+  }
+  if (plies > 0) {  // the new stones as planes: [0] the first ply's, [1] the second's
+    for (int q = lane; q < NWg; q += 64) {
+      const uint32_t r0 = root[q], r1 = root[NWg + q], o0 = pos[q], o1 = pos[NW + q];
+      ext[q] = plies == 1 ? (o1 & ~r0) : (o0 & ~r0);
+      ext[NW + q] = plies == 1 ? 0u : (o1 & ~r1);
+    }
+    row_wave_sync();
+  }
+  int v = 0;  // the node the path ends in
+  for (int s = 0; s < plies; ++s) {
+    int a = -1;
+    for (int a0 = 0; a0 < C && a < 0; a0 += 64) {
+      const uint64_t hit = __ballot(a0 + lane < C && row_stone<CN>(g, ext + s * NW, a0 + lane));
+      if (hit) a = a0 + (int)__ffsll((unsigned long long)hit) - 1;
+    }
+    const uint32_t ch = a >= 0 ? child[(int64_t)v * C + a] : 0u;
+    if (ch == 0u || ch == MNK_PUCT_NONE) {
+      plies = -1;
+      break;
+    }
+    v = min((int)ch, nodes - 1);
+    if (MNK_PUCT_TERM(node[v].info)) {
+      plies = -1;
+      break;
+    }
+  }
+
+  if (plies < 0) {  // exactly what k_puct_begin writes
+    puct_row_fresh<NW>(row, L, pos, NWg, stones < C, lane);
+    if (carried && lane == 0) {
+      carried[2 * i] = 0;
+      carried[2 * i + 1] = 0;
+    }
+    row_write_view<NW, CN>(g, pos, 0, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+    return;
+  }
+  const uint32_t root_n = node[v].n;
+
+  // ---- 1. marking
+  int cnt = 0;
+  for (int base = 0; base < nodes; base += 64) {
+    const int id = base + lane;
+    const bool valid = id < nodes;
+    int p = valid && id > 0 ? min((int)MNK_PUCT_PARENT(node[id].info), id - 1) : 0;
+    bool in = id == v;
+    bool known = !valid || id <= v;  // (a lower id is never in the subtree)
+    if (!known && p < base) {
+      in = map[p] != MNK_PUCT_NONE;
+      known = true;
+    }
+    for (int r = 0; r < 6 && __ballot(!known); ++r) {
+      const int from = known ? lane : p - base;
+      const int fknown = __shfl((int)known, from, 64), fin = __shfl((int)in, from, 64), fp = __shfl(p, from, 64);
+      if (!known) {
+        if (fknown) {
+          in = fin != 0;
+          known = true;
+        } else {
+          p = fp;  // (the parent is neither the new root nor decided: the same answer as its own parent, in the chunk too)
+        }
+      }
+    }
+    in = in && known;
+    const uint64_t marked = __ballot(in);
+    const int rank = cnt + (int)__popcll(marked & ((1ull << lane) - 1ull));
+    const bool kept = in && rank < keep;  // (a dropped node's descendants have higher ranks: dropped as well)
+    if (valid) map[id] = kept ? (uint16_t)rank : (uint16_t)MNK_PUCT_NONE;
+    if (kept) inv[rank] = (uint16_t)id;
+    cnt += (int)__popcll(marked);
+    row_wave_sync();
+  }
+  const int kept = min(cnt, keep);  // >= 1: the new root
+
+  // ---- 2. compaction in place
+  for (int base = 0; base < kept; base += 64) {
+    const int j = base + lane;
+    MnkPuctNode k;
+    k.n = 0u; k.w = 0.0f; k.info = 0u;
+    if (j < kept) k = node[inv[j]];
+    row_wave_sync();
+    if (j < kept) {
+      const uint32_t up = map[min((int)MNK_PUCT_PARENT(k.info), nodes - 1)];  // (kept: the node is in the subtree)
+      k.info = j ? ((k.info & 0x3FFFFu) | ((up == MNK_PUCT_NONE ? 0u : up) << 18)) : 0u;  // (the root: as a fresh one's)
+      node[j] = k;
+    }
+  }
+  constexpr int B = 8;
+  for (int j0 = 0; j0 < kept; j0 += B) {
+    for (int a = lane; a < C; a += 64) {
+      float pr[B];
+      uint32_t cl[B];
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        const int64_t o = (int64_t)inv[min(j0 + b, kept - 1)] * C + a;
+        pr[b] = prior[o];
+        cl[b] = child[o];
+      }
+#pragma unroll
+      for (int b = 0; b < B; ++b) {
+        if (j0 + b < kept) {
+          uint32_t ch = cl[b];
+          if (ch != 0u && ch != MNK_PUCT_NONE) {
+            ch = map[min((int)ch, nodes - 1)];
+            if (ch == MNK_PUCT_NONE) ch = 0u;  // a dropped child: none yet
+          }
+          const int64_t o = (int64_t)(j0 + b) * C + a;
+          prior[o] = pr[b];
+          child[o] = (uint16_t)ch;
+        }
+      }
+    }
+  }
+
+  // ---- the new root as evaluation 0
+  puct_row_root<NW>(row, L, pos, NWg, lane);
+  if (lane == 0) {
+    hdr[0] = (uint32_t)kept;
+    hdr[1] = 0u;
+    hdr[2] = 1u | 8u;  // pending, and only the priors of it are used
+    hdr[3] = 1u;       // (a node that is not terminal has a legal cell)
+    ((uint16_t*)(row + L.path))[0] = 0;
+    if (carried) {
+      carried[2 * i] = kept;
+      carried[2 * i + 1] = (int32_t)root_n;
+    }
   }
   row_write_view<NW, CN>(g, pos, 0, i, leaf_obs, leaf_dtype, leaf_mask, lane);
 }
@@ -155,6 +372,7 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
   if (state & 1u) {
     const int lf = min((int)path[depth], nodes - 1);
     const uint32_t term = (state >> 1) & 3u;
+    const bool renew = (state & 8u) != 0u;  // a carried root (k_puct_rebase): its priors again and nothing else
     float v;
     if (term) {
       v = term == 1u ? -1.0f : 0.0f;  // the mover into the leaf won: a loss for its side to move
@@ -164,11 +382,11 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
       uint16_t* cl = child + (int64_t)lf * C;
       for (int a = lane; a < C; a += 64) {
         const bool occ = row_stone<CN>(g, pos, a) || row_stone<CN>(g, pos + NW, a);
-        cl[a] = occ ? (uint16_t)MNK_PUCT_NONE : (uint16_t)0;
+        if (!renew) cl[a] = occ ? (uint16_t)MNK_PUCT_NONE : (uint16_t)0;
         if (!occ) pr[a] = puct_read(priors, priors_dtype, i * C + a);
       }
     }
-    for (int p = lane; p <= depth; p += 64) {  // depth - p odd: the mover into path[p] is the leaf's side to move
+    for (int p = lane; p <= depth && !renew; p += 64) {  // depth - p odd: the mover into path[p] is the leaf's side to move
       MnkPuctNode* k = &node[min((int)path[p], nodes - 1)];
       k->n += 1u;
       k->w = __fadd_rn(k->w, ((depth - p) & 1) ? v : -v);
@@ -262,7 +480,7 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
         const uint32_t term = ply.win ? 1u : (ply.done ? 2u : 0u);
         if (lane == 0) {
           MnkPuctNode k;
-          k.n = 0u; k.w = 0.0f; k.info = (uint32_t)a | (term << 16);
+          k.n = 0u; k.w = 0.0f; k.info = (uint32_t)a | (term << 16) | ((uint32_t)v << 18);
           node[nodes] = k;
           child[(int64_t)v * C + a] = (uint16_t)nodes;
           path[d] = (uint16_t)nodes;
@@ -273,7 +491,7 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
       }
       const int k = min((int)ch, nodes - 1);
       if (lane == 0) path[d] = (uint16_t)k;
-      const uint32_t term = node[k].info >> 16;
+      const uint32_t term = MNK_PUCT_TERM(node[k].info);
       if (term) {  // an existing terminal child: the leaf again
         nstate = 1u | (term << 1);
         break;
@@ -331,6 +549,23 @@ int mnk_puct_begin(const void* obs, int obs_dtype, int64_t N, int m, int n, int 
   MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_begin), grid, block, 0, s, g, obs, obs_dtype, N, iterations,
                                      (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask));
   return mnk_launch_status("puct_begin");
+}
+
+int mnk_puct_rebase(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int tree_iterations, int keep_nodes,
+                    void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried, void* stream) {
+  MnkGeom g;
+  const int rc = mnk_check_geom(m, n, k, &g);
+  if (rc != MNK_OK) return rc;
+  if (!obs || !workspace || !leaf_obs || !leaf_mask || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS || !mnk_obs_dtype_ok(obs_dtype) ||
+      !mnk_obs_dtype_ok(leaf_dtype) || tree_iterations < 1 || tree_iterations > MNK_PUCT_ITERS_MAX || keep_nodes < 1 ||
+      keep_nodes > tree_iterations)  // (at least one iteration's room: keep_nodes <= tree_iterations + 1 - J, J >= 1)
+    return MNK_EINVAL;
+  if (N == 0) return MNK_OK;
+  const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
+  hipStream_t s = (hipStream_t)stream;
+  MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_rebase), grid, block, 0, s, g, obs, obs_dtype, N, tree_iterations,
+                                     keep_nodes, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask, carried));
+  return mnk_launch_status("puct_rebase");
 }
 
 int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iterations, const void* priors, int priors_dtype,

@@ -93,6 +93,9 @@ SIGNATURES = {
     "mnk_puct_workspace_bytes": [_i64, _i, _i, _i],
     # obs, obs dtype, N, m, n, k, iterations, workspace, leaf obs, leaf dtype, leaf mask, stream
     "mnk_puct_begin": [_vp, _i, _i64, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
+    # obs, obs dtype, N, m, n, k, tree iterations, keep nodes, workspace, leaf obs, leaf dtype, leaf mask, carried (int32
+    # [N][2]), stream
+    "mnk_puct_rebase": [_vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
     # workspace, N, m, n, k, iterations, priors, priors dtype, values, values dtype, c, last, temperature, then the
     # sampler block, leaf obs, leaf dtype, leaf mask, actions, visits (int32 [N][C]), root value (f32 [N]), stream
     "mnk_puct_step": [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i, _vp, _i,

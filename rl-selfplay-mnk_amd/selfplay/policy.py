@@ -289,10 +289,21 @@ class PUCTSearchPolicy(Policy):
     The tree and the leaf buffers are allocated on the first ``act`` and reused while (N, m, n, iterations) stay; after
     that an ``act`` allocates nothing of its own but its result and never synchronises with the host, so
     ``torch.cuda.graph`` can capture it (with a capturable evaluator).  As the opponent of ``TorchSelfPlayWrapper`` it is
-    called through pre -> act -> post like any policy."""
+    called through pre -> act -> post like any policy.
+
+    ``reuse=True`` keeps each row's tree between calls (``mnk_puct_rebase`` in the place of ``mnk_puct_begin``): a row whose
+    position is the stored root, or one or two plies on from it through children that exist, starts its search from the
+    subtree of that position -- its visits are then the carried ones plus ``iterations`` -- and every other row (a reset
+    game, an unrelated position, the first call) starts fresh.  The rule is by position, so self-play (the next root is
+    one ply on) and a wrapper's opponent (two plies on) are the same call, and every ``act`` is the same launches.  The
+    workspace holds ``tree_nodes`` nodes per row (default ``2 * iterations + 1``, at most ``PUCT_ITERS_MAX + 1``) of which
+    an ``act`` carries at most ``tree_nodes - iterations`` over, the oldest first.  The first evaluator call of an
+    ``act`` is still on the roots; on a carried root it only renews the root's priors.  The kept statistics come from the
+    evaluator as it was: after its weights change, ``reset_tree()`` drops them -- whether stale visits matter is the
+    caller's decision."""
 
     def __init__(self, k: int, model=None, evaluator=None, iterations: int = 256, c: float = 1.25, temperature: int = 0,
-                 leaf_dtype=torch.float32, seed=None):
+                 leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None):
         if (model is None) == (evaluator is None):
             raise ValueError("PUCTSearchPolicy needs exactly one of model and evaluator")
         self.k = int(k)
@@ -312,13 +323,25 @@ class PUCTSearchPolicy(Policy):
         self.leaf_dtype = leaf_dtype
         self._leaf_code = mnk_hip.obs_dtype_code(leaf_dtype)  # (TypeError for anything but float32 / bfloat16 / uint8)
         self._sampler = _HipSampler(seed)
+        self.reuse = bool(reuse)
+        if self.reuse:
+            self.tree_nodes = 2 * self.iterations + 1 if tree_nodes is None else int(tree_nodes)
+            if not self.iterations + 1 <= self.tree_nodes <= mnk_hip.PUCT_ITERS_MAX + 1:
+                raise ValueError(f"tree_nodes must lie in [iterations + 1, {mnk_hip.PUCT_ITERS_MAX + 1}] = "
+                                 f"[{self.iterations + 1}, {mnk_hip.PUCT_ITERS_MAX + 1}], got {tree_nodes}"
+                                 + (" (the default, 2 * iterations + 1)" if tree_nodes is None else ""))
+        else:
+            if tree_nodes is not None:
+                raise ValueError("tree_nodes is the workspace of a search that keeps its tree: it needs reuse=True")
+            self.tree_nodes = self.iterations + 1
         self._bufs = None  # (key, workspace, leaf_obs, leaf_mask)
 
     def _buffers(self, b, m, n, device):
-        key = (b, m, n, self.iterations, device)
+        key = (b, m, n, self.iterations, self.tree_nodes, device)
         if self._bufs is None or self._bufs[0] != key:
-            size = mnk_hip.puct_workspace_bytes(b, m, n, self.iterations)
-            self._bufs = (key, torch.empty(size, dtype=torch.uint8, device=device),
+            size = mnk_hip.puct_workspace_bytes(b, m, n, self.tree_nodes - 1)
+            # (a tree that is kept starts as zeros: no row continues a workspace of zeros)
+            self._bufs = (key, (torch.zeros if self.reuse else torch.empty)(size, dtype=torch.uint8, device=device),
                           torch.empty((b, 2, m, n), dtype=self.leaf_dtype, device=device),
                           torch.empty((b, m * n), dtype=torch.bool, device=device))
         return self._bufs[1:]
@@ -335,15 +358,27 @@ class PUCTSearchPolicy(Policy):
         code = {torch.float32: mnk_hip.LOGITS_F32, torch.bfloat16: mnk_hip.LOGITS_BF16}
         return priors, code[priors.dtype], values, code[values.dtype]
 
-    def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, visits=None, root_value=None) -> torch.Tensor:
+    def reset_tree(self) -> None:
+        """forget every row's tree (``reuse=True``): the next ``act`` starts every row fresh.  For after the evaluator's
+        weights changed, when the caller wants no statistics of the old ones in the next searches"""
+        if self._bufs is not None and self.reuse:
+            self._bufs[1].zero_()
+
+    def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, visits=None, root_value=None,
+            carried=None) -> torch.Tensor:
         """``visits``: optional int32 ``[B, m*n]`` tensor that receives each row's root visit counts (an AlphaZero policy
-        target; they sum to ``iterations`` on a row with a legal cell); ``root_value``: optional float32 ``[B]`` tensor
-        that receives the root's mean value for the side to move"""
+        target; they sum to ``iterations`` on a row with a legal cell, to the carried visits plus ``iterations`` on a row
+        that kept its tree); ``root_value``: optional float32 ``[B]`` tensor that receives the root's mean value for the
+        side to move; ``carried`` (``reuse=True``): optional int32 ``[B, 2]`` tensor that receives {nodes kept, the visit
+        count of the root that was kept} of each row, {0, 0} where the row started fresh"""
         observation = _canonical_observation(obs)
         b, _, m, n = observation.shape
         dev = observation.device
+        if carried is not None and not self.reuse:
+            raise ValueError("carried is an output of a search that keeps its tree: it needs reuse=True")
         for name, t, shape, dtype in (("visits", visits, (b, m * n), torch.int32),
-                                      ("root_value", root_value, (b,), torch.float32)):
+                                      ("root_value", root_value, (b,), torch.float32),
+                                      ("carried", carried, (b, 2), torch.int32)):
             if t is not None and (t.shape != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
                 raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {shape} tensor on {dev}")
         actions = torch.empty(b, dtype=torch.long, device=dev)
@@ -351,12 +386,18 @@ class PUCTSearchPolicy(Policy):
             ws, leaf_obs, leaf_mask = self._buffers(b, m, n, dev)
             stream = mnk_hip.stream_ptr(dev)
             I, k, code = self.iterations, self.k, self._leaf_code
-            mnk_hip.call("mnk_puct_begin", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k, I,
-                         mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask), stream)
+            cap = self.tree_nodes - 1  # the workspace's layout parameter: node capacity - 1 (= I without reuse)
+            if self.reuse:
+                mnk_hip.call("mnk_puct_rebase", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k, cap,
+                             self.tree_nodes - I, mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask),
+                             mnk_hip.ptr(carried), stream)
+            else:
+                mnk_hip.call("mnk_puct_begin", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k, I,
+                             mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask), stream)
             for it in range(I + 1):
                 priors, pcode, values, vcode = self._evaluate(leaf_obs, leaf_mask, b, m * n)
                 last = it == I
-                mnk_hip.call("mnk_puct_step", mnk_hip.ptr(ws), b, m, n, k, I, mnk_hip.ptr(priors), pcode,
+                mnk_hip.call("mnk_puct_step", mnk_hip.ptr(ws), b, m, n, k, cap, mnk_hip.ptr(priors), pcode,
                              mnk_hip.ptr(values), vcode, self.c, 1 if last else 0, self.temperature,
                              *self._sampler.block(deterministic), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask),
                              mnk_hip.ptr(actions) if last else None, mnk_hip.ptr(visits) if last else None,

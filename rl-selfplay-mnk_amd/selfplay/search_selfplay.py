@@ -10,6 +10,10 @@ buffers exist (after one eager ply) and the evaluator is capturable.
 
 Root noise (Dirichlet) stays an evaluator wrapper: the first evaluator call of every ``act`` is on the roots, so a wrapper
 that counts its calls modulo ``iterations + 1`` knows which call to perturb (examples/alphazero_selfplay.py).
+
+``reuse=True`` keeps every row's search tree from ply to ply (``PUCTSearchPolicy(reuse=True)``): the next root that the step
+kernel writes is what the next search matches its stored tree against, so the subtree of the move that was played -- drawn
+by temperature or not -- is carried over and a game that was reset starts fresh, with no word from the host.
 """
 from typing import Dict
 
@@ -24,7 +28,7 @@ from selfplay.policy import PUCTSearchPolicy
 class SearchSelfPlay:
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  c: float = 1.25, temp_plies: int = None, capacity: int = None, seed=None, leaf_dtype=torch.float32,
-                 device="cuda"):
+                 device="cuda", reuse: bool = False, tree_nodes: int = None):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -39,7 +43,7 @@ class SearchSelfPlay:
             raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
         # (the policy checks model / evaluator, iterations, c and leaf_dtype before anything touches the GPU)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
-                                       temperature=0, leaf_dtype=leaf_dtype, seed=seed)
+                                       temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=reuse, tree_nodes=tree_nodes)
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
@@ -50,6 +54,8 @@ class SearchSelfPlay:
         self.mask = torch.empty((self.num_envs, C), dtype=torch.bool, device=dev)
         self.env.observe_into(obs=self.obs, mask=self.mask)  # a fresh board: black to move, absolute = canonical
         self.visits = torch.zeros((self.num_envs, C), dtype=torch.int32, device=dev)
+        # reuse: {nodes kept, the kept root's visit count} of every row in the last ply's search ({0, 0}: it began afresh)
+        self.carried = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=dev) if reuse else None
         self.stats = torch.zeros((mnk_hip.STATS_REPLICAS, mnk_hip.STATS_STRIDE), dtype=torch.int64, device=dev)
         self._ones = torch.ones(1, dtype=torch.int64, device=dev)
 
@@ -58,7 +64,7 @@ class SearchSelfPlay:
         env, buf = self.env, self.buffer
         stream = mnk_hip.stream_ptr(env._dev)
         for _ in range(int(plies)):
-            self.policy.act({"observation": self.obs, "action_mask": self.mask}, visits=self.visits)
+            self.policy.act({"observation": self.obs, "action_mask": self.mask}, visits=self.visits, carried=self.carried)
             seed, seed_dev, step, step_dev, env_id0, _ = self.sampler.block()
             mnk_hip.call("mnk_search_selfplay_step", mnk_hip.ptr(env._planes), mnk_hip.ptr(env._meta), self.num_envs,
                          self.m, self.n, self.k, mnk_hip.ptr(self.visits), self.temp_plies, seed, seed_dev, step, step_dev,
@@ -67,6 +73,11 @@ class SearchSelfPlay:
                          mnk_hip.ptr(env._err), stream)
             buf.plies.add_(self._ones)
             buf.plies_host += 1
+
+    def reset_trees(self) -> None:
+        """``reuse=True``: forget the kept trees, so that the next ply searches every row afresh -- for after the
+        evaluator's weights changed (``PUCTSearchPolicy.reset_tree``)"""
+        self.policy.reset_tree()
 
     def note_replayed(self, plies: int) -> None:
         """a captured graph of ``play`` has been replayed for ``plies`` plies in all: the host's count of written plies
@@ -83,7 +94,9 @@ class SearchSelfPlay:
                 "mean_length": tot[4] / games if games else 0.0}
 
     def state_dict(self) -> Dict[str, object]:
-        """env, ring, ply counter and Philox key: a restored run continues bit-exactly"""
+        """env, ring, ply counter and Philox key: a restored run continues bit-exactly with ``reuse=False``.  The kept
+        trees of ``reuse=True`` are not part of the state: ``load_state_dict`` drops them, and the plies after it search
+        afresh where the run that was saved had carried visits"""
         return {"env": self.env.state_dict(), "buffer": self.buffer.state_dict(), "seed": self.sampler.seed,
                 "temp_plies": self.temp_plies, "stats": self.stats.cpu()}
 
@@ -93,4 +106,5 @@ class SearchSelfPlay:
         self.sampler.seed = int(state["seed"])
         self.temp_plies = int(state["temp_plies"])
         self.stats.copy_(state["stats"])
+        self.reset_trees()
         self.env.observe_into(obs=self.obs, mask=self.mask, flip_side=(self.env._meta & 1).to(torch.int64))
