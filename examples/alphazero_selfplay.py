@@ -42,11 +42,11 @@ class PolicyValueNet(nn.Module):
 
 
 class RootNoise:
-    """(1 - eps) * P + eps * Dirichlet(alpha) on the legal cells, in the first of every ``iterations + 1`` evaluator
-    calls (the roots of a search); the other calls pass through"""
+    """(1 - eps) * P + eps * Dirichlet(alpha) on the legal cells, in the first of every ``period`` evaluator calls (the
+    roots of a search: ``PUCTSearchPolicy.evaluations_per_act`` = iterations / leaves + 1); the other calls pass through"""
 
-    def __init__(self, inner, iterations, alpha=0.3, eps=0.25):
-        self.inner, self.period, self.alpha, self.eps, self.calls = inner, iterations + 1, alpha, eps, 0
+    def __init__(self, inner, period, alpha=0.3, eps=0.25):
+        self.inner, self.period, self.alpha, self.eps, self.calls = inner, period, alpha, eps, 0
 
     def __call__(self, leaf_obs, leaf_mask):
         priors, values = self.inner(leaf_obs, leaf_mask)
@@ -73,7 +73,7 @@ def greedy(net):
 
 
 def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates=40, batch=512, lr=2e-3, seed=0,
-          noise=True, reuse=False, log=print):
+          noise=True, reuse=False, leaves=1, log=print):
     """self-play and training rounds; returns the network"""
     entry.build()
     from selfplay.policy import model_evaluator
@@ -86,9 +86,10 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     evaluator = model_evaluator(net)
     if noise:
-        evaluator = RootNoise(evaluator, iterations)
+        evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
-                        capacity=2 * C, seed=seed, reuse=reuse)
+                        capacity=2 * C, seed=seed, reuse=reuse, leaves=leaves)
+    assert sp.policy.evaluations_per_act == iterations // leaves + 1
     plies = C if plies is None else plies
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)
@@ -134,10 +135,13 @@ def main():
     ap.add_argument("--updates", type=int, default=40)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--reuse", action="store_true", help="keep the subtree of the move played for the next search")
+    ap.add_argument("--leaves", type=int, default=1,
+                    help="leaves per row and evaluator call (a divisor of --iterations, at most 16): the network sees "
+                         "iterations / leaves + 1 batches of envs * leaves positions per move")
     a = ap.parse_args()
     m, n, k = (int(x) for x in a.board.lower().split("x"))
     net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed,
-                reuse=a.reuse)
+                reuse=a.reuse, leaves=a.leaves)
     for name, res in validate(net, m, n, k).items():
         print(f"vs {name}: win {res['win_rate']:.3f} loss {res['loss_rate']:.3f} draw {res['draw_rate']:.3f} "
               f"score {res['score_rate']:.3f}")

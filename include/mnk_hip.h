@@ -462,6 +462,49 @@ int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iteration
  * carried (optional) int32 [N][2] = {nodes kept, the new root's n}, {0, 0} on a fresh row. */
 int mnk_puct_rebase(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int tree_iterations, int keep_nodes,
                     void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried, void* stream);
+/* The same search with L = leaves in [1, MNK_PUCT_LEAVES_MAX] leaves per row and evaluation, so that the evaluator sees
+ * I / L + 1 batches of N * L rows instead of I + 1 batches of N.  Everything above holds, with a ROUND in the place of an
+ * iteration: a round backs up the L pending SLOTS of the row, then selects L new ones.  An act of I simulations is I / L
+ * rounds (the host requires I % L = 0, of the workspace's `iterations` too); the node capacity stays I + 1 (tree_iterations
+ * + 1 with mnk_puct_rebase_leaves).  leaves = 1 is the search above, bit for bit, in the same workspace.
+ *   batch layout: slot j of row i is batch row i * L + j of leaf_obs [N*L][2][m][n], leaf_mask [N*L][C], priors
+ *     [N*L][C] and values [N*L] -- an evaluator sees a larger batch and nothing else.
+ *   evaluation 0: slot 0 is the root, exactly as mnk_puct_begin / mnk_puct_rebase write it (on a carried root it only
+ *     renews the priors); slots 1 .. L-1 are void.
+ *   void slots: a void slot shows the root's view and the root's legal cells; the evaluator's outputs for it are never
+ *     read and nothing is backed up for it.  A row whose root has no legal cell has only void slots.
+ *   selection: slots 0 .. L-1 of a round select one after the other.  Slot j walks from the root by the score above under
+ *     VIRTUAL VISITS: with vl(x) = the number of earlier non-void slots of this round whose path contains node x, at node
+ *     v the child through cell a counts as
+ *       n'_a = n_a + vl(a),  w'_a = fadd(w_a, -(float)vl(a)),  q = n'_a ? fdiv(w'_a, (float)n'_a) : 0,
+ *       s = fadd(q, fdiv(fmul(fmul(c, P[a]), fsqrt((float)(n_v + vl(v)))), (float)(1 + n'_a))),
+ *     every operation correctly rounded, no contraction, ties to the lowest cell (vl = 0: the score above, bit for bit).
+ *     A child that does not exist yet is created and is the slot's leaf.  An existing terminal child is the leaf again,
+ *     as often as the round's slots reach it (one created earlier in the same round too: it needs no evaluation).  A walk
+ *     that reaches a node that is not terminal and was created earlier in this round makes the slot void: that node has no
+ *     evaluation yet.  A void slot changes nothing, so every later slot of the round is void as well.  A full tree makes
+ *     a slot void (it cannot happen within the budgets the host allows).
+ *   backup: the round's non-void slots are backed up in slot order, each exactly as above (n += 1 and one correctly
+ *     rounded f32 add per node of its path; slot 0's adds to a node come before slot 1's).  Virtual visits never touch n
+ *     or w: they exist only while a round selects.
+ *   visits: on a fresh row they sum to I minus the row's void slots after evaluation 0, on a carried row to the carried
+ *     visits plus that.  The move, root_value, both temperatures, the key words and `deterministic` are as above.
+ * One act() = mnk_puct_begin_leaves (or mnk_puct_rebase_leaves with keep_nodes <= tree_iterations + 1 - leaves), I / L
+ * steps with last = 0 and one with last = 1; every call of an act gets the same `leaves`.  mnk_puct_workspace_bytes_leaves
+ * (.., 1) = mnk_puct_workspace_bytes(..): the slots' own state (L paths, L leaves, L x {depth, state}) lies behind the
+ * tree.  Every host check runs before anything is enqueued. */
+#define MNK_PUCT_LEAVES_MAX 16
+int64_t mnk_puct_workspace_bytes_leaves(int64_t N, int m, int n, int iterations, int leaves);
+int mnk_puct_begin_leaves(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, int leaves,
+                          void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, void* stream);
+int mnk_puct_rebase_leaves(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int tree_iterations,
+                           int keep_nodes, int leaves, void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask,
+                           int32_t* carried, void* stream);
+int mnk_puct_step_leaves(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                         int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                         uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                         int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                         int32_t* visits, float* root_value, void* stream);
 
 /* ---- search self-play: the env side of an AlphaZero loop.  A ply = a search that writes every row's root visit counts
  * (PUCTSearchPolicy.act(visits=...), mnk_puct_step), then ONE mnk_search_selfplay_step launch that plays every row's move

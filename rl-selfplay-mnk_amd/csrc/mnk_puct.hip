@@ -2,7 +2,9 @@
 // (normally a policy/value network), batched over rows.  The tree lives in a device workspace between launches; each
 // launch backs up the previous evaluation and selects the next leaf (mnk_puct_step), so an act() is mnk_puct_begin,
 // I + 1 evaluator calls and I + 1 steps with no host synchronisation.  mnk_puct_rebase in the place of mnk_puct_begin
-// carries the subtree of the position that was reached into the next search.  The rule: include/mnk_hip.h.
+// carries the subtree of the position that was reached into the next search.  The *_leaves entry points run the same
+// search with L leaves per row and evaluation (a round = L backups, then L selections under virtual visits), so the
+// evaluator sees I / L + 1 batches of N * L rows.  The rule: include/mnk_hip.h.
 #include "mnk_host.h"
 #include "mnk_wave_rows.h"
 
@@ -28,12 +30,17 @@ static_assert(sizeof(MnkPuctNode) == 12, "node record");
 //   prior    f32[I + 1][C]   the evaluator's prior of each legal cell of node v, at v * C (slot = node id)
 //   child    u16[I + 1][C]   the child of node v through each cell: 0 = none yet (node 0, the root, is never a child),
 //                            0xFFFF = an occupied cell
+// and, with Lv > 1 leaves per evaluation, behind all of that the state of slots 1 .. Lv - 1 (slot 0's is the header's
+// depth and state, `leaf` and `path`):
+//   xhdr     u32[Lv - 1][2]       leaf depth, state
+//   xleaf    u32[Lv - 1][2][NWg]  the slot's pending leaf's planes
+//   xpath    u16[Lv - 1][..]      its path, `pstride` bytes apart
 // About (I + 1) * 6 * C bytes per row.  The host (mnk_puct_workspace_bytes) and the kernels share this one function.
 struct MnkPuctLayout {
-  int64_t root, leaf, path, node, prior, child, row;
+  int64_t root, leaf, path, node, prior, child, xhdr, xleaf, xpath, pstride, row;
 };
 __host__ __device__ inline int64_t mnk_puct_al(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-__host__ __device__ inline MnkPuctLayout mnk_puct_layout(int NWg, int C, int I) {
+__host__ __device__ inline MnkPuctLayout mnk_puct_layout(int NWg, int C, int I, int Lv = 1) {
   MnkPuctLayout L;
   L.root = 16;
   L.leaf = L.root + 8 * NWg;
@@ -42,6 +49,11 @@ __host__ __device__ inline MnkPuctLayout mnk_puct_layout(int NWg, int C, int I) 
   L.prior = mnk_puct_al(L.node + 12 * (int64_t)(I + 1), 16);
   L.child = mnk_puct_al(L.prior + 4 * (int64_t)(I + 1) * C, 16);
   L.row = mnk_puct_al(L.child + 2 * (int64_t)(I + 1) * C, 256);
+  L.pstride = mnk_puct_al(2 * (int64_t)(I + 2), 16);
+  L.xhdr = mnk_puct_al(L.child + 2 * (int64_t)(I + 1) * C, 16);
+  L.xleaf = mnk_puct_al(L.xhdr + 8 * (int64_t)(Lv - 1), 16);
+  L.xpath = mnk_puct_al(L.xleaf + 8 * (int64_t)NWg * (Lv - 1), 16);
+  if (Lv > 1) L.row = mnk_puct_al(L.xpath + L.pstride * (Lv - 1), 256);  // (Lv = 1: nothing behind `child`)
   return L;
 }
 
@@ -126,7 +138,34 @@ __device__ __forceinline__ void puct_row_fresh(unsigned char* row, const MnkPuct
   }
 }
 
-// One wave per row: the row into bit planes (LDS), the root node, the roots as the first leaves.
+// slots 1 .. leaves - 1 of evaluation 0 are void: nothing pending, the root's view (pos) as batch rows i * leaves + j
+template <int NW, int CN>
+__device__ __forceinline__ void puct_row_void_slots(const MnkGeom& g, unsigned char* row, const MnkPuctLayout& L,
+                                                    const uint32_t* pos, int64_t i, int leaves, void* leaf_obs,
+                                                    int leaf_dtype, uint8_t* leaf_mask, int lane) {
+  for (int j = 1; j < leaves; ++j) {
+    if (lane == 0) {
+      uint32_t* ds = (uint32_t*)(row + L.xhdr) + 2 * (j - 1);
+      ds[0] = 0u;
+      ds[1] = 0u;
+    }
+    row_write_view<NW, CN>(g, pos, 0, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
+  }
+}
+
+// One wave per row: the row into bit planes (LDS, pos), the root node, the roots as the first leaves (slot 0 of `leaves`).
+template <int NW, int CN>
+__device__ __forceinline__ void puct_begin_row(const MnkGeom& g, const void* obs, int obs_dtype, int64_t i, int I, int leaves,
+                                               unsigned char* ws, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask,
+                                               uint32_t* pos, int lane) {
+  const int C = g.C, NWg = g.NW;
+  const int stones = puct_row_planes<NW, CN>(g, obs, obs_dtype, i, pos, lane);
+  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, leaves);
+  puct_row_fresh<NW>(ws + i * L.row, L, pos, NWg, stones < C, lane);
+  row_write_view<NW, CN>(g, pos, 0, i * leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
+  puct_row_void_slots<NW, CN>(g, ws + i * L.row, L, pos, i, leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
+}
+
 template <int NW, int CN, int CK>
 __global__ void __launch_bounds__(256)
 k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsigned char* ws, void* leaf_obs,
@@ -135,12 +174,18 @@ k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsign
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
   if (i >= N) return;
-  const int C = g.C, NWg = g.NW;
-  uint32_t* pos = lds_pos[wave];
-  const int stones = puct_row_planes<NW, CN>(g, obs, obs_dtype, i, pos, lane);
-  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I);
-  puct_row_fresh<NW>(ws + i * L.row, L, pos, NWg, stones < C, lane);
-  row_write_view<NW, CN>(g, pos, 0, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+  puct_begin_row<NW, CN>(g, obs, obs_dtype, i, I, 1, ws, leaf_obs, leaf_dtype, leaf_mask, lds_pos[wave], lane);
+}
+
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_puct_begin_leaves(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int leaves, unsigned char* ws,
+                    void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask) {
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  puct_begin_row<NW, CN>(g, obs, obs_dtype, i, I, leaves, ws, leaf_obs, leaf_dtype, leaf_mask, lds_pos[wave], lane);
 }
 
 // ------------------------------------------------------------------ evaluation 0 of a search that keeps its tree
@@ -154,24 +199,14 @@ k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsign
 //      be a lower lane's source), the prior and child rows eight nodes at a time, a cell per lane.  new <= old, and a
 //      destination slot was itself moved or dropped before, so no second workspace is needed; a cell's column of the
 //      prior and child rows is only ever touched by the one lane that owns the cell.
-template <int NW, int CN, int CK>
-__global__ void __launch_bounds__(256)
-k_puct_rebase(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int keep, unsigned char* ws, void* leaf_obs,
-              int leaf_dtype, uint8_t* leaf_mask, int32_t* carried) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  __shared__ uint32_t lds_new[MNK_PUCT_ROWS][2 * NW];  // the stones the row has and the stored root has not
-  __shared__ uint16_t lds_map[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];
-  __shared__ uint16_t lds_inv[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
+template <int NW, int CN>
+__device__ __forceinline__ void puct_rebase_row(const MnkGeom& g, const void* obs, int obs_dtype, int64_t i, int I, int keep,
+                                                int leaves, unsigned char* ws, void* leaf_obs, int leaf_dtype,
+                                                uint8_t* leaf_mask, int32_t* carried, uint32_t* pos, uint32_t* ext,
+                                                uint16_t* map, uint16_t* inv, int lane) {
   const int C = g.C, NWg = g.NW;
-  uint32_t* pos = lds_pos[wave];
-  uint32_t* ext = lds_new[wave];
-  uint16_t* map = lds_map[wave];
-  uint16_t* inv = lds_inv[wave];
   const int stones = puct_row_planes<NW, CN>(g, obs, obs_dtype, i, pos, lane);
-  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I);
+  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, leaves);
   unsigned char* row = ws + i * L.row;
   uint32_t* hdr = (uint32_t*)row;
   const uint32_t* root = (const uint32_t*)(row + L.root);
@@ -237,7 +272,8 @@ k_puct_rebase(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int k
       carried[2 * i] = 0;
       carried[2 * i + 1] = 0;
     }
-    row_write_view<NW, CN>(g, pos, 0, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+    row_write_view<NW, CN>(g, pos, 0, i * leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
+    puct_row_void_slots<NW, CN>(g, row, L, pos, i, leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
     return;
   }
   const uint32_t root_n = node[v].n;
@@ -330,10 +366,213 @@ k_puct_rebase(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int k
       carried[2 * i + 1] = (int32_t)root_n;
     }
   }
-  row_write_view<NW, CN>(g, pos, 0, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+  row_write_view<NW, CN>(g, pos, 0, i * leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
+  puct_row_void_slots<NW, CN>(g, row, L, pos, i, leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
+}
+
+#define MNK_PUCT_REBASE_LDS                                                                                      \
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];                                                            \
+  __shared__ uint32_t lds_new[MNK_PUCT_ROWS][2 * NW]; /* the stones the row has and the stored root has not */ \
+  __shared__ uint16_t lds_map[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];                                            \
+  __shared__ uint16_t lds_inv[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];
+
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_puct_rebase(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int keep, unsigned char* ws, void* leaf_obs,
+              int leaf_dtype, uint8_t* leaf_mask, int32_t* carried) {
+  MNK_PUCT_REBASE_LDS
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  puct_rebase_row<NW, CN>(g, obs, obs_dtype, i, I, keep, 1, ws, leaf_obs, leaf_dtype, leaf_mask, carried, lds_pos[wave],
+                          lds_new[wave], lds_map[wave], lds_inv[wave], lane);
+}
+
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_puct_rebase_leaves(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int keep, int leaves, unsigned char* ws,
+                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried) {
+  MNK_PUCT_REBASE_LDS
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  puct_rebase_row<NW, CN>(g, obs, obs_dtype, i, I, keep, leaves, ws, leaf_obs, leaf_dtype, leaf_mask, carried,
+                          lds_pos[wave], lds_new[wave], lds_map[wave], lds_inv[wave], lane);
 }
 
 // ------------------------------------------------------------------ one backup, then one selection (or the move)
+// The backup of one pending evaluation (state bit 0 set): batch row b of priors / values, the leaf's planes in pos (LDS).
+template <int NW, int CN>
+__device__ __forceinline__ void puct_backup(const MnkGeom& g, const uint32_t* pos, const uint16_t* path, MnkPuctNode* node,
+                                            float* prior, uint16_t* child, int nodes, int depth, uint32_t state,
+                                            const void* priors, int priors_dtype, const void* values, int values_dtype,
+                                            int64_t b, int lane) {
+  const int C = g.C;
+  const int lf = min((int)path[depth], nodes - 1);
+  const uint32_t term = (state >> 1) & 3u;
+  const bool renew = (state & 8u) != 0u;  // a carried root (k_puct_rebase): its priors again and nothing else
+  float v;
+  if (term) {
+    v = term == 1u ? -1.0f : 0.0f;  // the mover into the leaf won: a loss for its side to move
+  } else {
+    v = puct_read(values, values_dtype, b);
+    float* pr = prior + (int64_t)lf * C;
+    uint16_t* cl = child + (int64_t)lf * C;
+    for (int a = lane; a < C; a += 64) {
+      const bool occ = row_stone<CN>(g, pos, a) || row_stone<CN>(g, pos + NW, a);
+      if (!renew) cl[a] = occ ? (uint16_t)MNK_PUCT_NONE : (uint16_t)0;
+      if (!occ) pr[a] = puct_read(priors, priors_dtype, b * C + a);
+    }
+  }
+  for (int p = lane; p <= depth && !renew; p += 64) {  // depth - p odd: the mover into path[p] is the leaf's side to move
+    MnkPuctNode* k = &node[min((int)path[p], nodes - 1)];
+    k->n += 1u;
+    k->w = __fadd_rn(k->w, ((depth - p) & 1) ? v : -v);
+  }
+  row_wave_sync();
+}
+
+// The move, the visits, the root value of row i, after its last backup.
+__device__ __forceinline__ void puct_move(int C, const MnkPuctNode* node, const uint16_t* child, int nodes, bool live,
+                                          int temperature, uint64_t seed, const uint64_t* seed_dev, uint64_t step,
+                                          const uint64_t* step_dev, int64_t env_id0, int deterministic, int64_t i,
+                                          int64_t* actions, int32_t* visits, float* root_value, int lane) {
+  if (step_dev) step += *step_dev;
+  if (seed_dev) seed = *seed_dev;
+  const uint32_t x = deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(env_id0 + i), step, MNK_STREAM_SAMPLE);
+  uint32_t maxn = 0u, tot = 0u;
+  for (int a = lane; a < C; a += 64) {
+    const uint32_t ch = live ? child[a] : MNK_PUCT_NONE;
+    const uint32_t na = (ch != 0u && ch != MNK_PUCT_NONE) ? node[min((int)ch, nodes - 1)].n : 0u;
+    if (visits) visits[i * C + a] = (int32_t)na;
+    maxn = max(maxn, na);
+    tot += na;
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
+    tot += (uint32_t)__shfl_xor((int)tot, off, 64);
+  }
+  int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells
+  if (maxn)
+    mnk_pick_by_visits(C, x, temperature == 1 && !deterministic, maxn, tot, lane, [&](int a) {
+      const uint32_t ch = a < C ? child[a] : 0u;
+      return (ch != 0u && ch != MNK_PUCT_NONE) ? node[min((int)ch, nodes - 1)].n : 0u;
+    }, move);
+  if (lane == 0) {
+    actions[i] = move;
+    if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
+  }
+}
+
+template <int NW>
+__device__ __forceinline__ void puct_env_root(MnkEnv<NW>& e, const uint32_t* root, int NWg) {
+  int stones = 0;
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    e.p[0][w] = w < NWg ? root[w] : 0u;
+    e.p[1][w] = w < NWg ? root[NWg + w] : 0u;
+    stones += __popc(e.p[0][w] | e.p[1][w]);
+  }
+  e.meta = (uint32_t)stones << 1;
+}
+
+// One walk from the root (e = the root's position on entry, the leaf's on return; wave-uniform): the new pending state
+// (0: no leaf), the leaf's depth in d, its path in path[1 .. d].  A new leaf becomes node `nodes`.
+// VL: the walk of a slot under the virtual visits of the round's earlier slots.  vl(x) is counted from their stored paths
+// (the tree has one path to a node: slot l's path holds x, a node at depth t, iff its entry t is x): `share` = the
+// earlier slots whose path runs through the walk's node v, slot l's path and depth are lane l's epath / edepth, and a
+// child's vl = how many slots of `share` go on to it.  nodes0 = the node count when the round began: a node of a higher
+// id that is not terminal has no evaluation yet, and reaching it ends the walk without a leaf.
+template <int NW, int CN, int CK, bool VL>
+__device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, int I, float c, MnkPuctNode* node,
+                                              const float* prior, uint16_t* child, uint16_t* path, int& nodes, int& d,
+                                              int lane, int nodes0 = 0, uint32_t share = 0u,
+                                              const uint16_t* epath = nullptr, int edepth = 0) {
+  const int C = g.C;
+  int v = 0;
+  for (;;) {
+    uint32_t nxt = 0u;  // VL: where lane l's slot goes from v (0: not through v, or its leaf is v)
+    uint32_t nv = node[v].n;
+    if (VL) {
+      if (lane < MNK_PUCT_LEAVES_MAX && ((share >> lane) & 1u) && edepth > d) nxt = epath[d + 1];
+      nv += (uint32_t)__popc(share);
+    }
+    // the slots' next nodes as wave-uniform values, read here where every lane is active (the per-cell loop below is not)
+    uint32_t nx[MNK_PUCT_LEAVES_MAX];
+    if (VL) {
+#pragma unroll
+      for (int l = 0; l < MNK_PUCT_LEAVES_MAX; ++l) nx[l] = (uint32_t)__builtin_amdgcn_readlane((int)nxt, l);
+    }
+    const float sq = puct_sqrt_rn(nv);
+    const float* pr = prior + (int64_t)v * C;
+    const uint16_t* cl = child + (int64_t)v * C;
+    float best = 0.0f;
+    int ba = 0x7fffffff;
+    for (int a = lane; a < C; a += 64) {
+      const uint32_t ch = cl[a];
+      if (ch == MNK_PUCT_NONE) continue;
+      uint32_t na = 0u;
+      float wa = 0.0f;
+      if (ch) {
+        const int kk = min((int)ch, nodes - 1);
+        const MnkPuctNode k = node[kk];
+        na = k.n;
+        wa = k.w;
+        if (VL && share) {
+          uint32_t vl = 0u;  // (nx is 0, never a child's id, for a slot that is not in `share`)
+#pragma unroll
+          for (int l = 0; l < MNK_PUCT_LEAVES_MAX; ++l) vl += nx[l] == (uint32_t)kk;
+          na += vl;
+          wa = __fadd_rn(wa, -(float)vl);
+        }
+      }
+      const float q = na ? __fdiv_rn(wa, (float)na) : 0.0f;
+      const float s = __fadd_rn(q, __fdiv_rn(__fmul_rn(__fmul_rn(c, pr[a]), sq), (float)(1u + na)));
+      if (ba == 0x7fffffff || s > best) {  // (a rises: ">" keeps the lowest cell of a tie)
+        best = s;
+        ba = a;
+      }
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+      const float ob = __shfl_xor(best, off, 64);
+      const int oa = __shfl_xor(ba, off, 64);
+      if (oa != 0x7fffffff && (ba == 0x7fffffff || ob > best || (ob == best && oa < ba))) {
+        best = ob;
+        ba = oa;
+      }
+    }
+    const int a = __builtin_amdgcn_readfirstlane(ba);
+    if (a == 0x7fffffff) return 0u;  // (an evaluated non-terminal node always has a legal cell)
+    const uint32_t ch = cl[a];
+    const MnkPly ply = env_play<NW, CN, CK, true>(g, e, a, false);
+    ++d;
+    if (ch == 0u) {  // a new node: the leaf
+      const uint32_t term = ply.win ? 1u : (ply.done ? 2u : 0u);
+      if (lane == 0) {
+        MnkPuctNode k;
+        k.n = 0u; k.w = 0.0f; k.info = (uint32_t)a | (term << 16) | ((uint32_t)v << 18);
+        node[nodes] = k;
+        child[(int64_t)v * C + a] = (uint16_t)nodes;
+        path[d] = (uint16_t)nodes;
+      }
+      ++nodes;
+      return 1u | (term << 1);
+    }
+    const int k = min((int)ch, nodes - 1);
+    if (lane == 0) path[d] = (uint16_t)k;
+    const uint32_t term = MNK_PUCT_TERM(node[k].info);
+    if (term) return 1u | (term << 1);  // an existing terminal child: the leaf again
+    if (VL) {
+      if (k >= nodes0) return 0u;  // created in this round: not evaluated yet
+      share = (uint32_t)__ballot(nxt == (uint32_t)k);
+    }
+    v = k;
+    if (d >= I) return 0u;  // (cannot happen: a path holds at most one new node per iteration)
+  }
+}
+
 // One wave per row, MNK_PUCT_ROWS rows per workgroup.  Selection is wave-uniform: the position in registers, the scores
 // of a node's C cells spread over the lanes and reduced to the maximum, ties to the lowest cell.
 template <int NW, int CN, int CK>
@@ -369,59 +608,13 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
   row_wave_sync();
 
   // ---- backup of the pending evaluation
-  if (state & 1u) {
-    const int lf = min((int)path[depth], nodes - 1);
-    const uint32_t term = (state >> 1) & 3u;
-    const bool renew = (state & 8u) != 0u;  // a carried root (k_puct_rebase): its priors again and nothing else
-    float v;
-    if (term) {
-      v = term == 1u ? -1.0f : 0.0f;  // the mover into the leaf won: a loss for its side to move
-    } else {
-      v = puct_read(values, values_dtype, i);
-      float* pr = prior + (int64_t)lf * C;
-      uint16_t* cl = child + (int64_t)lf * C;
-      for (int a = lane; a < C; a += 64) {
-        const bool occ = row_stone<CN>(g, pos, a) || row_stone<CN>(g, pos + NW, a);
-        if (!renew) cl[a] = occ ? (uint16_t)MNK_PUCT_NONE : (uint16_t)0;
-        if (!occ) pr[a] = puct_read(priors, priors_dtype, i * C + a);
-      }
-    }
-    for (int p = lane; p <= depth && !renew; p += 64) {  // depth - p odd: the mover into path[p] is the leaf's side to move
-      MnkPuctNode* k = &node[min((int)path[p], nodes - 1)];
-      k->n += 1u;
-      k->w = __fadd_rn(k->w, ((depth - p) & 1) ? v : -v);
-    }
-    row_wave_sync();
-  }
+  if (state & 1u)
+    puct_backup<NW, CN>(g, pos, path, node, prior, child, nodes, depth, state, priors, priors_dtype, values, values_dtype,
+                        i, lane);
 
   if (last) {
-    // ---- the move, the visits, the root value
-    if (step_dev) step += *step_dev;
-    if (seed_dev) seed = *seed_dev;
-    const uint32_t x = deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(env_id0 + i), step, MNK_STREAM_SAMPLE);
-    uint32_t maxn = 0u, tot = 0u;
-    for (int a = lane; a < C; a += 64) {
-      const uint32_t ch = live ? child[a] : MNK_PUCT_NONE;
-      const uint32_t na = (ch != 0u && ch != MNK_PUCT_NONE) ? node[min((int)ch, nodes - 1)].n : 0u;
-      if (visits) visits[i * C + a] = (int32_t)na;
-      maxn = max(maxn, na);
-      tot += na;
-    }
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-      maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
-      tot += (uint32_t)__shfl_xor((int)tot, off, 64);
-    }
-    int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells
-    if (maxn)
-      mnk_pick_by_visits(C, x, temperature == 1 && !deterministic, maxn, tot, lane, [&](int a) {
-        const uint32_t ch = a < C ? child[a] : 0u;
-        return (ch != 0u && ch != MNK_PUCT_NONE) ? node[min((int)ch, nodes - 1)].n : 0u;
-      }, move);
-    if (lane == 0) {
-      actions[i] = move;
-      if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
-    }
+    puct_move(C, node, child, nodes, live, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, i, actions,
+              visits, root_value, lane);
     return;
   }
 
@@ -430,75 +623,8 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
   uint32_t nstate = 0u;  // nothing pending: a row without a legal cell (or a full tree) shows its root again
   if (live && nodes <= I) {
     MnkEnv<NW> e;
-    int stones = 0;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      e.p[0][w] = w < NWg ? root[w] : 0u;
-      e.p[1][w] = w < NWg ? root[NWg + w] : 0u;
-      stones += __popc(e.p[0][w] | e.p[1][w]);
-    }
-    e.meta = (uint32_t)stones << 1;
-    int v = 0;
-    for (;;) {
-      const float sq = puct_sqrt_rn(node[v].n);
-      const float* pr = prior + (int64_t)v * C;
-      const uint16_t* cl = child + (int64_t)v * C;
-      float best = 0.0f;
-      int ba = 0x7fffffff;
-      for (int a = lane; a < C; a += 64) {
-        const uint32_t ch = cl[a];
-        if (ch == MNK_PUCT_NONE) continue;
-        uint32_t na = 0u;
-        float wa = 0.0f;
-        if (ch) {
-          const MnkPuctNode k = node[min((int)ch, nodes - 1)];
-          na = k.n;
-          wa = k.w;
-        }
-        const float q = na ? __fdiv_rn(wa, (float)na) : 0.0f;
-        const float s = __fadd_rn(q, __fdiv_rn(__fmul_rn(__fmul_rn(c, pr[a]), sq), (float)(1u + na)));
-        if (ba == 0x7fffffff || s > best) {  // (a rises: ">" keeps the lowest cell of a tie)
-          best = s;
-          ba = a;
-        }
-      }
-#pragma unroll
-      for (int off = 32; off; off >>= 1) {
-        const float ob = __shfl_xor(best, off, 64);
-        const int oa = __shfl_xor(ba, off, 64);
-        if (oa != 0x7fffffff && (ba == 0x7fffffff || ob > best || (ob == best && oa < ba))) {
-          best = ob;
-          ba = oa;
-        }
-      }
-      const int a = __builtin_amdgcn_readfirstlane(ba);
-      if (a == 0x7fffffff) break;  // (an evaluated non-terminal node always has a legal cell)
-      const uint32_t ch = cl[a];
-      const MnkPly ply = env_play<NW, CN, CK, true>(g, e, a, false);
-      ++d;
-      if (ch == 0u) {  // a new node: the leaf
-        const uint32_t term = ply.win ? 1u : (ply.done ? 2u : 0u);
-        if (lane == 0) {
-          MnkPuctNode k;
-          k.n = 0u; k.w = 0.0f; k.info = (uint32_t)a | (term << 16) | ((uint32_t)v << 18);
-          node[nodes] = k;
-          child[(int64_t)v * C + a] = (uint16_t)nodes;
-          path[d] = (uint16_t)nodes;
-        }
-        ++nodes;
-        nstate = 1u | (term << 1);
-        break;
-      }
-      const int k = min((int)ch, nodes - 1);
-      if (lane == 0) path[d] = (uint16_t)k;
-      const uint32_t term = MNK_PUCT_TERM(node[k].info);
-      if (term) {  // an existing terminal child: the leaf again
-        nstate = 1u | (term << 1);
-        break;
-      }
-      v = k;
-      if (d >= I) break;  // (cannot happen: a path holds at most one new node per iteration)
-    }
+    puct_env_root<NW>(e, root, NWg);
+    nstate = puct_walk<NW, CN, CK, false>(g, e, I, c, node, prior, child, path, nodes, d, lane);
     if (nstate == 0u) d = 0;
     if (lane == 0) {
 #pragma unroll
@@ -524,55 +650,171 @@ k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, 
   row_write_view<NW, CN>(g, pos, d & 1, i, leaf_obs, leaf_dtype, leaf_mask, lane);
 }
 
-// ------------------------------------------------------------------ the entry points
-extern "C" {
+// ------------------------------------------------------------------ a round: `leaves` backups, then `leaves` selections
+// One wave per row as above.  Slot j of row i is batch row i * leaves + j.  The backups run in slot order with a wave
+// sync between them (paths share nodes), each lane-parallel over its path.  Then the slots select one after the other,
+// each under the virtual visits of the slots before it (puct_walk<VL>), and every slot's leaf is written out as soon as
+// it is known: planes through the wave's LDS stage, the one part of a slot that every lane reads.  The paths stay in the
+// workspace (at the maxima 4 rows x 16 slots x 2 050 u16 exceed the CU's LDS); a walk reads one entry per earlier slot and
+// node.  A slot without a leaf is void (state 0, the root's view), and so is every slot after it: nothing has changed
+// that its walk could see.
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_puct_step_leaves(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, const void* priors, int priors_dtype,
+                   const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
+                   const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
+                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
+                   float* root_value) {
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  const int C = g.C, NWg = g.NW;
+  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, leaves);
+  unsigned char* row = ws + i * L.row;
+  uint32_t* hdr = (uint32_t*)row;
+  const uint32_t* root = (const uint32_t*)(row + L.root);
+  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
+  float* prior = (float*)(row + L.prior);
+  uint16_t* child = (uint16_t*)(row + L.child);
+  uint32_t* pos = lds_pos[wave];
+  // slot j's {depth, state}, leaf planes and path (slot 0: the header's, `leaf`, `path`)
+  auto slot_ds = [&](int j) { return j ? (uint32_t*)(row + L.xhdr) + 2 * (j - 1) : hdr + 1; };
+  auto slot_leaf = [&](int j) { return (uint32_t*)(row + (j ? L.xleaf + 8 * (int64_t)NWg * (j - 1) : L.leaf)); };
+  auto slot_path = [&](int j) { return (uint16_t*)(row + (j ? L.xpath + L.pstride * (j - 1) : L.path)); };
+  // (clamped: a workspace that mnk_puct_begin_leaves did not set up cannot send a store outside the row)
+  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
+  const bool live = hdr[3] != 0u;
 
-int64_t mnk_puct_workspace_bytes(int64_t N, int m, int n, int iterations) {
+  // ---- the backups of the pending evaluations, in slot order
+  for (int j = 0; j < leaves; ++j) {
+    const uint32_t* ds = slot_ds(j);
+    const int depth = (int)min(ds[0], (uint32_t)I);
+    const uint32_t state = ds[1];
+    if (!(state & 1u)) continue;
+    const uint32_t* leafp = slot_leaf(j);
+    for (int q = lane; q < 2 * NW; q += 64) {
+      const int pl = q >= NW, w = q - (pl ? NW : 0);
+      pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
+    }
+    row_wave_sync();
+    puct_backup<NW, CN>(g, pos, slot_path(j), node, prior, child, nodes, depth, state, priors, priors_dtype, values,
+                        values_dtype, i * leaves + j, lane);
+  }
+
+  if (last) {
+    puct_move(C, node, child, nodes, live, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, i, actions,
+              visits, root_value, lane);
+    return;
+  }
+
+  // ---- the selections
+  const int nodes0 = nodes;
+  const uint16_t* epath = slot_path(min(lane, leaves - 1));  // lane l < leaves: slot l's path
+  int edepth = 0;                                            // and, once it has selected, its leaf's depth
+  uint32_t active = 0u;                                      // the slots of this round that have a leaf
+  bool open = live;                                          // no slot was void yet
+  for (int j = 0; j < leaves; ++j) {
+    int d = 0;
+    uint32_t nstate = 0u;
+    uint16_t* path = slot_path(j);
+    MnkEnv<NW> e;
+    if (open && nodes <= I) {
+      puct_env_root<NW>(e, root, NWg);
+      nstate = puct_walk<NW, CN, CK, true>(g, e, I, c, node, prior, child, path, nodes, d, lane, nodes0, active, epath,
+                                           edepth);
+    }
+    if (nstate) {
+      active |= 1u << j;
+      if (lane == j) edepth = d;
+    } else {
+      d = 0;
+      open = false;
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
+        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
+      }
+      path[0] = 0;
+      uint32_t* ds = slot_ds(j);
+      ds[0] = (uint32_t)d;
+      ds[1] = nstate;
+    }
+    row_wave_sync();
+    uint32_t* leafp = slot_leaf(j);
+    for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
+    row_write_view<NW, CN>(g, pos, d & 1, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
+    row_wave_sync();  // (the next slot's walk reads this one's node, child entry and path; its write-out reuses pos)
+  }
+  if (lane == 0) hdr[0] = (uint32_t)nodes;
+}
+
+// ------------------------------------------------------------------ the entry points
+// what the four pairs of entry points share: the host checks (before anything is enqueued) and the launch.  leaves = 0
+// stands for the entry point without the argument: today's kernels, one leaf.
+static bool puct_leaves_ok(int iterations, int leaves) {
+  return leaves == 0 || (leaves >= 1 && leaves <= MNK_PUCT_LEAVES_MAX && iterations % leaves == 0);
+}
+
+static int64_t puct_workspace_bytes(int64_t N, int m, int n, int iterations, int leaves) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, 1, &g);
   if (rc != MNK_OK) return rc;
-  if (N < 0 || iterations < 1 || iterations > MNK_PUCT_ITERS_MAX) return MNK_EINVAL;
-  return N * mnk_puct_layout(g.NW, g.C, iterations).row;
+  if (N < 0 || iterations < 1 || iterations > MNK_PUCT_ITERS_MAX || !puct_leaves_ok(iterations, leaves)) return MNK_EINVAL;
+  return N * mnk_puct_layout(g.NW, g.C, iterations, leaves ? leaves : 1).row;
 }
 
-int mnk_puct_begin(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, void* workspace,
-                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, void* stream) {
+static int puct_begin(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, int leaves,
+                      void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, void* stream) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
   if (!obs || !workspace || !leaf_obs || !leaf_mask || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS || !mnk_obs_dtype_ok(obs_dtype) ||
-      !mnk_obs_dtype_ok(leaf_dtype) || iterations < 1 || iterations > MNK_PUCT_ITERS_MAX)
+      !mnk_obs_dtype_ok(leaf_dtype) || iterations < 1 || iterations > MNK_PUCT_ITERS_MAX || !puct_leaves_ok(iterations, leaves))
     return MNK_EINVAL;
   if (N == 0) return MNK_OK;
   const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
   hipStream_t s = (hipStream_t)stream;
-  MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_begin), grid, block, 0, s, g, obs, obs_dtype, N, iterations,
-                                     (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask));
-  return mnk_launch_status("puct_begin");
+  if (leaves)
+    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_begin_leaves), grid, block, 0, s, g, obs, obs_dtype, N, iterations,
+                                       leaves, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask));
+  else
+    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_begin), grid, block, 0, s, g, obs, obs_dtype, N, iterations,
+                                       (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask));
+  return mnk_launch_status(leaves ? "puct_begin_leaves" : "puct_begin");
 }
 
-int mnk_puct_rebase(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int tree_iterations, int keep_nodes,
-                    void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried, void* stream) {
+static int puct_rebase(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int tree_iterations, int keep_nodes,
+                       int leaves, void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried,
+                       void* stream) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
+  // (at least one round's room: keep_nodes <= tree_iterations + 1 - J, J >= leaves)
   if (!obs || !workspace || !leaf_obs || !leaf_mask || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS || !mnk_obs_dtype_ok(obs_dtype) ||
-      !mnk_obs_dtype_ok(leaf_dtype) || tree_iterations < 1 || tree_iterations > MNK_PUCT_ITERS_MAX || keep_nodes < 1 ||
-      keep_nodes > tree_iterations)  // (at least one iteration's room: keep_nodes <= tree_iterations + 1 - J, J >= 1)
+      !mnk_obs_dtype_ok(leaf_dtype) || tree_iterations < 1 || tree_iterations > MNK_PUCT_ITERS_MAX ||
+      !puct_leaves_ok(tree_iterations, leaves) || keep_nodes < 1 || keep_nodes > tree_iterations + 1 - (leaves ? leaves : 1))
     return MNK_EINVAL;
   if (N == 0) return MNK_OK;
   const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
   hipStream_t s = (hipStream_t)stream;
-  MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_rebase), grid, block, 0, s, g, obs, obs_dtype, N, tree_iterations,
-                                     keep_nodes, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask, carried));
-  return mnk_launch_status("puct_rebase");
+  if (leaves)
+    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_rebase_leaves), grid, block, 0, s, g, obs, obs_dtype, N, tree_iterations,
+                                       keep_nodes, leaves, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask,
+                                       carried));
+  else
+    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_rebase), grid, block, 0, s, g, obs, obs_dtype, N, tree_iterations,
+                                       keep_nodes, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask, carried));
+  return mnk_launch_status(leaves ? "puct_rebase_leaves" : "puct_rebase");
 }
 
-int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iterations, const void* priors, int priors_dtype,
-                  const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
-                  const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
-                  void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
-                  float* root_value, void* stream) {
+static int puct_step(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                     int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                     uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                     int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                     int32_t* visits, float* root_value, void* stream) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
@@ -580,17 +822,75 @@ int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iteration
                      (values_dtype == MNK_LOGITS_F32 || values_dtype == MNK_LOGITS_BF16);
   if (!workspace || !priors || !values || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS || !dt_ok || iterations < 1 ||
       iterations > MNK_PUCT_ITERS_MAX || !(c >= 0.0f && c <= 3.0e38f) || (last != 0 && last != 1) ||
-      (temperature != 0 && temperature != 1))
+      (temperature != 0 && temperature != 1) || !puct_leaves_ok(iterations, leaves))
     return MNK_EINVAL;
   if (last ? !actions : (!leaf_obs || !leaf_mask || !mnk_obs_dtype_ok(leaf_dtype))) return MNK_EINVAL;
   if (N == 0) return MNK_OK;
   const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
   hipStream_t s = (hipStream_t)stream;
-  MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step), grid, block, 0, s, g, (unsigned char*)workspace, N, iterations,
-                                     priors, priors_dtype, values, values_dtype, c, last, temperature, seed, seed_dev,
-                                     step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions,
-                                     visits, root_value));
-  return mnk_launch_status("puct_step");
+  if (leaves)
+    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step_leaves), grid, block, 0, s, g, (unsigned char*)workspace, N,
+                                       iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
+                                       temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs,
+                                       leaf_dtype, leaf_mask, actions, visits, root_value));
+  else
+    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step), grid, block, 0, s, g, (unsigned char*)workspace, N, iterations,
+                                       priors, priors_dtype, values, values_dtype, c, last, temperature, seed, seed_dev,
+                                       step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions,
+                                       visits, root_value));
+  return mnk_launch_status(leaves ? "puct_step_leaves" : "puct_step");
+}
+
+extern "C" {
+
+int64_t mnk_puct_workspace_bytes(int64_t N, int m, int n, int iterations) {
+  return puct_workspace_bytes(N, m, n, iterations, 0);
+}
+int64_t mnk_puct_workspace_bytes_leaves(int64_t N, int m, int n, int iterations, int leaves) {
+  return leaves ? puct_workspace_bytes(N, m, n, iterations, leaves) : MNK_EINVAL;
+}
+
+int mnk_puct_begin(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, void* workspace,
+                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, void* stream) {
+  return puct_begin(obs, obs_dtype, N, m, n, k, iterations, 0, workspace, leaf_obs, leaf_dtype, leaf_mask, stream);
+}
+int mnk_puct_begin_leaves(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, int leaves,
+                          void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, void* stream) {
+  if (!leaves) return MNK_EINVAL;
+  return puct_begin(obs, obs_dtype, N, m, n, k, iterations, leaves, workspace, leaf_obs, leaf_dtype, leaf_mask, stream);
+}
+
+int mnk_puct_rebase(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int tree_iterations, int keep_nodes,
+                    void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried, void* stream) {
+  return puct_rebase(obs, obs_dtype, N, m, n, k, tree_iterations, keep_nodes, 0, workspace, leaf_obs, leaf_dtype, leaf_mask,
+                     carried, stream);
+}
+int mnk_puct_rebase_leaves(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int tree_iterations,
+                           int keep_nodes, int leaves, void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask,
+                           int32_t* carried, void* stream) {
+  if (!leaves) return MNK_EINVAL;
+  return puct_rebase(obs, obs_dtype, N, m, n, k, tree_iterations, keep_nodes, leaves, workspace, leaf_obs, leaf_dtype,
+                     leaf_mask, carried, stream);
+}
+
+int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iterations, const void* priors, int priors_dtype,
+                  const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
+                  const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
+                  void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
+                  float* root_value, void* stream) {
+  return puct_step(workspace, N, m, n, k, iterations, 0, priors, priors_dtype, values, values_dtype, c, last, temperature,
+                   seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions, visits,
+                   root_value, stream);
+}
+int mnk_puct_step_leaves(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                         int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                         uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                         int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                         int32_t* visits, float* root_value, void* stream) {
+  if (!leaves) return MNK_EINVAL;
+  return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
+                   temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
+                   actions, visits, root_value, stream);
 }
 
 }  // extern "C"

@@ -28,6 +28,7 @@ PLAYOUTS_MAX = 4096  # MNK_PLAYOUTS_MAX: the largest playout count of mnk_sample
 SEARCH_ITERS_MAX = 2048  # MNK_SEARCH_ITERS_MAX: the largest iteration budget of mnk_sample_search
 SEARCH_PLAYOUTS_MAX = 256  # MNK_SEARCH_PLAYOUTS_MAX: the largest playout count per leaf of mnk_sample_search
 PUCT_ITERS_MAX = 2048  # MNK_PUCT_ITERS_MAX: the largest iteration budget of mnk_puct_begin / mnk_puct_step
+PUCT_LEAVES_MAX = 16  # MNK_PUCT_LEAVES_MAX: the most leaves per row and evaluation of the mnk_puct_*_leaves entry points
 STATS_REPLICAS, STATS_STRIDE, STATS_COUNTERS = 64, 8, 5
 # run-time specialised API kernels (MNK_JIT_API_* of include/mnk_hip.h): bit numbers for jit_prepare()
 (JIT_API_STEP, JIT_API_STEP_DRAW, JIT_API_STEP_SUBSET, JIT_API_OBSERVE, JIT_API_SAMPLE_LEGAL, JIT_API_UNPACK_RECORDS,
@@ -100,6 +101,12 @@ SIGNATURES = {
     # sampler block, leaf obs, leaf dtype, leaf mask, actions, visits (int32 [N][C]), root value (f32 [N]), stream
     "mnk_puct_step": [_vp, _i64, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i, _vp, _i,
                       _vp, _vp, _vp, _vp, _vp],
+    # the four above with `leaves` (after iterations; after keep nodes for the rebase): L leaves per row and evaluation
+    "mnk_puct_workspace_bytes_leaves": [_i64, _i, _i, _i, _i],
+    "mnk_puct_begin_leaves": [_vp, _i, _i64, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp],
+    "mnk_puct_rebase_leaves": [_vp, _i, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
+    "mnk_puct_step_leaves": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i,
+                             _vp, _i, _vp, _vp, _vp, _vp, _vp],
     # planes, meta, N, m, n, k, visits (int32 [N][C]), temp_plies, then seed, seed_dev, step, step_dev, env_id0, T, ring
     # planes, ring visits, ring z, obs, obs dtype, legal mask, stats, err, stream
     "mnk_search_selfplay_step": [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _u64, _vp, _u64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
@@ -164,7 +171,7 @@ def load():
         if name in ("mnk_last_launch_error", "mnk_comm_last_error", "mnk_jit_last_error"):
             fn.restype = ctypes.c_char_p
         elif name in ("mnk_jit_compile_rollout", "mnk_jit_compile_kernel", "mnk_jit_compile_api",
-                      "mnk_puct_workspace_bytes"):
+                      "mnk_puct_workspace_bytes", "mnk_puct_workspace_bytes_leaves"):
             fn.restype = ctypes.c_int64
         else:
             fn.restype = ctypes.c_int
@@ -292,11 +299,15 @@ def state_words(m, n):
     return load().mnk_state_words(m, n)
 
 
-def puct_workspace_bytes(N: int, m: int, n: int, iterations: int) -> int:
-    """bytes of the PUCT tree workspace of N rows (mnk_puct_workspace_bytes); MnkHipError on a bad board or budget"""
-    size = load().mnk_puct_workspace_bytes(N, m, n, iterations)
+def puct_workspace_bytes(N: int, m: int, n: int, iterations: int, leaves: int = None) -> int:
+    """bytes of the PUCT tree workspace of N rows (mnk_puct_workspace_bytes; with ``leaves``,
+    mnk_puct_workspace_bytes_leaves); MnkHipError on a bad board, budget or number of leaves"""
+    if leaves is None:
+        name, size = "mnk_puct_workspace_bytes", load().mnk_puct_workspace_bytes(N, m, n, iterations)
+    else:
+        name, size = "mnk_puct_workspace_bytes_leaves", load().mnk_puct_workspace_bytes_leaves(N, m, n, iterations, leaves)
     if size < 0:
-        raise MnkHipError(f"mnk_puct_workspace_bytes: {_STATUS.get(size, f'status {size}')}")
+        raise MnkHipError(f"{name}: {_STATUS.get(size, f'status {size}')}")
     return size
 
 

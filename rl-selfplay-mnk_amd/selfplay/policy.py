@@ -300,10 +300,17 @@ class PUCTSearchPolicy(Policy):
     an ``act`` carries at most ``tree_nodes - iterations`` over, the oldest first.  The first evaluator call of an
     ``act`` is still on the roots; on a carried root it only renews the root's priors.  The kept statistics come from the
     evaluator as it was: after its weights change, ``reset_tree()`` drops them -- whether stale visits matter is the
-    caller's decision."""
+    caller's decision.
+
+    ``leaves=L`` (1 .. ``PUCT_LEAVES_MAX``, a divisor of ``iterations``; default 1, the search above) selects L leaves per
+    row before every evaluator call, each under a virtual loss for the ones selected before it in the round
+    (``mnk_puct_step_leaves``): the evaluator is called ``evaluations_per_act = iterations / L + 1`` times on batches of
+    ``N * L`` rows, rows ``i * L .. i * L + L - 1`` being row i's.  The first call is still the roots (row ``i * L``; the
+    other rows of that call, like every slot a round could not fill, repeat the root and are ignored).  With ``reuse`` the
+    workspace's ``tree_nodes - 1`` must be a multiple of L as well (the default is)."""
 
     def __init__(self, k: int, model=None, evaluator=None, iterations: int = 256, c: float = 1.25, temperature: int = 0,
-                 leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None):
+                 leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None, leaves: int = 1):
         if (model is None) == (evaluator is None):
             raise ValueError("PUCTSearchPolicy needs exactly one of model and evaluator")
         self.k = int(k)
@@ -320,6 +327,11 @@ class PUCTSearchPolicy(Policy):
             raise ValueError(f"c must be finite and >= 0, got {c}")
         if temperature not in (0, 1):
             raise ValueError(f"temperature must be 0 or 1, got {temperature}")
+        self.leaves = int(leaves)
+        if not 1 <= self.leaves <= mnk_hip.PUCT_LEAVES_MAX or self.leaves != leaves:
+            raise ValueError(f"leaves must lie in [1, {mnk_hip.PUCT_LEAVES_MAX}], got {leaves}")
+        if self.iterations % self.leaves:
+            raise ValueError(f"iterations must be a multiple of leaves, got {iterations} and {leaves}")
         self.leaf_dtype = leaf_dtype
         self._leaf_code = mnk_hip.obs_dtype_code(leaf_dtype)  # (TypeError for anything but float32 / bfloat16 / uint8)
         self._sampler = _HipSampler(seed)
@@ -330,20 +342,27 @@ class PUCTSearchPolicy(Policy):
                 raise ValueError(f"tree_nodes must lie in [iterations + 1, {mnk_hip.PUCT_ITERS_MAX + 1}] = "
                                  f"[{self.iterations + 1}, {mnk_hip.PUCT_ITERS_MAX + 1}], got {tree_nodes}"
                                  + (" (the default, 2 * iterations + 1)" if tree_nodes is None else ""))
+            if (self.tree_nodes - 1) % self.leaves:
+                raise ValueError(f"tree_nodes - 1 must be a multiple of leaves, got {self.tree_nodes} and {leaves}")
         else:
             if tree_nodes is not None:
                 raise ValueError("tree_nodes is the workspace of a search that keeps its tree: it needs reuse=True")
             self.tree_nodes = self.iterations + 1
         self._bufs = None  # (key, workspace, leaf_obs, leaf_mask)
 
+    @property
+    def evaluations_per_act(self) -> int:
+        """evaluator calls per ``act``: the roots', then one per round of ``leaves`` simulations"""
+        return self.iterations // self.leaves + 1
+
     def _buffers(self, b, m, n, device):
         key = (b, m, n, self.iterations, self.tree_nodes, device)
         if self._bufs is None or self._bufs[0] != key:
-            size = mnk_hip.puct_workspace_bytes(b, m, n, self.tree_nodes - 1)
+            size = mnk_hip.puct_workspace_bytes(b, m, n, self.tree_nodes - 1, self.leaves)
             # (a tree that is kept starts as zeros: no row continues a workspace of zeros)
             self._bufs = (key, (torch.zeros if self.reuse else torch.empty)(size, dtype=torch.uint8, device=device),
-                          torch.empty((b, 2, m, n), dtype=self.leaf_dtype, device=device),
-                          torch.empty((b, m * n), dtype=torch.bool, device=device))
+                          torch.empty((b * self.leaves, 2, m, n), dtype=self.leaf_dtype, device=device),
+                          torch.empty((b * self.leaves, m * n), dtype=torch.bool, device=device))
         return self._bufs[1:]
 
     def _evaluate(self, leaf_obs, leaf_mask, b, c):
@@ -387,17 +406,20 @@ class PUCTSearchPolicy(Policy):
             stream = mnk_hip.stream_ptr(dev)
             I, k, code = self.iterations, self.k, self._leaf_code
             cap = self.tree_nodes - 1  # the workspace's layout parameter: node capacity - 1 (= I without reuse)
+            # leaves = 1 stays on the entry points without the argument (the same results either way: include/mnk_hip.h)
+            sfx, lv = ("_leaves", (self.leaves,)) if self.leaves > 1 else ("", ())
             if self.reuse:
-                mnk_hip.call("mnk_puct_rebase", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k, cap,
-                             self.tree_nodes - I, mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask),
-                             mnk_hip.ptr(carried), stream)
+                mnk_hip.call("mnk_puct_rebase" + sfx, mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k,
+                             cap, self.tree_nodes - I, *lv, mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code,
+                             mnk_hip.ptr(leaf_mask), mnk_hip.ptr(carried), stream)
             else:
-                mnk_hip.call("mnk_puct_begin", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k, I,
-                             mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask), stream)
-            for it in range(I + 1):
-                priors, pcode, values, vcode = self._evaluate(leaf_obs, leaf_mask, b, m * n)
-                last = it == I
-                mnk_hip.call("mnk_puct_step", mnk_hip.ptr(ws), b, m, n, k, cap, mnk_hip.ptr(priors), pcode,
+                mnk_hip.call("mnk_puct_begin" + sfx, mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k,
+                             I, *lv, mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask), stream)
+            rounds = I // self.leaves
+            for it in range(rounds + 1):
+                priors, pcode, values, vcode = self._evaluate(leaf_obs, leaf_mask, b * self.leaves, m * n)
+                last = it == rounds
+                mnk_hip.call("mnk_puct_step" + sfx, mnk_hip.ptr(ws), b, m, n, k, cap, *lv, mnk_hip.ptr(priors), pcode,
                              mnk_hip.ptr(values), vcode, self.c, 1 if last else 0, self.temperature,
                              *self._sampler.block(deterministic), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask),
                              mnk_hip.ptr(actions) if last else None, mnk_hip.ptr(visits) if last else None,

@@ -9,7 +9,11 @@ step kernel both read, and one more tiny kernel advances it, so ``torch.cuda.gra
 buffers exist (after one eager ply) and the evaluator is capturable.
 
 Root noise (Dirichlet) stays an evaluator wrapper: the first evaluator call of every ``act`` is on the roots, so a wrapper
-that counts its calls modulo ``iterations + 1`` knows which call to perturb (examples/alphazero_selfplay.py).
+that counts its calls modulo the policy's ``evaluations_per_act`` knows which call to perturb
+(examples/alphazero_selfplay.py).
+
+``leaves=L`` searches with L leaves per row and evaluator call (``PUCTSearchPolicy(leaves=L)``): ``iterations / L + 1``
+calls per ply on batches of ``num_envs * L`` rows.
 
 ``reuse=True`` keeps every row's search tree from ply to ply (``PUCTSearchPolicy(reuse=True)``): the next root that the step
 kernel writes is what the next search matches its stored tree against, so the subtree of the move that was played -- drawn
@@ -28,7 +32,7 @@ from selfplay.policy import PUCTSearchPolicy
 class SearchSelfPlay:
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  c: float = 1.25, temp_plies: int = None, capacity: int = None, seed=None, leaf_dtype=torch.float32,
-                 device="cuda", reuse: bool = False, tree_nodes: int = None):
+                 device="cuda", reuse: bool = False, tree_nodes: int = None, leaves: int = 1):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -41,9 +45,10 @@ class SearchSelfPlay:
         capacity = 2 * C if capacity is None else int(capacity)
         if capacity < C:
             raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
-        # (the policy checks model / evaluator, iterations, c and leaf_dtype before anything touches the GPU)
+        # (the policy checks model / evaluator, iterations, c, leaves and leaf_dtype before anything touches the GPU)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
-                                       temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=reuse, tree_nodes=tree_nodes)
+                                       temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=reuse, tree_nodes=tree_nodes,
+                                       leaves=leaves)
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)

@@ -1,0 +1,52 @@
+"""What the CPU and the GPU tests of the PUCT player with several leaves per evaluation share: the boards, budgets and
+positions the GPU test runs (tests/test_gpu_puct_leaves.py), and the rule's answer on each, computed once per process.
+The CPU test (tests/test_puct_leaves_cpu.py) checks from the rule's trace alone that these inputs reach the paths a kernel
+can go wrong on: void slots, terminal leaves repeated within a round, slots that share a prefix -- and a case with none."""
+import functools
+
+import numpy as np
+
+from puct_leaves_rule import LeavesPuct
+from tactical_rule import random_positions
+from test_gpu_puct_reuse import exact_np
+
+C_PUCT, SEED, ENV_ID0 = 1.25, 43, 7
+#        name      board        rows  I     the L of the case
+CASES = {
+    "3x3x3": ((3, 3, 3), 23, 32, (1, 2, 4, 8, 16)),      # NW = 1; half-full boards: terminals everywhere, trees that run out
+    "4x6x3": ((4, 6, 3), 14, 48, (1, 2, 4, 8, 16)),      # the generic form, not square
+    "9x9x5": ((9, 9, 5), 6, 48, (1, 2, 4, 8, 16)),       # C > 64: two trips of every per-cell loop; a built-in variant
+    "19x19x5": ((19, 19, 5), 3, 32, (4, 16)),            # C = 361; fewer rows than a workgroup holds
+    "round": ((9, 9, 5), 5, 8, (8,)),                    # I = L: a single round
+    "long": ((9, 9, 5), 1, 2048, (16,)),                 # the largest budget and the most leaves, one row
+}
+PARAMS = [(name, L) for name, (_, _, _, Ls) in CASES.items() for L in Ls]
+
+
+def positions(name):
+    (m, n, k), rows, _, _ = CASES[name]
+    rng = np.random.default_rng(sum(map(ord, name)))
+    if name == "3x3x3":  # half-full: four or five stones, no run yet
+        out = []
+        while len(out) < rows:
+            o = random_positions(m, n, k, 1, rng, max_fill=0.6)[0]
+            if 4 <= o.sum() <= 5:
+                out.append(o)
+        obs = np.stack(out)
+    else:
+        obs = random_positions(m, n, k, rows, rng, max_fill=0.5 if name == "4x6x3" else 0.25)
+    if name in ("4x6x3", "9x9x5"):  # an empty board, and a full one (no legal cell: void slots only)
+        obs[0] = 0
+        obs[1, 0].reshape(-1)[::2], obs[1, 1].reshape(-1)[::2] = 1, 0
+        obs[1, 0].reshape(-1)[1::2], obs[1, 1].reshape(-1)[1::2] = 0, 1
+    return obs
+
+
+@functools.lru_cache(maxsize=None)
+def reference(name, L, temperature=0):
+    """(obs, (actions, visits, root_value), every evaluation's (leaf_obs, leaf_mask), the per-row trace) of the rule"""
+    (m, n, k), _, I, _ = CASES[name]
+    obs, seen = positions(name), []
+    rule = LeavesPuct(k, I, C_PUCT, exact_np(m * n), L, seed=SEED, env_id0=ENV_ID0, temperature=temperature, leaves=seen)
+    out = rule.act(obs, step=2)
+    return obs, out[:3], seen, rule.trace
