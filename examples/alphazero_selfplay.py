@@ -1,10 +1,12 @@
 """AlphaZero on the HIP env: PUCT self-play into an outcome-labelled ring (``SearchSelfPlay``), minibatches with the
 board's symmetries (``SearchReplayBuffer.sample``), the loss -sum(pi * log p) + (v - z)^2 weighted by ``weight`` (0 for
 records of games still running), and validation of the greedy network against ``RandomPolicy`` and ``TacticalPolicy``.
-Root noise is an evaluator wrapper (``RootNoise``): Dirichlet noise mixed into the priors of the first evaluator call of
-every search, the one on the roots.  ``--reuse`` keeps every search tree from ply to ply (the subtree of the move that
-was played starts the next search; the roots' priors, and so the noise, are renewed every ply) and drops the trees after
-each training round, since their statistics are the old weights'.
+Root noise is Dirichlet noise mixed into the priors of the first evaluator call of every search, the one on the roots:
+``--noise wrapper`` (the default) draws it in an evaluator wrapper (``RootNoise``) from torch's generator, ``--noise
+builtin`` in the search itself (``SearchSelfPlay(root_noise=...)``: Philox-keyed by seed, row and ply, so a run can be
+restored, sharded and captured without changing a draw), ``--noise off`` plays without.  ``--reuse`` keeps every search
+tree from ply to ply (the subtree of the move that was played starts the next search; the roots' priors, and so the noise,
+are renewed every ply) and drops the trees after each training round, since their statistics are the old weights'.
 
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse]
 """
@@ -74,7 +76,8 @@ def greedy(net):
 
 def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates=40, batch=512, lr=2e-3, seed=0,
           noise=True, reuse=False, leaves=1, log=print):
-    """self-play and training rounds; returns the network"""
+    """self-play and training rounds; returns the network.  ``noise``: True / "wrapper" (``RootNoise``), "builtin" (the
+    search's own root noise, same alpha and eps) or False / "off" (none)"""
     entry.build()
     from selfplay.policy import model_evaluator
     from selfplay.search_selfplay import SearchSelfPlay
@@ -85,10 +88,14 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
     net = PolicyValueNet(C).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     evaluator = model_evaluator(net)
-    if noise:
+    noise = {True: "wrapper", False: "off"}.get(noise, noise)
+    if noise not in ("wrapper", "builtin", "off"):
+        raise ValueError(f"noise must be 'wrapper', 'builtin' or 'off', got {noise!r}")
+    if noise == "wrapper":
         evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
-                        capacity=2 * C, seed=seed, reuse=reuse, leaves=leaves)
+                        capacity=2 * C, seed=seed, reuse=reuse, leaves=leaves,
+                        root_noise=(0.3, 0.25) if noise == "builtin" else None)
     assert sp.policy.evaluations_per_act == iterations // leaves + 1
     plies = C if plies is None else plies
     gen = torch.Generator(device=dev)
@@ -135,13 +142,16 @@ def main():
     ap.add_argument("--updates", type=int, default=40)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--reuse", action="store_true", help="keep the subtree of the move played for the next search")
+    ap.add_argument("--noise", choices=("wrapper", "builtin", "off"), default="wrapper",
+                    help="Dirichlet root noise: an evaluator wrapper on torch's generator, the search's own (Philox-keyed, "
+                         "reproducible), or none")
     ap.add_argument("--leaves", type=int, default=1,
                     help="leaves per row and evaluator call (a divisor of --iterations, at most 16): the network sees "
                          "iterations / leaves + 1 batches of envs * leaves positions per move")
     a = ap.parse_args()
     m, n, k = (int(x) for x in a.board.lower().split("x"))
     net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed,
-                reuse=a.reuse, leaves=a.leaves)
+                noise=a.noise, reuse=a.reuse, leaves=a.leaves)
     for name, res in validate(net, m, n, k).items():
         print(f"vs {name}: win {res['win_rate']:.3f} loss {res['loss_rate']:.3f} draw {res['draw_rate']:.3f} "
               f"score {res['score_rate']:.3f}")

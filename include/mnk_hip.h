@@ -124,6 +124,7 @@ extern "C" {
 #define MNK_STREAM_PLAYOUT 4 /* the random plies of the Monte Carlo player's playouts (mnk_sample_playouts) */
 #define MNK_STREAM_SEARCH 5  /* the random plies of the tree-search player's playouts (mnk_sample_search) */
 #define MNK_STREAM_SELFPLAY 6 /* the move of a search self-play ply (mnk_search_selfplay_step) */
+#define MNK_STREAM_NOISE 7    /* the Dirichlet noise on the PUCT player's root priors (mnk_puct_root_noise) */
 
 int mnk_abi_version(void);
 /* Developer knobs (MNK_ROLLOUT_PAIR, MNK_ROLLOUT_FORM, MNK_JIT, MNK_ROLLOUT_SADDR, MNK_EMIT_ENVS, MNK_EMIT_THREADS: A/B
@@ -505,6 +506,31 @@ int mnk_puct_step_leaves(void* workspace, int64_t N, int m, int n, int k, int it
                          uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                          int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                          int32_t* visits, float* root_value, void* stream);
+/* Dirichlet root noise for the search above (optional): one launch between evaluation 0 and the first mnk_puct_step[_leaves]
+ * that mixes eta ~ Dirichlet(alpha) over each root's free cells into a copy of the root's priors.  priors (f32 / bf16,
+ * MNK_LOGITS_*) and mask (u8, non-zero = free) are evaluation 0's [N * leaves][C] tensors; row i's root is batch row
+ * i * leaves.  out is a caller-owned f32 [N * leaves][C] buffer of which only the rows i * leaves are written -- the step
+ * reads no other row of evaluation 0 -- and which the first step then takes as its f32 priors.  priors is never written
+ * (an evaluator may hand back the same tensor every call).  The rule for row i, F = its free cells, C4 = C rounded up to a
+ * multiple of 4, alpha and eps widened to f64, all arithmetic f64 unless marked:
+ *   draws: cell a and try t = 0 .. MNK_PUCT_NOISE_TRIES - 1 own u = ((step [+ *step_dev]) * C4 + a) * 16 + t and
+ *     x_j = Philox(seed [or *seed_dev], env_id0 + i, 4 * u + j, MNK_STREAM_NOISE), j = 0 .. 3 -- the four words of one
+ *     Philox block; U_j = (x_j + 0.5) * 2^-32, never 0 or 1.
+ *   Gamma(alpha + 1) by Marsaglia and Tsang: d = alpha + 1 - 1/3, c = 1 / sqrt(9 d), z = sqrt(-2 ln U_0) * cos(2 pi U_1),
+ *     v = (1 + c z)^3; the try is accepted iff v > 0 and ln U_2 < 0.5 z^2 + d - d v + d ln v.
+ *   the first accepted try gives l_a = ln(d v) + ln(U_3) / alpha (the boost to shape alpha, U^(1 / alpha), in log space);
+ *     if none of the 16 is accepted (acceptance is above 0.95 per try), l_a = ln d + ln(U_3) / alpha with try 15's U_3.
+ *   normalisation: M = max of l_a over F, e_a = exp(l_a - M), eta_a = e_a / sum of e over F (at alpha = 0.03 the gammas
+ *     of a 19x19 root span hundreds of decades: their plain sum can be 0).
+ *   the mix, in correctly rounded f32 operations: w = fl32(1 - eps), P'_a = fl32(fl32(w * P_a) + fl32(eps * fl32(eta_a)))
+ *     on free cells, P'_a = P_a elsewhere (a bf16 prior widened exactly).  A row with no free cell is a plain copy.
+ *     Priors are not renormalised, as they are not without noise.
+ * C in [1, 1024], leaves in [1, MNK_PUCT_LEAVES_MAX], alpha finite and > 0, eps in [0, 1]; every host check runs before
+ * anything is enqueued.  One wave per row; the kernel needs C and the mask only, no board geometry. */
+#define MNK_PUCT_NOISE_TRIES 16
+int mnk_puct_root_noise(const void* priors, int priors_dtype, const void* mask, int64_t N, int C, int leaves, float alpha,
+                        float eps, uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev,
+                        int64_t env_id0, float* out, void* stream);
 
 /* ---- search self-play: the env side of an AlphaZero loop.  A ply = a search that writes every row's root visit counts
  * (PUCTSearchPolicy.act(visits=...), mnk_puct_step), then ONE mnk_search_selfplay_step launch that plays every row's move

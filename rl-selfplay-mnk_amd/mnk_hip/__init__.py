@@ -23,12 +23,14 @@ ACT_U8, ACT_U16, ACT_BITS7, ACT_U8P1 = 1, 2, 3, 4
 COMM_ID_BYTES = 128
 SP_NEED_OPP, SP_WAS_RESET = 1, 2
 STREAM_MOVE, STREAM_OPP, STREAM_SIDE, STREAM_SAMPLE, STREAM_PLAYOUT, STREAM_SEARCH, STREAM_SELFPLAY = 0, 1, 2, 3, 4, 5, 6
+STREAM_NOISE = 7  # MNK_STREAM_NOISE: the Dirichlet noise on the PUCT player's root priors (mnk_puct_root_noise)
 Z_UNKNOWN = -128  # MNK_Z_UNKNOWN: the outcome of a ring record whose game is still running
 PLAYOUTS_MAX = 4096  # MNK_PLAYOUTS_MAX: the largest playout count of mnk_sample_playouts
 SEARCH_ITERS_MAX = 2048  # MNK_SEARCH_ITERS_MAX: the largest iteration budget of mnk_sample_search
 SEARCH_PLAYOUTS_MAX = 256  # MNK_SEARCH_PLAYOUTS_MAX: the largest playout count per leaf of mnk_sample_search
 PUCT_ITERS_MAX = 2048  # MNK_PUCT_ITERS_MAX: the largest iteration budget of mnk_puct_begin / mnk_puct_step
 PUCT_LEAVES_MAX = 16  # MNK_PUCT_LEAVES_MAX: the most leaves per row and evaluation of the mnk_puct_*_leaves entry points
+PUCT_NOISE_TRIES = 16  # MNK_PUCT_NOISE_TRIES: the most Marsaglia-Tsang candidates per cell of mnk_puct_root_noise
 STATS_REPLICAS, STATS_STRIDE, STATS_COUNTERS = 64, 8, 5
 # run-time specialised API kernels (MNK_JIT_API_* of include/mnk_hip.h): bit numbers for jit_prepare()
 (JIT_API_STEP, JIT_API_STEP_DRAW, JIT_API_STEP_SUBSET, JIT_API_OBSERVE, JIT_API_SAMPLE_LEGAL, JIT_API_UNPACK_RECORDS,
@@ -107,6 +109,9 @@ SIGNATURES = {
     "mnk_puct_rebase_leaves": [_vp, _i, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "mnk_puct_step_leaves": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i,
                              _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    # priors, priors dtype, mask, N, C, leaves, alpha, eps, then seed, seed_dev, step, step_dev, env_id0, out (f32
+    # [N * leaves][C]), stream
+    "mnk_puct_root_noise": [_vp, _i, _vp, _i64, _i, _i, _f, _f, _u64, _vp, _u64, _vp, _i64, _vp, _vp],
     # planes, meta, N, m, n, k, visits (int32 [N][C]), temp_plies, then seed, seed_dev, step, step_dev, env_id0, T, ring
     # planes, ring visits, ring z, obs, obs dtype, legal mask, stats, err, stream
     "mnk_search_selfplay_step": [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _u64, _vp, _u64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,

@@ -23,6 +23,7 @@
                    recognised (``fused_logits``): the wrapper asks it for its logits only and the draw happens INSIDE
                    ``mnk_selfplay_post_logits`` -- same stream of random numbers, one launch fewer per step.
 """
+import ctypes
 import math
 from abc import ABC, abstractmethod
 from typing import Dict
@@ -282,9 +283,17 @@ class PUCTSearchPolicy(Policy):
     of ``leaf_dtype`` (channel 0 = the leaf's side to move), ``leaf_mask`` a bool ``[N, m*n]`` of its legal cells; priors
     and values in float32 or bfloat16, the value from the view of the leaf's side to move.  Priors are used as returned
     (not renormalised).  With ``model`` instead, ``model_evaluator(model)``.  The first evaluator call of every ``act`` is
-    always on the roots (the rows of ``obs`` themselves): an evaluator that mixes noise into the priors of that call
-    (Dirichlet root noise, say) only has to count its calls modulo ``iterations + 1``.  The rows of terminal leaves are
-    evaluated too (a fixed batch shape) and their outputs ignored.
+    always on the roots (the rows of ``obs`` themselves): an evaluator that perturbs the priors of that call only has to
+    count its calls modulo ``evaluations_per_act``.  The rows of terminal leaves are evaluated too (a fixed batch shape)
+    and their outputs ignored.
+
+    ``root_noise=(alpha, eps)`` mixes Dirichlet noise into every root's priors (the rule: include/mnk_hip.h,
+    mnk_puct_root_noise): ``(1 - eps) * P + eps * eta`` on the root's free cells, ``eta ~ Dirichlet(alpha)`` over them,
+    drawn from Philox keyed by (seed, row id, call) like the move -- the same noise however the rows are sharded, after a
+    restored ``state_dict`` and in every replay of a captured ``act``.  One more launch per ``act``, after the roots'
+    evaluation, into a float32 buffer of the policy's own: the evaluator's tensor is never written.  With ``reuse`` a
+    carried root takes fresh priors every ``act`` and so fresh noise.  ``None`` (the default): no noise, no launch, no
+    buffer.
 
     The tree and the leaf buffers are allocated on the first ``act`` and reused while (N, m, n, iterations) stay; after
     that an ``act`` allocates nothing of its own but its result and never synchronises with the host, so
@@ -310,7 +319,8 @@ class PUCTSearchPolicy(Policy):
     workspace's ``tree_nodes - 1`` must be a multiple of L as well (the default is)."""
 
     def __init__(self, k: int, model=None, evaluator=None, iterations: int = 256, c: float = 1.25, temperature: int = 0,
-                 leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None, leaves: int = 1):
+                 leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None, leaves: int = 1,
+                 root_noise=None):
         if (model is None) == (evaluator is None):
             raise ValueError("PUCTSearchPolicy needs exactly one of model and evaluator")
         self.k = int(k)
@@ -348,7 +358,23 @@ class PUCTSearchPolicy(Policy):
             if tree_nodes is not None:
                 raise ValueError("tree_nodes is the workspace of a search that keeps its tree: it needs reuse=True")
             self.tree_nodes = self.iterations + 1
-        self._bufs = None  # (key, workspace, leaf_obs, leaf_mask)
+        self.root_noise = self._checked_root_noise(root_noise)
+        self._bufs = None  # (key, workspace, leaf_obs, leaf_mask, noised priors or None)
+
+    @staticmethod
+    def _checked_root_noise(root_noise):
+        """None, or (alpha, eps) as floats: alpha finite and > 0 (as a float32 too), eps in [0, 1]"""
+        if root_noise is None:
+            return None
+        try:
+            alpha, eps = (float(x) for x in root_noise)
+        except (TypeError, ValueError):
+            raise ValueError(f"root_noise must be None or (alpha, eps), got {root_noise!r}") from None
+        if not (math.isfinite(alpha) and alpha <= 3.0e38 and ctypes.c_float(alpha).value > 0.0):
+            raise ValueError(f"root_noise: alpha must be finite and > 0 as a float32, got {alpha}")
+        if not 0.0 <= eps <= 1.0:
+            raise ValueError(f"root_noise: eps must lie in [0, 1], got {eps}")
+        return alpha, eps
 
     @property
     def evaluations_per_act(self) -> int:
@@ -362,7 +388,10 @@ class PUCTSearchPolicy(Policy):
             # (a tree that is kept starts as zeros: no row continues a workspace of zeros)
             self._bufs = (key, (torch.zeros if self.reuse else torch.empty)(size, dtype=torch.uint8, device=device),
                           torch.empty((b * self.leaves, 2, m, n), dtype=self.leaf_dtype, device=device),
-                          torch.empty((b * self.leaves, m * n), dtype=torch.bool, device=device))
+                          torch.empty((b * self.leaves, m * n), dtype=torch.bool, device=device),
+                          # (zeros: only the roots' rows are ever written, the step reads no other row of evaluation 0)
+                          torch.zeros((b * self.leaves, m * n), dtype=torch.float32, device=device)
+                          if self.root_noise is not None else None)
         return self._bufs[1:]
 
     def _evaluate(self, leaf_obs, leaf_mask, b, c):
@@ -402,7 +431,7 @@ class PUCTSearchPolicy(Policy):
                 raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {shape} tensor on {dev}")
         actions = torch.empty(b, dtype=torch.long, device=dev)
         if b:
-            ws, leaf_obs, leaf_mask = self._buffers(b, m, n, dev)
+            ws, leaf_obs, leaf_mask, noised = self._buffers(b, m, n, dev)
             stream = mnk_hip.stream_ptr(dev)
             I, k, code = self.iterations, self.k, self._leaf_code
             cap = self.tree_nodes - 1  # the workspace's layout parameter: node capacity - 1 (= I without reuse)
@@ -419,6 +448,10 @@ class PUCTSearchPolicy(Policy):
             for it in range(rounds + 1):
                 priors, pcode, values, vcode = self._evaluate(leaf_obs, leaf_mask, b * self.leaves, m * n)
                 last = it == rounds
+                if it == 0 and noised is not None:  # the roots' priors, noise mixed in, as f32 in the policy's buffer
+                    mnk_hip.call("mnk_puct_root_noise", mnk_hip.ptr(priors), pcode, mnk_hip.ptr(leaf_mask), b, m * n,
+                                 self.leaves, *self.root_noise, *self._sampler.block()[:5], mnk_hip.ptr(noised), stream)
+                    priors, pcode = noised, mnk_hip.LOGITS_F32
                 mnk_hip.call("mnk_puct_step" + sfx, mnk_hip.ptr(ws), b, m, n, k, cap, *lv, mnk_hip.ptr(priors), pcode,
                              mnk_hip.ptr(values), vcode, self.c, 1 if last else 0, self.temperature,
                              *self._sampler.block(deterministic), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask),

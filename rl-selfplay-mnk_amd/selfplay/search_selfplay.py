@@ -8,9 +8,11 @@ Nothing waits on the host: the ply counter is a device word (the buffer's ``plie
 step kernel both read, and one more tiny kernel advances it, so ``torch.cuda.graph`` can capture ``play(1)`` once the
 buffers exist (after one eager ply) and the evaluator is capturable.
 
-Root noise (Dirichlet) stays an evaluator wrapper: the first evaluator call of every ``act`` is on the roots, so a wrapper
-that counts its calls modulo the policy's ``evaluations_per_act`` knows which call to perturb
-(examples/alphazero_selfplay.py).
+``root_noise=(alpha, eps)`` mixes Dirichlet noise into every root's priors (``PUCTSearchPolicy(root_noise=...)``, the rule:
+include/mnk_hip.h, mnk_puct_root_noise).  The sampler's step is the ring's ply counter, so the noise of ply p is a function
+of (seed, row id, p) alone: a restored ``state_dict`` and every replay of a captured ``play(1)`` draw what an eager run
+draws.  (An evaluator wrapper can still perturb the roots' call -- the first of every ``evaluations_per_act`` -- from a
+generator of its own, without any of that: examples/alphazero_selfplay.py keeps one.)
 
 ``leaves=L`` searches with L leaves per row and evaluator call (``PUCTSearchPolicy(leaves=L)``): ``iterations / L + 1``
 calls per ply on batches of ``num_envs * L`` rows.
@@ -32,7 +34,7 @@ from selfplay.policy import PUCTSearchPolicy
 class SearchSelfPlay:
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  c: float = 1.25, temp_plies: int = None, capacity: int = None, seed=None, leaf_dtype=torch.float32,
-                 device="cuda", reuse: bool = False, tree_nodes: int = None, leaves: int = 1):
+                 device="cuda", reuse: bool = False, tree_nodes: int = None, leaves: int = 1, root_noise=None):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -45,10 +47,11 @@ class SearchSelfPlay:
         capacity = 2 * C if capacity is None else int(capacity)
         if capacity < C:
             raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
-        # (the policy checks model / evaluator, iterations, c, leaves and leaf_dtype before anything touches the GPU)
+        # (the policy checks model / evaluator, iterations, c, leaves, root_noise and leaf_dtype before anything touches the
+        # GPU)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
                                        temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=reuse, tree_nodes=tree_nodes,
-                                       leaves=leaves)
+                                       leaves=leaves, root_noise=root_noise)
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
