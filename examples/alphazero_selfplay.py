@@ -7,8 +7,10 @@ builtin`` in the search itself (``SearchSelfPlay(root_noise=...)``: Philox-keyed
 restored, sharded and captured without changing a draw), ``--noise off`` plays without.  ``--reuse`` keeps every search
 tree from ply to ply (the subtree of the move that was played starts the next search; the roots' priors, and so the noise,
 are renewed every ply) and drops the trees after each training round, since their statistics are the old weights'.
+``--solver`` proves wins, draws and losses inside the search (``SearchSelfPlay(solver=True)``): the policy targets drop
+the moves proven to lose.
 
-    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse]
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse] [--solver]
 """
 import argparse
 import os
@@ -75,7 +77,7 @@ def greedy(net):
 
 
 def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates=40, batch=512, lr=2e-3, seed=0,
-          noise=True, reuse=False, leaves=1, log=print):
+          noise=True, reuse=False, leaves=1, solver=False, log=print):
     """self-play and training rounds; returns the network.  ``noise``: True / "wrapper" (``RootNoise``), "builtin" (the
     search's own root noise, same alpha and eps) or False / "off" (none)"""
     entry.build()
@@ -94,7 +96,7 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
     if noise == "wrapper":
         evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
-                        capacity=2 * C, seed=seed, reuse=reuse, leaves=leaves,
+                        capacity=2 * C, seed=seed, reuse=reuse, leaves=leaves, solver=solver,
                         root_noise=(0.3, 0.25) if noise == "builtin" else None)
     assert sp.policy.evaluations_per_act == iterations // leaves + 1
     plies = C if plies is None else plies
@@ -148,10 +150,12 @@ def main():
     ap.add_argument("--leaves", type=int, default=1,
                     help="leaves per row and evaluator call (a divisor of --iterations, at most 16): the network sees "
                          "iterations / leaves + 1 batches of envs * leaves positions per move")
+    ap.add_argument("--solver", action="store_true",
+                    help="prove wins, draws and losses in the search tree; proven losses leave the policy targets")
     a = ap.parse_args()
     m, n, k = (int(x) for x in a.board.lower().split("x"))
     net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed,
-                noise=a.noise, reuse=a.reuse, leaves=a.leaves)
+                noise=a.noise, reuse=a.reuse, leaves=a.leaves, solver=a.solver)
     for name, res in validate(net, m, n, k).items():
         print(f"vs {name}: win {res['win_rate']:.3f} loss {res['loss_rate']:.3f} draw {res['draw_rate']:.3f} "
               f"score {res['score_rate']:.3f}")

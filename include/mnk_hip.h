@@ -506,6 +506,39 @@ int mnk_puct_step_leaves(void* workspace, int64_t N, int m, int n, int k, int it
                          uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                          int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                          int32_t* visits, float* root_value, void* stream);
+/* mnk_puct_step_leaves with exact game-theoretic proofs in the backup ("MCTS-Solver"; optional: a search that never calls
+ * it is the search above).  The workspace is that of mnk_puct_begin_leaves / mnk_puct_rebase_leaves, leaves in [1,
+ * MNK_PUCT_LEAVES_MAX]; every step of an act is this entry point (and with mnk_puct_rebase_leaves every act on the tree).
+ * Every node has a PROOF from the same point of view as its w, the player who moved into it: 0 unknown, 1 WIN, 2 DRAW,
+ * 3 LOSS; the root's point of view is the opponent of its side to move.  A proven node is worth, for its own side to
+ * move, -1 (WIN), 0 (DRAW), +1 (LOSS).  Proofs are kept with the node, so a kept subtree keeps them; the node that
+ * becomes the new root starts unknown again.
+ *   creation: a new node whose move won is WIN, one whose move filled the board is DRAW, any other is unknown.
+ *   selection at an evaluated, unproven node v: the candidates are the free cells whose child is not proven LOSS (a move
+ *     proven to lose for the player making it); if that leaves none, all free cells.  The candidates are scored exactly
+ *     as above (virtual visits included), the maximal score wins, ties to the lowest cell.  A child that does not exist
+ *     is created and is the leaf.  A child with a proof is the leaf and needs no evaluation, as a terminal child above
+ *     (as often as the round's slots reach it); its backup's v is -1 (WIN), 0 (DRAW), +1 (LOSS).  Otherwise descend.
+ *     A root with a proof selects nothing: its slots are void, as those of a row whose tree is full.
+ *   backup: n and w along the path exactly as above.  When the leaf has a proof, then for p = depth - 1 down to 0, x =
+ *     the path's node at depth p:  (1) x has a proof: stop;  (2) some child of x is WIN: x is LOSS;  (3) else some free
+ *     cell of x has no child or an unknown one: x stays unknown, stop;  (4) else every child is LOSS: x is WIN;  (5) else
+ *     x is DRAW.  At most `depth` levels.  It runs on every backup of a proven leaf, so a carried root is proven again by
+ *     the first visit to its deciding child.  w is not rewritten when a node becomes proven.
+ *   the move: adjusted counts n' over the root's free cells -- some root child is WIN: n' = n on the WIN children and 0
+ *     elsewhere; else n' = 0 on the LOSS children and n elsewhere; if that is all zero, n' = n.  visits = n', and the move
+ *     is drawn from n' by the rules above (both temperatures, deterministic).  WITH THE SOLVER visits NO LONGER SUM TO THE
+ *     NUMBER OF ITERATIONS: a proven root stops searching, and counts are dropped from n'.
+ *   root_value = +1, 0 or -1 exactly when the root is proven (LOSS, DRAW, WIN), -w_root / n_root otherwise.
+ *   proof (optional, NULL = off) int8 [N] = the root's proof for its side to move: +1 a proven win, 0 a proven draw, -1 a
+ *     proven loss, MNK_PROOF_UNKNOWN otherwise (and on a row without a legal cell).
+ * leaves outside [1, MNK_PUCT_LEAVES_MAX] is MNK_EINVAL; every host check runs before anything is enqueued. */
+#define MNK_PROOF_UNKNOWN (-128)
+int mnk_puct_step_solver(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                         int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                         uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                         int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                         int32_t* visits, float* root_value, int8_t* proof, void* stream);
 /* Dirichlet root noise for the search above (optional): one launch between evaluation 0 and the first mnk_puct_step[_leaves]
  * that mixes eta ~ Dirichlet(alpha) over each root's free cells into a copy of the root's priors.  priors (f32 / bf16,
  * MNK_LOGITS_*) and mask (u8, non-zero = free) are evaluation 0's [N * leaves][C] tensors; row i's root is batch row

@@ -4,7 +4,8 @@
 // I + 1 evaluator calls and I + 1 steps with no host synchronisation.  mnk_puct_rebase in the place of mnk_puct_begin
 // carries the subtree of the position that was reached into the next search.  The *_leaves entry points run the same
 // search with L leaves per row and evaluation (a round = L backups, then L selections under virtual visits), so the
-// evaluator sees I / L + 1 batches of N * L rows.  The rule: include/mnk_hip.h.
+// evaluator sees I / L + 1 batches of N * L rows.  mnk_puct_step_solver is mnk_puct_step_leaves with exact proofs of wins,
+// draws and losses in the backup (a 2-bit proof per node, propagated up the leaf's path).  The rule: include/mnk_hip.h.
 #include "mnk_host.h"
 #include "mnk_wave_rows.h"
 
@@ -12,15 +13,18 @@
 struct MnkPuctNode {
   uint32_t n;
   float w;
-  uint32_t info;  // the move into the node | term << 16 (0: not terminal; 1: the move won; 2: it filled the board) |
+  uint32_t info;  // the move into the node | proof << 12 (k_puct_step_solver only; from w's point of view, 0: unknown,
+                  // 1: WIN, 2: DRAW, 3: LOSS) | term << 16 (0: not terminal; 1: the move won; 2: it filled the board) |
                   // the parent's id << 18 (what k_puct_rebase marks a subtree by; the root's is 0)
 };
+#define MNK_PUCT_PROOF(info) (((info) >> 12) & 3u)
 #define MNK_PUCT_TERM(info) (((info) >> 16) & 3u)
 #define MNK_PUCT_PARENT(info) ((info) >> 18)
 static_assert(sizeof(MnkPuctNode) == 12, "node record");
 
 // The workspace of one row, at row * L.row bytes (every part 16-byte aligned, the row 256-byte aligned):
-//   header   u32[4]          nodes created, leaf depth, state (bit 0: a backup is pending; bits 1-2: the leaf's term;
+//   header   u32[4]          nodes created, leaf depth, state (bit 0: a backup is pending; bits 1-2: the leaf's term, with
+//                            the solver its proof;
 //                            bit 3: the pending evaluation is of a root that k_puct_rebase carried over -- it only
 //                            renews the root's priors), live (the root has a legal cell)
 //   root     u32[2][NWg]     the root's guard-column bit planes (plane 0 = the root's side to move), NWg = MnkGeom::NW
@@ -402,7 +406,11 @@ k_puct_rebase_leaves(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I
 
 // ------------------------------------------------------------------ one backup, then one selection (or the move)
 // The backup of one pending evaluation (state bit 0 set): batch row b of priors / values, the leaf's planes in pos (LDS).
-template <int NW, int CN>
+// SOLVER: the leaf's term is its proof (3: a proven loss of its mover, +1 for its side to move), and a proven leaf's
+// backup ends with the proofs of its path, leaf side first: one scan of a node's child row per level (the selection's
+// access shape, the children's info gathered, reduced over the wave), at most `depth` levels, over as soon as a node
+// stays unknown or was proven before.
+template <int NW, int CN, bool SOLVER = false>
 __device__ __forceinline__ void puct_backup(const MnkGeom& g, const uint32_t* pos, const uint16_t* path, MnkPuctNode* node,
                                             float* prior, uint16_t* child, int nodes, int depth, uint32_t state,
                                             const void* priors, int priors_dtype, const void* values, int values_dtype,
@@ -414,6 +422,8 @@ __device__ __forceinline__ void puct_backup(const MnkGeom& g, const uint32_t* po
   float v;
   if (term) {
     v = term == 1u ? -1.0f : 0.0f;  // the mover into the leaf won: a loss for its side to move
+    if constexpr (SOLVER)
+      if (term == 3u) v = 1.0f;
   } else {
     v = puct_read(values, values_dtype, b);
     float* pr = prior + (int64_t)lf * C;
@@ -430,16 +440,89 @@ __device__ __forceinline__ void puct_backup(const MnkGeom& g, const uint32_t* po
     k->w = __fadd_rn(k->w, ((depth - p) & 1) ? v : -v);
   }
   row_wave_sync();
+  if constexpr (SOLVER) {
+    for (int p = depth - 1; p >= 0 && term; --p) {
+      const int x = min((int)path[p], nodes - 1);
+      const uint32_t info = node[x].info;
+      if (MNK_PUCT_PROOF(info)) break;
+      const uint16_t* cl = child + (int64_t)x * C;
+      bool win = false, open = false, held = false;  // a child that is WIN / missing or unknown / not LOSS
+      for (int a = lane; a < C; a += 64) {
+        const uint32_t ch = cl[a];
+        if (ch == MNK_PUCT_NONE) continue;
+        const uint32_t pf = ch ? MNK_PUCT_PROOF(node[min((int)ch, nodes - 1)].info) : 0u;
+        win |= pf == 1u;
+        open |= pf == 0u;
+        held |= pf != 3u;
+      }
+      uint32_t pf = 3u;  // a move that wins: the mover into x has lost
+      if (!__ballot(win)) {
+        if (__ballot(open)) break;
+        pf = __ballot(held) ? 2u : 1u;
+      }
+      if (lane == 0) node[x].info = info | (pf << 12);
+      row_wave_sync();  // (the next level gathers this proof)
+    }
+  }
 }
 
 // The move, the visits, the root value of row i, after its last backup.
+// SOLVER: the counts are the adjusted ones (`keep`: 0 = every child's n, 1 = the WIN children's, 2 = all but the LOSS
+// children's), a proven root's value is exact, and `proof` takes the root's proof for its side to move.
+template <bool SOLVER = false>
 __device__ __forceinline__ void puct_move(int C, const MnkPuctNode* node, const uint16_t* child, int nodes, bool live,
                                           int temperature, uint64_t seed, const uint64_t* seed_dev, uint64_t step,
                                           const uint64_t* step_dev, int64_t env_id0, int deterministic, int64_t i,
-                                          int64_t* actions, int32_t* visits, float* root_value, int lane) {
+                                          int64_t* actions, int32_t* visits, float* root_value, int lane,
+                                          int8_t* proof = nullptr) {
   if (step_dev) step += *step_dev;
   if (seed_dev) seed = *seed_dev;
   const uint32_t x = deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(env_id0 + i), step, MNK_STREAM_SAMPLE);
+  if constexpr (SOLVER) {
+    auto kid = [&](int a) {  // the root's child through cell a; n = 0 where there is none
+      MnkPuctNode k;
+      k.n = 0u; k.w = 0.0f; k.info = 0u;
+      const uint32_t ch = live && a < C ? child[a] : MNK_PUCT_NONE;
+      if (ch != 0u && ch != MNK_PUCT_NONE) k = node[min((int)ch, nodes - 1)];
+      return k;
+    };
+    auto count = [&](int a, int keep) {
+      const MnkPuctNode k = kid(a);
+      const uint32_t pf = MNK_PUCT_PROOF(k.info);
+      return (keep == 1 && pf != 1u) || (keep == 2 && pf == 3u) ? 0u : k.n;
+    };
+    bool win = false;
+    for (int a = lane; a < C; a += 64) win |= MNK_PUCT_PROOF(kid(a).info) == 1u;
+    int keep = __ballot(win) ? 1 : 2;
+    uint32_t maxn = 0u, tot = 0u;
+    for (int t = 0; t < 2 && !maxn; ++t) {  // the adjusted counts; were they all zero, the raw ones
+      if (t) keep = 0;
+      tot = 0u;
+      for (int a = lane; a < C; a += 64) {
+        const uint32_t na = count(a, keep);
+        maxn = max(maxn, na);
+        tot += na;
+      }
+#pragma unroll
+      for (int off = 32; off; off >>= 1) {
+        maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
+        tot += (uint32_t)__shfl_xor((int)tot, off, 64);
+      }
+    }
+    if (visits)
+      for (int a = lane; a < C; a += 64) visits[i * C + a] = (int32_t)count(a, keep);
+    int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells
+    if (maxn)
+      mnk_pick_by_visits(C, x, temperature == 1 && !deterministic, maxn, tot, lane, [&](int a) { return count(a, keep); },
+                         move);
+    if (lane == 0) {
+      const uint32_t pf = MNK_PUCT_PROOF(node[0].info);  // from the view of the side that is NOT to move
+      actions[i] = move;
+      if (root_value) root_value[i] = pf ? (float)((int)pf - 2) : __fdiv_rn(-node[0].w, (float)node[0].n);
+      if (proof) proof[i] = pf ? (int8_t)((int)pf - 2) : (int8_t)MNK_PROOF_UNKNOWN;
+    }
+    return;
+  }
   uint32_t maxn = 0u, tot = 0u;
   for (int a = lane; a < C; a += 64) {
     const uint32_t ch = live ? child[a] : MNK_PUCT_NONE;
@@ -484,7 +567,10 @@ __device__ __forceinline__ void puct_env_root(MnkEnv<NW>& e, const uint32_t* roo
 // earlier slots whose path runs through the walk's node v, slot l's path and depth are lane l's epath / edepth, and a
 // child's vl = how many slots of `share` go on to it.  nodes0 = the node count when the round began: a node of a higher
 // id that is not terminal has no evaluation yet, and reaching it ends the walk without a leaf.
-template <int NW, int CN, int CK, bool VL>
+// SOLVER: a child that is proven LOSS (a move proven to lose for the player making it) is a candidate only when every
+// child is -- `bc`, the class of the best cell so far (1: not such a child), orders before the score -- and the walk ends
+// in a child with a proof as it ends in a terminal one; the new pending state carries the proof in the term's bits.
+template <int NW, int CN, int CK, bool VL, bool SOLVER = false>
 __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, int I, float c, MnkPuctNode* node,
                                               const float* prior, uint16_t* child, uint16_t* path, int& nodes, int& d,
                                               int lane, int nodes0 = 0, uint32_t share = 0u,
@@ -509,16 +595,19 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
     const uint16_t* cl = child + (int64_t)v * C;
     float best = 0.0f;
     int ba = 0x7fffffff;
+    [[maybe_unused]] int bc = 0;
     for (int a = lane; a < C; a += 64) {
       const uint32_t ch = cl[a];
       if (ch == MNK_PUCT_NONE) continue;
       uint32_t na = 0u;
       float wa = 0.0f;
+      [[maybe_unused]] int cls = 1;
       if (ch) {
         const int kk = min((int)ch, nodes - 1);
         const MnkPuctNode k = node[kk];
         na = k.n;
         wa = k.w;
+        if constexpr (SOLVER) cls = MNK_PUCT_PROOF(k.info) != 3u;
         if (VL && share) {
           uint32_t vl = 0u;  // (nx is 0, never a child's id, for a slot that is not in `share`)
 #pragma unroll
@@ -529,7 +618,13 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
       }
       const float q = na ? __fdiv_rn(wa, (float)na) : 0.0f;
       const float s = __fadd_rn(q, __fdiv_rn(__fmul_rn(__fmul_rn(c, pr[a]), sq), (float)(1u + na)));
-      if (ba == 0x7fffffff || s > best) {  // (a rises: ">" keeps the lowest cell of a tie)
+      if constexpr (SOLVER) {
+        if (ba == 0x7fffffff || cls > bc || (cls == bc && s > best)) {
+          best = s;
+          ba = a;
+          bc = cls;
+        }
+      } else if (ba == 0x7fffffff || s > best) {  // (a rises: ">" keeps the lowest cell of a tie)
         best = s;
         ba = a;
       }
@@ -538,7 +633,15 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
     for (int off = 32; off; off >>= 1) {
       const float ob = __shfl_xor(best, off, 64);
       const int oa = __shfl_xor(ba, off, 64);
-      if (oa != 0x7fffffff && (ba == 0x7fffffff || ob > best || (ob == best && oa < ba))) {
+      if constexpr (SOLVER) {
+        const int oc = __shfl_xor(bc, off, 64);
+        if (oa != 0x7fffffff &&
+            (ba == 0x7fffffff || oc > bc || (oc == bc && (ob > best || (ob == best && oa < ba))))) {
+          best = ob;
+          ba = oa;
+          bc = oc;
+        }
+      } else if (oa != 0x7fffffff && (ba == 0x7fffffff || ob > best || (ob == best && oa < ba))) {
         best = ob;
         ba = oa;
       }
@@ -553,6 +656,7 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
       if (lane == 0) {
         MnkPuctNode k;
         k.n = 0u; k.w = 0.0f; k.info = (uint32_t)a | (term << 16) | ((uint32_t)v << 18);
+        if constexpr (SOLVER) k.info |= term << 12;
         node[nodes] = k;
         child[(int64_t)v * C + a] = (uint16_t)nodes;
         path[d] = (uint16_t)nodes;
@@ -562,8 +666,8 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
     }
     const int k = min((int)ch, nodes - 1);
     if (lane == 0) path[d] = (uint16_t)k;
-    const uint32_t term = MNK_PUCT_TERM(node[k].info);
-    if (term) return 1u | (term << 1);  // an existing terminal child: the leaf again
+    const uint32_t term = SOLVER ? MNK_PUCT_PROOF(node[k].info) : MNK_PUCT_TERM(node[k].info);  // (a constant choice)
+    if (term) return 1u | (term << 1);  // an existing terminal child (SOLVER: a proven one): the leaf again
     if (VL) {
       if (k >= nodes0) return 0u;  // created in this round: not evaluated yet
       share = (uint32_t)__ballot(nxt == (uint32_t)k);
@@ -751,6 +855,105 @@ k_puct_step_leaves(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, c
   if (lane == 0) hdr[0] = (uint32_t)nodes;
 }
 
+// ------------------------------------------------------------------ a round that proves wins, draws and losses
+// k_puct_step_leaves (for any number of leaves, 1 included) with the solver's parts of puct_backup, puct_walk and
+// puct_move compiled in: the backups prove what they can along their paths, a root that is proven selects nothing (its
+// slots are void, as those of a full tree), and the move is made from the adjusted counts.  The rule: include/mnk_hip.h,
+// mnk_puct_step_solver.
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_puct_step_solver(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, const void* priors, int priors_dtype,
+                   const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
+                   const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
+                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
+                   float* root_value, int8_t* proof) {
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  const int C = g.C, NWg = g.NW;
+  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, leaves);
+  unsigned char* row = ws + i * L.row;
+  uint32_t* hdr = (uint32_t*)row;
+  const uint32_t* root = (const uint32_t*)(row + L.root);
+  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
+  float* prior = (float*)(row + L.prior);
+  uint16_t* child = (uint16_t*)(row + L.child);
+  uint32_t* pos = lds_pos[wave];
+  // slot j's {depth, state}, leaf planes and path (slot 0: the header's, `leaf`, `path`)
+  auto slot_ds = [&](int j) { return j ? (uint32_t*)(row + L.xhdr) + 2 * (j - 1) : hdr + 1; };
+  auto slot_leaf = [&](int j) { return (uint32_t*)(row + (j ? L.xleaf + 8 * (int64_t)NWg * (j - 1) : L.leaf)); };
+  auto slot_path = [&](int j) { return (uint16_t*)(row + (j ? L.xpath + L.pstride * (j - 1) : L.path)); };
+  // (clamped: a workspace that mnk_puct_begin_leaves did not set up cannot send a store outside the row)
+  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
+  const bool live = hdr[3] != 0u;
+
+  // ---- the backups of the pending evaluations, in slot order
+  for (int j = 0; j < leaves; ++j) {
+    const uint32_t* ds = slot_ds(j);
+    const int depth = (int)min(ds[0], (uint32_t)I);
+    const uint32_t state = ds[1];
+    if (!(state & 1u)) continue;
+    const uint32_t* leafp = slot_leaf(j);
+    for (int q = lane; q < 2 * NW; q += 64) {
+      const int pl = q >= NW, w = q - (pl ? NW : 0);
+      pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
+    }
+    row_wave_sync();
+    puct_backup<NW, CN, true>(g, pos, slot_path(j), node, prior, child, nodes, depth, state, priors, priors_dtype, values,
+                              values_dtype, i * leaves + j, lane);
+  }
+
+  if (last) {
+    puct_move<true>(C, node, child, nodes, live, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, i,
+                    actions, visits, root_value, lane, proof);
+    return;
+  }
+
+  // ---- the selections
+  const int nodes0 = nodes;
+  const uint16_t* epath = slot_path(min(lane, leaves - 1));  // lane l < leaves: slot l's path
+  int edepth = 0;                                            // and, once it has selected, its leaf's depth
+  uint32_t active = 0u;                                      // the slots of this round that have a leaf
+  bool open = live;                                          // no slot was void yet
+  if (MNK_PUCT_PROOF(node[0].info)) open = false;            // a proven root: nothing left to search
+  for (int j = 0; j < leaves; ++j) {
+    int d = 0;
+    uint32_t nstate = 0u;
+    uint16_t* path = slot_path(j);
+    MnkEnv<NW> e;
+    if (open && nodes <= I) {
+      puct_env_root<NW>(e, root, NWg);
+      nstate = puct_walk<NW, CN, CK, true, true>(g, e, I, c, node, prior, child, path, nodes, d, lane, nodes0, active,
+                                                 epath, edepth);
+    }
+    if (nstate) {
+      active |= 1u << j;
+      if (lane == j) edepth = d;
+    } else {
+      d = 0;
+      open = false;
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
+        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
+      }
+      path[0] = 0;
+      uint32_t* ds = slot_ds(j);
+      ds[0] = (uint32_t)d;
+      ds[1] = nstate;
+    }
+    row_wave_sync();
+    uint32_t* leafp = slot_leaf(j);
+    for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
+    row_write_view<NW, CN>(g, pos, d & 1, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
+    row_wave_sync();  // (the next slot's walk reads this one's node, child entry and path; its write-out reuses pos)
+  }
+  if (lane == 0) hdr[0] = (uint32_t)nodes;
+}
+
 // ------------------------------------------------------------------ the entry points
 // what the four pairs of entry points share: the host checks (before anything is enqueued) and the launch.  leaves = 0
 // stands for the entry point without the argument: today's kernels, one leaf.
@@ -814,7 +1017,7 @@ static int puct_step(void* workspace, int64_t N, int m, int n, int k, int iterat
                      int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
                      uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                      int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
-                     int32_t* visits, float* root_value, void* stream) {
+                     int32_t* visits, float* root_value, void* stream, bool solver = false, int8_t* proof = nullptr) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
@@ -828,7 +1031,12 @@ static int puct_step(void* workspace, int64_t N, int m, int n, int k, int iterat
   if (N == 0) return MNK_OK;
   const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
   hipStream_t s = (hipStream_t)stream;
-  if (leaves)
+  if (solver)
+    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step_solver), grid, block, 0, s, g, (unsigned char*)workspace, N,
+                                       iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
+                                       temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs,
+                                       leaf_dtype, leaf_mask, actions, visits, root_value, proof));
+  else if (leaves)
     MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step_leaves), grid, block, 0, s, g, (unsigned char*)workspace, N,
                                        iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
                                        temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs,
@@ -838,7 +1046,7 @@ static int puct_step(void* workspace, int64_t N, int m, int n, int k, int iterat
                                        priors, priors_dtype, values, values_dtype, c, last, temperature, seed, seed_dev,
                                        step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions,
                                        visits, root_value));
-  return mnk_launch_status(leaves ? "puct_step_leaves" : "puct_step");
+  return mnk_launch_status(solver ? "puct_step_solver" : leaves ? "puct_step_leaves" : "puct_step");
 }
 
 extern "C" {
@@ -891,6 +1099,16 @@ int mnk_puct_step_leaves(void* workspace, int64_t N, int m, int n, int k, int it
   return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
                    temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
                    actions, visits, root_value, stream);
+}
+int mnk_puct_step_solver(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                         int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                         uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                         int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                         int32_t* visits, float* root_value, int8_t* proof, void* stream) {
+  if (!leaves) return MNK_EINVAL;
+  return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
+                   temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
+                   actions, visits, root_value, stream, true, proof);
 }
 
 }  // extern "C"

@@ -25,6 +25,7 @@ SP_NEED_OPP, SP_WAS_RESET = 1, 2
 STREAM_MOVE, STREAM_OPP, STREAM_SIDE, STREAM_SAMPLE, STREAM_PLAYOUT, STREAM_SEARCH, STREAM_SELFPLAY = 0, 1, 2, 3, 4, 5, 6
 STREAM_NOISE = 7  # MNK_STREAM_NOISE: the Dirichlet noise on the PUCT player's root priors (mnk_puct_root_noise)
 Z_UNKNOWN = -128  # MNK_Z_UNKNOWN: the outcome of a ring record whose game is still running
+PROOF_UNKNOWN = -128  # MNK_PROOF_UNKNOWN: the `proof` of a root that mnk_puct_step_solver has not proven
 PLAYOUTS_MAX = 4096  # MNK_PLAYOUTS_MAX: the largest playout count of mnk_sample_playouts
 SEARCH_ITERS_MAX = 2048  # MNK_SEARCH_ITERS_MAX: the largest iteration budget of mnk_sample_search
 SEARCH_PLAYOUTS_MAX = 256  # MNK_SEARCH_PLAYOUTS_MAX: the largest playout count per leaf of mnk_sample_search
@@ -109,6 +110,9 @@ SIGNATURES = {
     "mnk_puct_rebase_leaves": [_vp, _i, _i64, _i, _i, _i, _i, _i, _i, _vp, _vp, _i, _vp, _vp, _vp],
     "mnk_puct_step_leaves": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i,
                              _vp, _i, _vp, _vp, _vp, _vp, _vp],
+    # mnk_puct_step_leaves with proofs of wins, draws and losses: its arguments, then proof (int8 [N]) before the stream
+    "mnk_puct_step_solver": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i,
+                             _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     # priors, priors dtype, mask, N, C, leaves, alpha, eps, then seed, seed_dev, step, step_dev, env_id0, out (f32
     # [N * leaves][C]), stream
     "mnk_puct_root_noise": [_vp, _i, _vp, _i64, _i, _i, _f, _f, _u64, _vp, _u64, _vp, _i64, _vp, _vp],

@@ -316,11 +316,21 @@ class PUCTSearchPolicy(Policy):
     (``mnk_puct_step_leaves``): the evaluator is called ``evaluations_per_act = iterations / L + 1`` times on batches of
     ``N * L`` rows, rows ``i * L .. i * L + L - 1`` being row i's.  The first call is still the roots (row ``i * L``; the
     other rows of that call, like every slot a round could not fill, repeat the root and are ignored).  With ``reuse`` the
-    workspace's ``tree_nodes - 1`` must be a multiple of L as well (the default is)."""
+    workspace's ``tree_nodes - 1`` must be a multiple of L as well (the default is).
+
+    ``solver=True`` proves wins, draws and losses in the tree ("MCTS-Solver"; the rule: include/mnk_hip.h,
+    mnk_puct_step_solver): every node carries a proof, a move that ends the game is proven when its node is created, and
+    the backup of a proven leaf proves what follows from it along the path -- a node with a winning move is lost for the
+    player who moved into it, a node all of whose moves are proven is a win or a draw.  The selection leaves out moves
+    proven to lose, a proven child costs no evaluation, a proven root stops searching, the visit counts handed out drop
+    the proven losses (or everything but the proven wins), and the root value of a proven root is exactly +1, 0 or -1.
+    Every step is then ``mnk_puct_step_solver``, at any ``leaves``, with or without ``reuse`` (a kept subtree keeps its
+    proofs) and ``root_noise``; the evaluator sees the same batches.  With the solver the visits no longer sum to the
+    number of iterations.  ``False`` (the default): the search above, launch for launch."""
 
     def __init__(self, k: int, model=None, evaluator=None, iterations: int = 256, c: float = 1.25, temperature: int = 0,
                  leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None, leaves: int = 1,
-                 root_noise=None):
+                 root_noise=None, solver: bool = False):
         if (model is None) == (evaluator is None):
             raise ValueError("PUCTSearchPolicy needs exactly one of model and evaluator")
         self.k = int(k)
@@ -359,6 +369,7 @@ class PUCTSearchPolicy(Policy):
                 raise ValueError("tree_nodes is the workspace of a search that keeps its tree: it needs reuse=True")
             self.tree_nodes = self.iterations + 1
         self.root_noise = self._checked_root_noise(root_noise)
+        self.solver = bool(solver)
         self._bufs = None  # (key, workspace, leaf_obs, leaf_mask, noised priors or None)
 
     @staticmethod
@@ -413,20 +424,26 @@ class PUCTSearchPolicy(Policy):
             self._bufs[1].zero_()
 
     def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, visits=None, root_value=None,
-            carried=None) -> torch.Tensor:
+            carried=None, proof=None) -> torch.Tensor:
         """``visits``: optional int32 ``[B, m*n]`` tensor that receives each row's root visit counts (an AlphaZero policy
         target; they sum to ``iterations`` on a row with a legal cell, to the carried visits plus ``iterations`` on a row
         that kept its tree); ``root_value``: optional float32 ``[B]`` tensor that receives the root's mean value for the
         side to move; ``carried`` (``reuse=True``): optional int32 ``[B, 2]`` tensor that receives {nodes kept, the visit
-        count of the root that was kept} of each row, {0, 0} where the row started fresh"""
+        count of the root that was kept} of each row, {0, 0} where the row started fresh; ``proof`` (``solver=True``):
+        optional int8 ``[B]`` tensor that receives +1, 0 or -1 where the root is a proven win, draw or loss for the side to
+        move and ``mnk_hip.PROOF_UNKNOWN`` elsewhere.  With ``solver=True`` ``visits`` are the adjusted counts (the proven
+        wins alone when there is one, else all but the proven losses) and do not sum to ``iterations``, and
+        ``root_value`` is exactly +1, 0 or -1 on a proven root"""
         observation = _canonical_observation(obs)
         b, _, m, n = observation.shape
         dev = observation.device
         if carried is not None and not self.reuse:
             raise ValueError("carried is an output of a search that keeps its tree: it needs reuse=True")
+        if proof is not None and not self.solver:
+            raise ValueError("proof is an output of a search that proves its tree: it needs solver=True")
         for name, t, shape, dtype in (("visits", visits, (b, m * n), torch.int32),
                                       ("root_value", root_value, (b,), torch.float32),
-                                      ("carried", carried, (b, 2), torch.int32)):
+                                      ("carried", carried, (b, 2), torch.int32), ("proof", proof, (b,), torch.int8)):
             if t is not None and (t.shape != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
                 raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {shape} tensor on {dev}")
         actions = torch.empty(b, dtype=torch.long, device=dev)
@@ -436,7 +453,9 @@ class PUCTSearchPolicy(Policy):
             I, k, code = self.iterations, self.k, self._leaf_code
             cap = self.tree_nodes - 1  # the workspace's layout parameter: node capacity - 1 (= I without reuse)
             # leaves = 1 stays on the entry points without the argument (the same results either way: include/mnk_hip.h)
-            sfx, lv = ("_leaves", (self.leaves,)) if self.leaves > 1 else ("", ())
+            # (the solver's step takes `leaves` always, and the workspace the *_leaves entry points set up)
+            sfx, lv = ("_leaves", (self.leaves,)) if self.leaves > 1 or self.solver else ("", ())
+            step, out = ("mnk_puct_step_solver", (mnk_hip.ptr(proof),)) if self.solver else ("mnk_puct_step" + sfx, ())
             if self.reuse:
                 mnk_hip.call("mnk_puct_rebase" + sfx, mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k,
                              cap, self.tree_nodes - I, *lv, mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code,
@@ -452,11 +471,11 @@ class PUCTSearchPolicy(Policy):
                     mnk_hip.call("mnk_puct_root_noise", mnk_hip.ptr(priors), pcode, mnk_hip.ptr(leaf_mask), b, m * n,
                                  self.leaves, *self.root_noise, *self._sampler.block()[:5], mnk_hip.ptr(noised), stream)
                     priors, pcode = noised, mnk_hip.LOGITS_F32
-                mnk_hip.call("mnk_puct_step" + sfx, mnk_hip.ptr(ws), b, m, n, k, cap, *lv, mnk_hip.ptr(priors), pcode,
+                mnk_hip.call(step, mnk_hip.ptr(ws), b, m, n, k, cap, *lv, mnk_hip.ptr(priors), pcode,
                              mnk_hip.ptr(values), vcode, self.c, 1 if last else 0, self.temperature,
                              *self._sampler.block(deterministic), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask),
                              mnk_hip.ptr(actions) if last else None, mnk_hip.ptr(visits) if last else None,
-                             mnk_hip.ptr(root_value) if last else None, stream)
+                             mnk_hip.ptr(root_value) if last else None, *out, stream)
         self._sampler.advance()
         return actions
 

@@ -20,6 +20,11 @@ calls per ply on batches of ``num_envs * L`` rows.
 ``reuse=True`` keeps every row's search tree from ply to ply (``PUCTSearchPolicy(reuse=True)``): the next root that the step
 kernel writes is what the next search matches its stored tree against, so the subtree of the move that was played -- drawn
 by temperature or not -- is carried over and a game that was reset starts fresh, with no word from the host.
+
+``solver=True`` searches with exact proofs of wins, draws and losses (``PUCTSearchPolicy(solver=True)``, the rule:
+include/mnk_hip.h, mnk_puct_step_solver).  The step kernel is the same: it plays from, and records, the visits it is
+given, which are then the adjusted ones -- the ring's policy targets carry no count of a move proven to lose, and only the
+proven wins where there is one.
 """
 from typing import Dict
 
@@ -34,7 +39,8 @@ from selfplay.policy import PUCTSearchPolicy
 class SearchSelfPlay:
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  c: float = 1.25, temp_plies: int = None, capacity: int = None, seed=None, leaf_dtype=torch.float32,
-                 device="cuda", reuse: bool = False, tree_nodes: int = None, leaves: int = 1, root_noise=None):
+                 device="cuda", reuse: bool = False, tree_nodes: int = None, leaves: int = 1, root_noise=None,
+                 solver: bool = False):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -51,7 +57,7 @@ class SearchSelfPlay:
         # GPU)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
                                        temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=reuse, tree_nodes=tree_nodes,
-                                       leaves=leaves, root_noise=root_noise)
+                                       leaves=leaves, root_noise=root_noise, solver=solver)
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
