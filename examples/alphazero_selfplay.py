@@ -8,9 +8,12 @@ restored, sharded and captured without changing a draw), ``--noise off`` plays w
 tree from ply to ply (the subtree of the move that was played starts the next search; the roots' priors, and so the noise,
 are renewed every ply) and drops the trees after each training round, since their statistics are the old weights'.
 ``--solver`` proves wins, draws and losses inside the search (``SearchSelfPlay(solver=True)``): the policy targets drop
-the moves proven to lose.
+the moves proven to lose.  ``--search gumbel`` searches with a Gumbel root (``SearchSelfPlay(gumbel=m)``): the Gumbel draw
+is the exploration (no root noise, no temperature) and the targets are the improved policy; the default ``puct`` is the
+run it was.
 
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse] [--solver]
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --search gumbel --iterations 16
 """
 import argparse
 import os
@@ -77,9 +80,11 @@ def greedy(net):
 
 
 def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates=40, batch=512, lr=2e-3, seed=0,
-          noise=True, reuse=False, leaves=1, solver=False, log=print):
+          noise=True, reuse=False, leaves=1, solver=False, search="puct", considered=4, log=print):
     """self-play and training rounds; returns the network.  ``noise``: True / "wrapper" (``RootNoise``), "builtin" (the
-    search's own root noise, same alpha and eps) or False / "off" (none)"""
+    search's own root noise, same alpha and eps) or False / "off" (none).  ``search``: "puct", or "gumbel" -- a Gumbel
+    root over ``considered`` moves (``SearchSelfPlay(gumbel=...)``): the exploration is the Gumbel draw and the targets are
+    the improved policy, so ``noise`` is not used, and a small ``iterations`` (16) is what it is meant for"""
     entry.build()
     from selfplay.policy import model_evaluator
     from selfplay.search_selfplay import SearchSelfPlay
@@ -90,14 +95,17 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
     net = PolicyValueNet(C).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=lr)
     evaluator = model_evaluator(net)
-    noise = {True: "wrapper", False: "off"}.get(noise, noise)
+    if search not in ("puct", "gumbel"):
+        raise ValueError(f"search must be 'puct' or 'gumbel', got {search!r}")
+    noise = "off" if search == "gumbel" else {True: "wrapper", False: "off"}.get(noise, noise)
     if noise not in ("wrapper", "builtin", "off"):
         raise ValueError(f"noise must be 'wrapper', 'builtin' or 'off', got {noise!r}")
     if noise == "wrapper":
         evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
                         capacity=2 * C, seed=seed, reuse=reuse, leaves=leaves, solver=solver,
-                        root_noise=(0.3, 0.25) if noise == "builtin" else None)
+                        root_noise=(0.3, 0.25) if noise == "builtin" else None,
+                        gumbel=considered if search == "gumbel" else None)
     assert sp.policy.evaluations_per_act == iterations // leaves + 1
     plies = C if plies is None else plies
     gen = torch.Generator(device=dev)
@@ -152,10 +160,14 @@ def main():
                          "iterations / leaves + 1 batches of envs * leaves positions per move")
     ap.add_argument("--solver", action="store_true",
                     help="prove wins, draws and losses in the search tree; proven losses leave the policy targets")
+    ap.add_argument("--search", choices=("puct", "gumbel"), default="puct",
+                    help="gumbel: a Gumbel root with Sequential Halving and improved-policy targets (no root noise; try "
+                         "--iterations 16)")
+    ap.add_argument("--considered", type=int, default=4, help="--search gumbel: the root moves Sequential Halving considers")
     a = ap.parse_args()
     m, n, k = (int(x) for x in a.board.lower().split("x"))
     net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed,
-                noise=a.noise, reuse=a.reuse, leaves=a.leaves, solver=a.solver)
+                noise=a.noise, reuse=a.reuse, leaves=a.leaves, solver=a.solver, search=a.search, considered=a.considered)
     for name, res in validate(net, m, n, k).items():
         print(f"vs {name}: win {res['win_rate']:.3f} loss {res['loss_rate']:.3f} draw {res['draw_rate']:.3f} "
               f"score {res['score_rate']:.3f}")

@@ -125,6 +125,7 @@ extern "C" {
 #define MNK_STREAM_SEARCH 5  /* the random plies of the tree-search player's playouts (mnk_sample_search) */
 #define MNK_STREAM_SELFPLAY 6 /* the move of a search self-play ply (mnk_search_selfplay_step) */
 #define MNK_STREAM_NOISE 7    /* the Dirichlet noise on the PUCT player's root priors (mnk_puct_root_noise) */
+#define MNK_STREAM_GUMBEL 8   /* the Gumbel variables of the PUCT player's Gumbel root (mnk_puct_gumbel_root) */
 
 int mnk_abi_version(void);
 /* Developer knobs (MNK_ROLLOUT_PAIR, MNK_ROLLOUT_FORM, MNK_JIT, MNK_ROLLOUT_SADDR, MNK_EMIT_ENVS, MNK_EMIT_THREADS: A/B
@@ -539,6 +540,54 @@ int mnk_puct_step_solver(void* workspace, int64_t N, int m, int n, int k, int it
                          uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                          int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                          int32_t* visits, float* root_value, int8_t* proof, void* stream);
+/* The search above with a GUMBEL ROOT ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022;
+ * optional: a search that never calls these is the search above).  One Gumbel variable per root move, the budget spent on
+ * the `considered` best moves by Sequential Halving, the survivor played -- an exact sample from the improved policy --
+ * and that policy, pi' = softmax(ln P + sigma(completed q)), handed out as the training target.  Gumbel applies at the
+ * root only: below the root the walk is mnk_puct_step's, backup included, bit for bit ("Gumbel root, PUCT elsewhere").
+ * The workspace is that of mnk_puct_begin_leaves with leaves = 1 (any other `leaves` is MNK_EINVAL).  One act() =
+ * mnk_puct_begin_leaves, evaluation 0, mnk_puct_gumbel_root, I times mnk_puct_step_gumbel with last = 0 and one with
+ * last = 1, an evaluation before each; the table is uploaded once per (considered, I).
+ * Parameters: considered = m in [1, MNK_PUCT_CONSIDERED_MAX]; c_visit (f32, >= 0; the paper's 50); c_scale (f32, >= 0;
+ * 0.5 here where the paper has 1.0: the paper's q lies in [0, 1], this q in [-1, 1] = 2 q_paper - 1, and the constant
+ * shift cancels in every argmax and softmax below, so 0.5 * q is the paper's 1.0 * q_paper); gumbel_scale (f32, >= 0;
+ * 1: the sample, 0: the whole act is deterministic).
+ *   the schedule (host only, no GPU): mnk_puct_gumbel_schedule fills out u16 [considered + 1][iterations].  Row m' is the
+ *     sequence of considered visits of a root with m' moves to consider.  m' <= 1: 0, 1, 2, ...  Otherwise, with L2 =
+ *     ceil(log2 m'), visits[0 .. m') = 0 and nc = m', repeat until the row holds I entries: extra = max(1, floor(I /
+ *     (L2 * nc))); `extra` times over, append visits[0 .. nc) and then add 1 to each of them; nc = max(2, nc / 2).  The row
+ *     is truncated to I entries.  (m' = 4, I = 8: 0 0 0 0 1 1 2 2.)
+ *   the prep launch: mnk_puct_gumbel_root reads evaluation 0's priors [N][C] (f32 / bf16), mask (u8, non-zero = free) and
+ *     values [N] and writes the caller-owned gscore f32 [N][C] and vroot f32 [N]; the evaluator's tensors are never
+ *     written.  For a free cell a of row i, C4 = C rounded up to a multiple of 4, all arithmetic f64 with the full-
+ *     precision logarithm:  P~_a = max(P_a, 2^-126),  l_a = ln((double)P~_a),  x_a = word a & 3 of the Philox block
+ *     (step [+ *step_dev]) * (C4 / 4) + (a >> 2) of stream MNK_STREAM_GUMBEL keyed by (seed [or *seed_dev], env_id0 + i),
+ *     U_a = (x_a + 0.5) * 2^-32,  g_a = -ln(-ln U_a),  gscore[a] = fl32(gumbel_scale * g_a + l_a)  (the product rounded,
+ *     then the sum).  An occupied cell gets -inf.  vroot[i] = the root's value, widened to f32 exactly.
+ *   root selection in simulation t = n_root - 1: F = the root's free cells, m' = min(m, F), v* = table[m'][t].  A root
+ *     child has q_a = fdiv(w_a, (float)n_a), and maxn = the largest n_a.  The candidates are the free cells with
+ *     n_a = v*; if there is none (it cannot happen on a fresh tree), all free cells.  A cell's key is gscore[a] when
+ *     n_a = 0, else fadd(gscore[a], fmul(fmul(fadd(c_visit, (float)maxn), c_scale), q_a)), every operation correctly
+ *     rounded, no contraction.  The maximal key wins, ties to the lowest cell.  From the chosen child on, the walk above.
+ *   the move, after the last backup: the free cell of maximal key among those with n_a = maxn, ties to the lowest cell.
+ *     A row without a legal cell draws as mnk_puct_step does.  visits (the raw n_a) and root_value are as above.
+ *   policy (optional) f32 [N][C], the improved policy, in f64 (q_a above, widened):  pi_a = P~_a / sum over F of P~;  over
+ *     the visited free cells Sv = sum pi_a, Sq = sum pi_a * q_a, Ns = sum n_a;  v_mix = (vroot + Ns * Sq / Sv) / (1 + Ns),
+ *     or vroot when Sv = 0;  qhat_a = q_a if n_a > 0, else v_mix;  K = ((double)c_visit + maxn) * (double)c_scale;
+ *     y_a = l_a + K * qhat_a;  policy_a = fl32(exp(y_a - max y) / sum exp(y - max y)).  An occupied cell gets 0, a row
+ *     without a free cell is all zeros.  P~ is the root's prior as the backup of evaluation 0 stored it.
+ * Every host check runs before anything is enqueued. */
+#define MNK_PUCT_CONSIDERED_MAX 1024
+int mnk_puct_gumbel_schedule(int considered, int iterations, uint16_t* out);
+int mnk_puct_gumbel_root(const void* priors, int priors_dtype, const void* mask, const void* values, int values_dtype,
+                         int64_t N, int C, float gumbel_scale, uint64_t seed, const uint64_t* seed_dev, uint64_t step,
+                         const uint64_t* step_dev, int64_t env_id0, float* gscore, float* vroot, void* stream);
+int mnk_puct_step_gumbel(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                         int priors_dtype, const void* values, int values_dtype, float c, int last, int considered,
+                         float c_visit, float c_scale, const uint16_t* table, const float* gscore, const float* vroot,
+                         uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                         int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                         int32_t* visits, float* root_value, float* policy, void* stream);
 /* Dirichlet root noise for the search above (optional): one launch between evaluation 0 and the first mnk_puct_step[_leaves]
  * that mixes eta ~ Dirichlet(alpha) over each root's free cells into a copy of the root's priors.  priors (f32 / bf16,
  * MNK_LOGITS_*) and mask (u8, non-zero = free) are evaluation 0's [N * leaves][C] tensors; row i's root is batch row
@@ -594,6 +643,17 @@ int mnk_search_selfplay_step(uint64_t* planes, uint32_t* meta, int64_t N, int m,
                              const uint64_t* step_dev, int64_t env_id0, int64_t T, uint64_t* ring_planes,
                              uint16_t* ring_visits, int8_t* ring_z, void* obs, int obs_dtype, uint8_t* legal_mask,
                              int64_t* stats, int32_t* err, void* stream);
+/* mnk_search_selfplay_step for a search that hands out its move and a policy target (mnk_puct_step_gumbel): the same
+ * launch with two differences.  The move of row i is actions[i] (int64 [N]) instead of a draw from the visits -- no Philox
+ * word is used, so there is no seed or env_id0: an action outside [0, C) sets MNK_ERR_ACTION_RANGE, one on an occupied
+ * cell MNK_ERR_ILLEGAL_MOVE, and the env is then not played, exactly as a row of MNK_ERR_VISITS above.  The ring's u16
+ * visits of a free cell are min(65535, rint(fl32(policy_a * 65535))) (policy f32 [N][C]; ties to even; 0 for anything
+ * not above 0), so the ring format and mnk_search_gather stay as they are: the gather's n / sum n gives the target back
+ * to 1.5e-5.  Outcome labels, resets, stats, the next root and every other argument are as above. */
+int mnk_search_selfplay_step_moves(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, const float* policy,
+                                   const int64_t* actions, uint64_t step, const uint64_t* step_dev, int64_t T,
+                                   uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* obs, int obs_dtype,
+                                   uint8_t* legal_mask, int64_t* stats, int32_t* err, void* stream);
 /* A minibatch of ring records: sample b is the flat id idx[b] = t*N + i (negative ids wrap, an id outside [0, T*N) sets
  * MNK_ERR_ACTION_RANGE as in mnk_gather_obs and gives zero planes, policy, value and weight) under symmetry s = sym[b]
  * (sym int8 [B] or NULL = the identity).  Output cell (r, c) reads source cell (r', c'): start from (r, c); if s & 4,

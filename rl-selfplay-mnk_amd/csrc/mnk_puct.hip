@@ -560,6 +560,174 @@ __device__ __forceinline__ void puct_env_root(MnkEnv<NW>& e, const uint32_t* roo
   e.meta = (uint32_t)stones << 1;
 }
 
+// ------------------------------------------------------------------ the Gumbel root (k_puct_step_gumbel only)
+// What the root of row i reads besides the tree: its row of gscore (mnk_puct_gumbel_root), the table of considered visits
+// (mnk_puct_gumbel_schedule, [considered + 1][I]) and the constants of sigma.
+struct MnkPuctGumbel {
+  const float* gs;
+  const uint16_t* table;
+  int considered;
+  float c_visit, c_scale;
+};
+
+// The root's child of maximal key among the free cells of `want` visits -- LAST: of the most visits; else of
+// table[min(considered, F)][n_root - 1] visits -- or, when no free cell has that count, among all free cells; ties to the
+// lowest cell, 0x7fffffff for a root without a free cell.  Wave-uniform.  Two scans of the root's child row in the access
+// shape of the scoring loop (cells over the lanes, a child's record gathered): the first for F and the most visits, the
+// second for the two maxima, each reduced by __shfl_xor.
+template <bool LAST>
+__device__ __forceinline__ int puct_gumbel_pick(int C, int I, const MnkPuctNode* node, const uint16_t* cl, int nodes,
+                                                const MnkPuctGumbel& gm, int lane, uint32_t* maxn_out = nullptr) {
+  uint32_t F = 0u, maxn = 0u;
+  for (int a = lane; a < C; a += 64) {
+    const uint32_t ch = cl[a];
+    if (ch == MNK_PUCT_NONE) continue;
+    ++F;
+    if (ch) maxn = max(maxn, node[min((int)ch, nodes - 1)].n);
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    F += (uint32_t)__shfl_xor((int)F, off, 64);
+    maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
+  }
+  if (maxn_out) *maxn_out = maxn;
+  uint32_t want = maxn;
+  if (!LAST) {  // (clamped: whatever the workspace holds, the read stays inside the table)
+    const int t = min((int)max(node[0].n, 1u) - 1, I - 1);
+    want = gm.table[(int64_t)min((uint32_t)gm.considered, F) * I + t];
+  }
+  const float sigma = __fmul_rn(__fadd_rn(gm.c_visit, (float)maxn), gm.c_scale);
+  float bk = 0.0f, ak = 0.0f;  // the best key among the cells of `want` visits / among all free cells
+  int ba = 0x7fffffff, aa = 0x7fffffff;
+  for (int a = lane; a < C; a += 64) {
+    const uint32_t ch = cl[a];
+    if (ch == MNK_PUCT_NONE) continue;
+    float key = gm.gs[a];
+    uint32_t na = 0u;
+    if (ch) {
+      const MnkPuctNode k = node[min((int)ch, nodes - 1)];
+      na = k.n;
+      if (na) key = __fadd_rn(key, __fmul_rn(sigma, __fdiv_rn(k.w, (float)na)));
+    }
+    if (na == want && (ba == 0x7fffffff || key > bk)) {  // (a rises: ">" keeps the lowest cell of a tie)
+      bk = key;
+      ba = a;
+    }
+    if (aa == 0x7fffffff || key > ak) {
+      ak = key;
+      aa = a;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const float ob = __shfl_xor(bk, off, 64), oa = __shfl_xor(ak, off, 64);
+    const int obc = __shfl_xor(ba, off, 64), oac = __shfl_xor(aa, off, 64);
+    if (obc != 0x7fffffff && (ba == 0x7fffffff || ob > bk || (ob == bk && obc < ba))) {
+      bk = ob;
+      ba = obc;
+    }
+    if (oac != 0x7fffffff && (aa == 0x7fffffff || oa > ak || (oa == ak && oac < aa))) {
+      ak = oa;
+      aa = oac;
+    }
+  }
+  return __builtin_amdgcn_readfirstlane(ba != 0x7fffffff ? ba : aa);
+}
+
+// a sum over the wave, the same value in every lane
+__device__ __forceinline__ double puct_wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
+
+// The move, the visits, the root value and the improved policy of row i, after its last backup (the rule:
+// include/mnk_hip.h, mnk_puct_step_gumbel).  The policy is f64: five passes over the root's cells (the sum of the clamped
+// priors; the visited cells' sums for v_mix; the maximum of y; the sum of exp(y - max); the store), every pass
+// recomputing a cell's terms from the tree -- the same operations on the same inputs give the same y each time -- and
+// reduced over the wave.  pr = the root's stored priors (node 0's row).
+__device__ __forceinline__ void puct_move_gumbel(int C, int I, const MnkPuctNode* node, const float* pr, const uint16_t* cl,
+                                                 int nodes, bool live, const MnkPuctGumbel& gm, float vroot, uint64_t seed,
+                                                 const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev,
+                                                 int64_t env_id0, int deterministic, int64_t i, int64_t* actions,
+                                                 int32_t* visits, float* root_value, float* policy, int lane) {
+  if (!live) {  // no legal cell: the draw over all C cells of mnk_puct_step, no visits, no policy
+    if (step_dev) step += *step_dev;
+    if (seed_dev) seed = *seed_dev;
+    const uint32_t x = deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(env_id0 + i), step, MNK_STREAM_SAMPLE);
+    for (int a = lane; a < C; a += 64) {
+      if (visits) visits[i * C + a] = 0;
+      if (policy) policy[i * C + a] = 0.0f;
+    }
+    if (lane == 0) {
+      actions[i] = (int)__umulhi(x, (uint32_t)C);
+      if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
+    }
+    return;
+  }
+  uint32_t maxn = 0u;
+  const int move = puct_gumbel_pick<true>(C, I, node, cl, nodes, gm, lane, &maxn);
+  if (lane == 0) {
+    actions[i] = move == 0x7fffffff ? 0 : move;
+    if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
+  }
+  if (!visits && !policy) return;
+  // a free cell's clamped prior, visit count and q (0 where it has no visit)
+  auto cell = [&](int a, double& p, uint32_t& na, double& q) {
+    const uint32_t ch = cl[a];
+    if (ch == MNK_PUCT_NONE) return false;
+    const float pa = pr[a];
+    p = (double)(pa > 0x1p-126f ? pa : 0x1p-126f);
+    na = 0u;
+    q = 0.0;
+    if (ch) {
+      const MnkPuctNode k = node[min((int)ch, nodes - 1)];
+      na = k.n;
+      if (na) q = (double)__fdiv_rn(k.w, (float)na);
+    }
+    return true;
+  };
+  double p, q, sp = 0.0;
+  uint32_t na, ns = 0u;
+  for (int a = lane; a < C; a += 64) {
+    const bool fr = cell(a, p, na, q);
+    if (visits) visits[i * C + a] = fr ? (int32_t)na : 0;
+    if (fr) {
+      sp += p;
+      ns += na;
+    }
+  }
+  if (!policy) return;
+  sp = puct_wave_sum(sp);
+#pragma unroll
+  for (int off = 32; off; off >>= 1) ns += (uint32_t)__shfl_xor((int)ns, off, 64);
+  double sv = 0.0, sq = 0.0;
+  for (int a = lane; a < C; a += 64)
+    if (cell(a, p, na, q) && na) {
+      sv += p / sp;
+      sq += p / sp * q;
+    }
+  sv = puct_wave_sum(sv);
+  sq = puct_wave_sum(sq);
+  const double vmix = sv > 0.0 ? ((double)vroot + (double)ns * sq / sv) / (1.0 + (double)ns) : (double)vroot;
+  const double K = ((double)gm.c_visit + (double)maxn) * (double)gm.c_scale;
+  auto y_of = [&](int a, double& y) {
+    if (!cell(a, p, na, q)) return false;
+    y = log(p) + K * (na ? q : vmix);
+    return true;
+  };
+  double y, my = -INFINITY;
+  for (int a = lane; a < C; a += 64)
+    if (y_of(a, y)) my = fmax(my, y);
+#pragma unroll
+  for (int off = 32; off; off >>= 1) my = fmax(my, __shfl_xor(my, off, 64));
+  double se = 0.0;
+  for (int a = lane; a < C; a += 64)
+    if (y_of(a, y)) se += exp(y - my);
+  se = puct_wave_sum(se);
+  for (int a = lane; a < C; a += 64) policy[i * C + a] = y_of(a, y) ? (float)(exp(y - my) / se) : 0.0f;
+}
+
 // One walk from the root (e = the root's position on entry, the leaf's on return; wave-uniform): the new pending state
 // (0: no leaf), the leaf's depth in d, its path in path[1 .. d].  A new leaf becomes node `nodes`.
 // VL: the walk of a slot under the virtual visits of the round's earlier slots.  vl(x) is counted from their stored paths
@@ -570,11 +738,14 @@ __device__ __forceinline__ void puct_env_root(MnkEnv<NW>& e, const uint32_t* roo
 // SOLVER: a child that is proven LOSS (a move proven to lose for the player making it) is a candidate only when every
 // child is -- `bc`, the class of the best cell so far (1: not such a child), orders before the score -- and the walk ends
 // in a child with a proof as it ends in a terminal one; the new pending state carries the proof in the term's bits.
-template <int NW, int CN, int CK, bool VL, bool SOLVER = false>
+// GUMBEL: at the root the cell is puct_gumbel_pick's (gm: the row's Gumbel inputs); from the chosen child on, the walk
+// below.
+template <int NW, int CN, int CK, bool VL, bool SOLVER = false, bool GUMBEL = false>
 __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, int I, float c, MnkPuctNode* node,
                                               const float* prior, uint16_t* child, uint16_t* path, int& nodes, int& d,
                                               int lane, int nodes0 = 0, uint32_t share = 0u,
-                                              const uint16_t* epath = nullptr, int edepth = 0) {
+                                              const uint16_t* epath = nullptr, int edepth = 0,
+                                              const MnkPuctGumbel* gm = nullptr) {
   const int C = g.C;
   int v = 0;
   for (;;) {
@@ -596,6 +767,14 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
     float best = 0.0f;
     int ba = 0x7fffffff;
     [[maybe_unused]] int bc = 0;
+    [[maybe_unused]] bool picked = false;  // GUMBEL, at the root: ba is the cell already, the same in every lane
+    if constexpr (GUMBEL) {
+      if (v == 0) {
+        ba = puct_gumbel_pick<false>(C, I, node, cl, nodes, *gm, lane);
+        picked = true;
+      }
+    }
+    if (!picked)  // (the loop keeps its indentation: below this line the scoring is the text it was)
     for (int a = lane; a < C; a += 64) {
       const uint32_t ch = cl[a];
       if (ch == MNK_PUCT_NONE) continue;
@@ -954,6 +1133,94 @@ k_puct_step_solver(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, c
   if (lane == 0) hdr[0] = (uint32_t)nodes;
 }
 
+// ------------------------------------------------------------------ a step whose root is a Gumbel root
+// k_puct_step (one leaf per row and evaluation, the same workspace) with the root's part of puct_walk replaced by
+// puct_gumbel_pick and puct_move by puct_move_gumbel; below the root the walk and the backup are k_puct_step's.  The
+// rule: include/mnk_hip.h, mnk_puct_step_gumbel.
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_puct_step_gumbel(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, int priors_dtype, const void* values,
+                   int values_dtype, float c, int last, int considered, float c_visit, float c_scale,
+                   const uint16_t* table, const float* gscore, const float* vroot, uint64_t seed, const uint64_t* seed_dev,
+                   uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic, void* leaf_obs,
+                   int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits, float* root_value,
+                   float* policy) {
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  const int C = g.C, NWg = g.NW;
+  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, 1);
+  unsigned char* row = ws + i * L.row;
+  uint32_t* hdr = (uint32_t*)row;
+  const uint32_t* root = (const uint32_t*)(row + L.root);
+  uint32_t* leafp = (uint32_t*)(row + L.leaf);
+  uint16_t* path = (uint16_t*)(row + L.path);
+  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
+  float* prior = (float*)(row + L.prior);
+  uint16_t* child = (uint16_t*)(row + L.child);
+  uint32_t* pos = lds_pos[wave];
+  // (clamped: a workspace that mnk_puct_begin_leaves did not set up cannot send a store outside the row)
+  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
+  const int depth = (int)min(hdr[1], (uint32_t)I);
+  const uint32_t state = hdr[2];
+  const bool live = hdr[3] != 0u;
+  for (int q = lane; q < 2 * NW; q += 64) {
+    const int pl = q >= NW, w = q - (pl ? NW : 0);
+    pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
+  }
+  row_wave_sync();
+  MnkPuctGumbel gm;
+  gm.gs = gscore + i * C;
+  gm.table = table;
+  gm.considered = considered;
+  gm.c_visit = c_visit;
+  gm.c_scale = c_scale;
+
+  // ---- backup of the pending evaluation
+  if (state & 1u)
+    puct_backup<NW, CN>(g, pos, path, node, prior, child, nodes, depth, state, priors, priors_dtype, values, values_dtype,
+                        i, lane);
+
+  if (last) {
+    puct_move_gumbel(C, I, node, prior, child, nodes, live, gm, policy ? vroot[i] : 0.0f, seed, seed_dev, step, step_dev,
+                     env_id0, deterministic, i, actions, visits, root_value, policy, lane);
+    return;
+  }
+
+  // ---- selection
+  int d = 0;
+  uint32_t nstate = 0u;  // nothing pending: a row without a legal cell (or a full tree) shows its root again
+  if (live && nodes <= I) {
+    MnkEnv<NW> e;
+    puct_env_root<NW>(e, root, NWg);
+    nstate = puct_walk<NW, CN, CK, false, false, true>(g, e, I, c, node, prior, child, path, nodes, d, lane, 0, 0u, nullptr,
+                                                       0, &gm);
+    if (nstate == 0u) d = 0;
+    if (lane == 0) {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
+        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
+      }
+    }
+  } else if (lane == 0) {
+    for (int q = 0; q < 2 * NW; ++q) {
+      const int pl = q >= NW, w = q - (pl ? NW : 0);
+      pos[q] = w < NWg ? root[pl * NWg + w] : 0u;
+    }
+  }
+  if (lane == 0) {
+    path[0] = 0;
+    hdr[0] = (uint32_t)nodes;
+    hdr[1] = (uint32_t)d;
+    hdr[2] = nstate;
+  }
+  row_wave_sync();
+  for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
+  row_write_view<NW, CN>(g, pos, d & 1, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+}
+
 // ------------------------------------------------------------------ the entry points
 // what the four pairs of entry points share: the host checks (before anything is enqueued) and the launch.  leaves = 0
 // stands for the entry point without the argument: today's kernels, one leaf.
@@ -1109,6 +1376,34 @@ int mnk_puct_step_solver(void* workspace, int64_t N, int m, int n, int k, int it
   return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
                    temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
                    actions, visits, root_value, stream, true, proof);
+}
+
+int mnk_puct_step_gumbel(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                         int priors_dtype, const void* values, int values_dtype, float c, int last, int considered,
+                         float c_visit, float c_scale, const uint16_t* table, const float* gscore, const float* vroot,
+                         uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                         int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                         int32_t* visits, float* root_value, float* policy, void* stream) {
+  MnkGeom g;
+  const int rc = mnk_check_geom(m, n, k, &g);
+  if (rc != MNK_OK) return rc;
+  const bool dt_ok = (priors_dtype == MNK_LOGITS_F32 || priors_dtype == MNK_LOGITS_BF16) &&
+                     (values_dtype == MNK_LOGITS_F32 || values_dtype == MNK_LOGITS_BF16);
+  if (!workspace || !priors || !values || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS || !dt_ok || iterations < 1 ||
+      iterations > MNK_PUCT_ITERS_MAX || !(c >= 0.0f && c <= 3.0e38f) || (last != 0 && last != 1) || leaves != 1 ||
+      considered < 1 || considered > MNK_PUCT_CONSIDERED_MAX || !(c_visit >= 0.0f && c_visit <= 3.0e38f) ||
+      !(c_scale >= 0.0f && c_scale <= 3.0e38f) || !table || !gscore)
+    return MNK_EINVAL;
+  if (last ? (!actions || (policy && !vroot)) : (!leaf_obs || !leaf_mask || !mnk_obs_dtype_ok(leaf_dtype)))
+    return MNK_EINVAL;
+  if (N == 0) return MNK_OK;
+  const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
+  MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step_gumbel), grid, block, 0, (hipStream_t)stream, g,
+                                     (unsigned char*)workspace, N, iterations, priors, priors_dtype, values, values_dtype, c,
+                                     last, considered, c_visit, c_scale, table, gscore, vroot, seed, seed_dev, step,
+                                     step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions, visits,
+                                     root_value, policy));
+  return mnk_launch_status("puct_step_gumbel");
 }
 
 }  // extern "C"

@@ -113,6 +113,101 @@ k_search_selfplay_step(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, c
   row_write_view<NW, CN, true>(g, pos, 0, i, obs, obs_dtype, legal_mask, lane);
 }
 
+// mnk_search_selfplay_step with the move given and the improved policy as the ring's visits (the rule: include/mnk_hip.h,
+// mnk_search_selfplay_step_moves).  A kernel of its own, not a flag on the one above: what follows the move -- the ply, the
+// outcome labels, the statistics, the reset, the next root -- is that kernel's text, kept apart so that its code objects
+// stay what they were.
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256)
+k_search_selfplay_step_moves(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, const float* policy,
+                             const int64_t* actions, uint64_t step, const uint64_t* step_dev, int64_t T,
+                             uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* obs, int obs_dtype,
+                             uint8_t* legal_mask, unsigned long long* stats, int32_t* err) {
+  __shared__ uint32_t lds_pos[MNK_SSP_ROWS][2 * NW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_SSP_ROWS + wave;
+  if (i >= N) return;
+  const int C = g.C, W = g.W;
+  uint32_t* pos = lds_pos[wave];
+  MnkEnv<NW> e;
+  env_load<NW>(e, planes, meta, N, W, i);
+  if (step_dev) step += *step_dev;
+  const int64_t t = (int64_t)(step % (uint64_t)T);
+  const uint32_t side = e.meta & 1u, moves = e.meta >> 1;
+  uint32_t mine[NW], theirs[NW];
+#pragma unroll
+  for (int w = 0; w < NW; ++w) {
+    mine[w] = side ? e.p[1][w] : e.p[0][w];
+    theirs[w] = side ? e.p[0][w] : e.p[1][w];
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      pos[w] = mine[w];
+      pos[NW + w] = theirs[w];
+    }
+  }
+  row_wave_sync();
+
+  // ---- the policy of the free cells, scaled to 65535, into ring row t; is the action a free cell?
+  const float* prow = policy + i * C;
+  uint16_t* rv = ring_visits + (t * N + i) * C;
+  for (int a = lane; a < C; a += 64) {
+    const bool occ = row_stone<CN>(g, pos, a) || row_stone<CN>(g, pos + NW, a);
+    const float v = rintf(__fmul_rn(prow[a], 65535.0f));
+    rv[a] = (occ || !(v > 0.0f)) ? (uint16_t)0 : (uint16_t)fminf(v, 65535.0f);
+  }
+  const int64_t act = actions[i];
+  const bool in_range = act >= 0 && act < C;
+  const int move = in_range ? (int)act : 0;
+  const bool playable = in_range && !(row_stone<CN>(g, pos, move) || row_stone<CN>(g, pos + NW, move));
+  if (lane == 0) {
+    uint64_t* rp = ring_planes + t * 2 * W * N;
+    plane_store<NW>(mine, rp, N, W, i);
+    plane_store<NW>(theirs, rp + (int64_t)W * N, N, W, i);
+  }
+
+  // ---- the ply, the outcome labels
+  MnkPly ply;
+  ply.win = false; ply.done = false; ply.err = 0;
+  if (playable) {
+    ply = env_play<NW, CN, CK, true>(g, e, move, false);
+  } else if (lane == 0) {  // the env is left as it is; its record carries no outcome
+    mnk_report(err, in_range ? MNK_ERR_ILLEGAL_MOVE : MNK_ERR_ACTION_RANGE, i);
+  }
+  if (lane == 0) ring_z[t * N + i] = ply.done ? (int8_t)(ply.win ? 1 : 0) : (int8_t)MNK_Z_UNKNOWN;
+  if (ply.done) {
+    // records t - d (mod T), d = 1 .. L - 1, of this game: the view of the side to move there; T >= C >= L
+    const int64_t L = min((int64_t)moves + 1, T);
+    const int8_t zw = ply.win ? 1 : 0;
+    for (int64_t d = 1 + lane; d < L; d += 64) {
+      const int64_t r = t >= d ? t - d : t + T - d;
+      ring_z[r * N + i] = (d & 1) ? (int8_t)-zw : zw;
+    }
+    if (stats && lane == 0) {
+      unsigned long long* s = stats + (size_t)(blockIdx.x % MNK_STATS_REPLICAS) * MNK_STATS_STRIDE;
+      atomicAdd(&s[0], 1ull);
+      atomicAdd(&s[ply.win ? 1 + side : 3], 1ull);
+      atomicAdd(&s[4], (unsigned long long)moves + 1ull);
+    }
+    env_clear<NW>(e);
+  }
+  if (playable && lane == 0) env_store<NW>(e, planes, meta, N, W, i);
+
+  // ---- the next root
+  row_wave_sync();  // (every lane is done with the position before this ply)
+  if (lane == 0) {
+    const uint32_t ns = e.meta & 1u;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      pos[w] = ns ? e.p[1][w] : e.p[0][w];
+      pos[NW + w] = ns ? e.p[0][w] : e.p[1][w];
+    }
+  }
+  row_wave_sync();
+  row_write_view<NW, CN, true>(g, pos, 0, i, obs, obs_dtype, legal_mask, lane);
+}
+
 // ------------------------------------------------------------------ a minibatch of ring records under symmetries
 // symmetry s of a board of m rows, n columns: the source cell of output cell (r, c)
 __device__ __forceinline__ void mnk_sym_src(int s, int m, int n, int& r, int& c) {
@@ -254,6 +349,25 @@ int mnk_search_selfplay_step(uint64_t* planes, uint32_t* meta, int64_t N, int m,
                                      temp_plies, seed, seed_dev, step, step_dev, env_id0, T, ring_planes, ring_visits,
                                      ring_z, obs, obs_dtype, legal_mask, (unsigned long long*)stats, err));
   return mnk_launch_status("search_selfplay_step");
+}
+
+int mnk_search_selfplay_step_moves(uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k, const float* policy,
+                                   const int64_t* actions, uint64_t step, const uint64_t* step_dev, int64_t T,
+                                   uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* obs, int obs_dtype,
+                                   uint8_t* legal_mask, int64_t* stats, int32_t* err, void* stream) {
+  MnkGeom g;
+  const int rc = mnk_check_geom(m, n, k, &g);
+  if (rc != MNK_OK) return rc;
+  if (!planes || !meta || !policy || !actions || !ring_planes || !ring_visits || !ring_z || !obs || N < 0 ||
+      N > (int64_t)0x7fffffff * MNK_SSP_ROWS || T < g.C || !mnk_obs_dtype_ok(obs_dtype))
+    return MNK_EINVAL;
+  if (N == 0) return MNK_OK;
+  const dim3 grid((unsigned)((N + MNK_SSP_ROWS - 1) / MNK_SSP_ROWS)), block(64 * MNK_SSP_ROWS);
+  hipStream_t s = (hipStream_t)stream;
+  MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_search_selfplay_step_moves), grid, block, 0, s, g, planes, meta, N, policy,
+                                     actions, step, step_dev, T, ring_planes, ring_visits, ring_z, obs, obs_dtype,
+                                     legal_mask, (unsigned long long*)stats, err));
+  return mnk_launch_status("search_selfplay_step_moves");
 }
 
 int mnk_search_gather(const uint64_t* ring_planes, const uint16_t* ring_visits, const int8_t* ring_z, int64_t T,

@@ -31,6 +31,8 @@ SEARCH_ITERS_MAX = 2048  # MNK_SEARCH_ITERS_MAX: the largest iteration budget of
 SEARCH_PLAYOUTS_MAX = 256  # MNK_SEARCH_PLAYOUTS_MAX: the largest playout count per leaf of mnk_sample_search
 PUCT_ITERS_MAX = 2048  # MNK_PUCT_ITERS_MAX: the largest iteration budget of mnk_puct_begin / mnk_puct_step
 PUCT_LEAVES_MAX = 16  # MNK_PUCT_LEAVES_MAX: the most leaves per row and evaluation of the mnk_puct_*_leaves entry points
+STREAM_GUMBEL = 8  # MNK_STREAM_GUMBEL: the Gumbel variables of the PUCT player's Gumbel root (mnk_puct_gumbel_root)
+PUCT_CONSIDERED_MAX = 1024  # MNK_PUCT_CONSIDERED_MAX: the most root moves mnk_puct_step_gumbel considers
 PUCT_NOISE_TRIES = 16  # MNK_PUCT_NOISE_TRIES: the most Marsaglia-Tsang candidates per cell of mnk_puct_root_noise
 STATS_REPLICAS, STATS_STRIDE, STATS_COUNTERS = 64, 8, 5
 # run-time specialised API kernels (MNK_JIT_API_* of include/mnk_hip.h): bit numbers for jit_prepare()
@@ -116,6 +118,19 @@ SIGNATURES = {
     # priors, priors dtype, mask, N, C, leaves, alpha, eps, then seed, seed_dev, step, step_dev, env_id0, out (f32
     # [N * leaves][C]), stream
     "mnk_puct_root_noise": [_vp, _i, _vp, _i64, _i, _i, _f, _f, _u64, _vp, _u64, _vp, _i64, _vp, _vp],
+    # considered, iterations, out (HOST u16 [considered + 1][iterations]): the Gumbel root's table of considered visits
+    "mnk_puct_gumbel_schedule": [_i, _i, _vp],
+    # priors, priors dtype, mask, values, values dtype, N, C, gumbel scale, then seed, seed_dev, step, step_dev, env_id0,
+    # gscore (f32 [N][C]), vroot (f32 [N]), stream
+    "mnk_puct_gumbel_root": [_vp, _i, _vp, _vp, _i, _i64, _i, _f, _u64, _vp, _u64, _vp, _i64, _vp, _vp, _vp],
+    # mnk_puct_step_leaves with considered, c_visit, c_scale, table, gscore, vroot in the place of the temperature, and
+    # policy (f32 [N][C]) before the stream
+    "mnk_puct_step_gumbel": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _f, _f, _vp, _vp, _vp, _u64, _vp,
+                             _u64, _vp, _i64, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    # planes, meta, N, m, n, k, policy (f32 [N][C]), actions (int64 [N]), step, step_dev, T, ring planes, ring visits, ring
+    # z, obs, obs dtype, legal mask, stats, err, stream
+    "mnk_search_selfplay_step_moves": [_vp, _vp, _i64, _i, _i, _i, _vp, _vp, _u64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp,
+                                       _vp, _vp, _vp],
     # planes, meta, N, m, n, k, visits (int32 [N][C]), temp_plies, then seed, seed_dev, step, step_dev, env_id0, T, ring
     # planes, ring visits, ring z, obs, obs dtype, legal mask, stats, err, stream
     "mnk_search_selfplay_step": [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _u64, _vp, _u64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
@@ -318,6 +333,16 @@ def puct_workspace_bytes(N: int, m: int, n: int, iterations: int, leaves: int = 
     if size < 0:
         raise MnkHipError(f"{name}: {_STATUS.get(size, f'status {size}')}")
     return size
+
+
+def puct_gumbel_schedule(considered: int, iterations: int):
+    """the Gumbel root's table of considered visits (mnk_puct_gumbel_schedule; needs no GPU): a numpy uint16 array
+    ``[considered + 1, iterations]`` whose row m' is the sequence a root with m' moves to consider follows"""
+    import numpy as np
+
+    out = np.zeros((max(int(considered), 0) + 1, max(int(iterations), 0)), np.uint16)
+    call("mnk_puct_gumbel_schedule", considered, iterations, out.ctypes.data)
+    return out
 
 
 def record_words(m: int, n: int) -> int:

@@ -326,11 +326,23 @@ class PUCTSearchPolicy(Policy):
     the proven losses (or everything but the proven wins), and the root value of a proven root is exactly +1, 0 or -1.
     Every step is then ``mnk_puct_step_solver``, at any ``leaves``, with or without ``reuse`` (a kept subtree keeps its
     proofs) and ``root_noise``; the evaluator sees the same batches.  With the solver the visits no longer sum to the
-    number of iterations.  ``False`` (the default): the search above, launch for launch."""
+    number of iterations.  ``False`` (the default): the search above, launch for launch.
+
+    ``gumbel=m`` (1 .. ``PUCT_CONSIDERED_MAX``) makes the root a Gumbel root ("Policy improvement by planning with
+    Gumbel", Danihelka et al. 2022; the rule: include/mnk_hip.h, mnk_puct_step_gumbel): one Philox-keyed Gumbel variable
+    per root move, the budget spent on the m best moves by Sequential Halving, the survivor played, and the improved
+    policy ``softmax(ln P + sigma(completed q))`` handed out through ``act(policy=...)`` as the training target -- a
+    search meant for small ``iterations``, where visit counts say little.  ``gumbel_c=(c_visit, c_scale)`` are sigma's
+    constants (q lies in [-1, 1] here, hence 0.5 where the paper has 1) and ``gumbel_scale`` scales the Gumbel variables
+    (0, which ``act(deterministic=True)`` passes: no randomness at all).  Below the root the search is the one above.  One
+    more launch per ``act`` (the draw, after the roots' evaluation) and three buffers of the policy's own.  It does not
+    combine with ``reuse``, ``leaves > 1``, ``solver``, ``root_noise`` or ``temperature=1`` yet (``ValueError``).
+    ``None`` (the default): the search above, launch for launch, and nothing is allocated."""
 
     def __init__(self, k: int, model=None, evaluator=None, iterations: int = 256, c: float = 1.25, temperature: int = 0,
                  leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None, leaves: int = 1,
-                 root_noise=None, solver: bool = False):
+                 root_noise=None, solver: bool = False, gumbel: int = None, gumbel_c=(50.0, 0.5),
+                 gumbel_scale: float = 1.0):
         if (model is None) == (evaluator is None):
             raise ValueError("PUCTSearchPolicy needs exactly one of model and evaluator")
         self.k = int(k)
@@ -370,7 +382,14 @@ class PUCTSearchPolicy(Policy):
             self.tree_nodes = self.iterations + 1
         self.root_noise = self._checked_root_noise(root_noise)
         self.solver = bool(solver)
+        self.gumbel, self.gumbel_c, self.gumbel_scale = self._checked_gumbel(gumbel, gumbel_c, gumbel_scale)
+        if self.gumbel is not None:
+            for name, on in (("reuse=True", self.reuse), ("leaves > 1", self.leaves > 1), ("solver=True", self.solver),
+                             ("root_noise", self.root_noise is not None), ("temperature=1", temperature == 1)):
+                if on:
+                    raise ValueError(f"gumbel does not combine with {name} yet")
         self._bufs = None  # (key, workspace, leaf_obs, leaf_mask, noised priors or None)
+        self._gumbel_bufs = None  # gumbel: (key, table, gscore, vroot)
 
     @staticmethod
     def _checked_root_noise(root_noise):
@@ -386,6 +405,33 @@ class PUCTSearchPolicy(Policy):
         if not 0.0 <= eps <= 1.0:
             raise ValueError(f"root_noise: eps must lie in [0, 1], got {eps}")
         return alpha, eps
+
+    @staticmethod
+    def _checked_gumbel(gumbel, gumbel_c, gumbel_scale):
+        """(None or m, (c_visit, c_scale), gumbel_scale): m an int in [1, PUCT_CONSIDERED_MAX], the floats finite, >= 0"""
+        try:
+            c_visit, c_scale = (float(x) for x in gumbel_c)
+            scale = float(gumbel_scale)
+        except (TypeError, ValueError):
+            raise ValueError(f"gumbel_c must be (c_visit, c_scale) and gumbel_scale a number, got {gumbel_c!r} and "
+                             f"{gumbel_scale!r}") from None
+        for name, x in (("gumbel_c: c_visit", c_visit), ("gumbel_c: c_scale", c_scale), ("gumbel_scale", scale)):
+            if not (math.isfinite(x) and 0.0 <= x <= 3.0e38):
+                raise ValueError(f"{name} must be finite and >= 0, got {x}")
+        if gumbel is None:
+            return None, (c_visit, c_scale), scale
+        if isinstance(gumbel, bool) or gumbel != int(gumbel) or not 1 <= int(gumbel) <= mnk_hip.PUCT_CONSIDERED_MAX:
+            raise ValueError(f"gumbel must be None or a number of moves in [1, {mnk_hip.PUCT_CONSIDERED_MAX}], got {gumbel!r}")
+        return int(gumbel), (c_visit, c_scale), scale
+
+    def _gumbel_buffers(self, b, c, device):
+        key = (b, c, self.iterations, self.gumbel, device)
+        if self._gumbel_bufs is None or self._gumbel_bufs[0] != key:
+            table = mnk_hip.puct_gumbel_schedule(self.gumbel, self.iterations)
+            self._gumbel_bufs = (key, torch.from_numpy(table.view("int16")).to(device),
+                                 torch.empty((b, c), dtype=torch.float32, device=device),
+                                 torch.empty(b, dtype=torch.float32, device=device))
+        return self._gumbel_bufs[1:]
 
     @property
     def evaluations_per_act(self) -> int:
@@ -424,7 +470,7 @@ class PUCTSearchPolicy(Policy):
             self._bufs[1].zero_()
 
     def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, visits=None, root_value=None,
-            carried=None, proof=None) -> torch.Tensor:
+            carried=None, proof=None, policy=None) -> torch.Tensor:
         """``visits``: optional int32 ``[B, m*n]`` tensor that receives each row's root visit counts (an AlphaZero policy
         target; they sum to ``iterations`` on a row with a legal cell, to the carried visits plus ``iterations`` on a row
         that kept its tree); ``root_value``: optional float32 ``[B]`` tensor that receives the root's mean value for the
@@ -433,7 +479,11 @@ class PUCTSearchPolicy(Policy):
         optional int8 ``[B]`` tensor that receives +1, 0 or -1 where the root is a proven win, draw or loss for the side to
         move and ``mnk_hip.PROOF_UNKNOWN`` elsewhere.  With ``solver=True`` ``visits`` are the adjusted counts (the proven
         wins alone when there is one, else all but the proven losses) and do not sum to ``iterations``, and
-        ``root_value`` is exactly +1, 0 or -1 on a proven root"""
+        ``root_value`` is exactly +1, 0 or -1 on a proven root; ``policy`` (``gumbel=m``): optional float32 ``[B, m*n]``
+        tensor that receives the improved policy (it sums to 1 over the free cells; 0 on occupied cells and on a row
+        without a free cell)"""
+        if policy is not None and self.gumbel is None:
+            raise ValueError("policy is an output of a search with a Gumbel root: it needs gumbel=m")
         observation = _canonical_observation(obs)
         b, _, m, n = observation.shape
         dev = observation.device
@@ -443,11 +493,14 @@ class PUCTSearchPolicy(Policy):
             raise ValueError("proof is an output of a search that proves its tree: it needs solver=True")
         for name, t, shape, dtype in (("visits", visits, (b, m * n), torch.int32),
                                       ("root_value", root_value, (b,), torch.float32),
-                                      ("carried", carried, (b, 2), torch.int32), ("proof", proof, (b,), torch.int8)):
+                                      ("carried", carried, (b, 2), torch.int32), ("proof", proof, (b,), torch.int8),
+                                      ("policy", policy, (b, m * n), torch.float32)):
             if t is not None and (t.shape != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
                 raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {shape} tensor on {dev}")
         actions = torch.empty(b, dtype=torch.long, device=dev)
-        if b:
+        if b and self.gumbel is not None:
+            self._act_gumbel(observation, deterministic, actions, visits, root_value, policy)
+        elif b:
             ws, leaf_obs, leaf_mask, noised = self._buffers(b, m, n, dev)
             stream = mnk_hip.stream_ptr(dev)
             I, k, code = self.iterations, self.k, self._leaf_code
@@ -478,6 +531,31 @@ class PUCTSearchPolicy(Policy):
                              mnk_hip.ptr(root_value) if last else None, *out, stream)
         self._sampler.advance()
         return actions
+
+    def _act_gumbel(self, observation, deterministic, actions, visits, root_value, policy):
+        """the launches of an ``act`` with a Gumbel root: mnk_puct_begin_leaves, the roots' evaluation,
+        mnk_puct_gumbel_root, then ``iterations + 1`` times mnk_puct_step_gumbel with an evaluation between them"""
+        b, _, m, n = observation.shape
+        dev = observation.device
+        ws, leaf_obs, leaf_mask, _ = self._buffers(b, m, n, dev)
+        table, gscore, vroot = self._gumbel_buffers(b, m * n, dev)
+        stream = mnk_hip.stream_ptr(dev)
+        I, k, code = self.iterations, self.k, self._leaf_code
+        mnk_hip.call("mnk_puct_begin_leaves", mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k, I, 1,
+                     mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask), stream)
+        for it in range(I + 1):
+            priors, pcode, values, vcode = self._evaluate(leaf_obs, leaf_mask, b, m * n)
+            last = it == I
+            if it == 0:
+                mnk_hip.call("mnk_puct_gumbel_root", mnk_hip.ptr(priors), pcode, mnk_hip.ptr(leaf_mask), mnk_hip.ptr(values),
+                             vcode, b, m * n, 0.0 if deterministic else self.gumbel_scale, *self._sampler.block()[:5],
+                             mnk_hip.ptr(gscore), mnk_hip.ptr(vroot), stream)
+            mnk_hip.call("mnk_puct_step_gumbel", mnk_hip.ptr(ws), b, m, n, k, I, 1, mnk_hip.ptr(priors), pcode,
+                         mnk_hip.ptr(values), vcode, self.c, 1 if last else 0, self.gumbel, *self.gumbel_c,
+                         mnk_hip.ptr(table), mnk_hip.ptr(gscore), mnk_hip.ptr(vroot), *self._sampler.block(deterministic),
+                         mnk_hip.ptr(leaf_obs), code, mnk_hip.ptr(leaf_mask), mnk_hip.ptr(actions) if last else None,
+                         mnk_hip.ptr(visits) if last else None, mnk_hip.ptr(root_value) if last else None,
+                         mnk_hip.ptr(policy) if last else None, stream)
 
 
 class NNPolicy(Policy):

@@ -25,6 +25,11 @@ by temperature or not -- is carried over and a game that was reset starts fresh,
 include/mnk_hip.h, mnk_puct_step_solver).  The step kernel is the same: it plays from, and records, the visits it is
 given, which are then the adjusted ones -- the ring's policy targets carry no count of a move proven to lose, and only the
 proven wins where there is one.
+
+``gumbel=m`` searches with a Gumbel root (``PUCTSearchPolicy(gumbel=m)``, the rule: include/mnk_hip.h,
+mnk_puct_step_gumbel) and plays through ``mnk_search_selfplay_step_moves``: the move is the search's own -- a sample from
+the improved policy, drawn at the ring's ply counter like the noise -- and the ring's u16 visits are that policy scaled to
+65 535, which ``mnk_search_gather`` turns back into the target.  ``temp_plies`` is then not read.
 """
 from typing import Dict
 
@@ -40,7 +45,7 @@ class SearchSelfPlay:
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  c: float = 1.25, temp_plies: int = None, capacity: int = None, seed=None, leaf_dtype=torch.float32,
                  device="cuda", reuse: bool = False, tree_nodes: int = None, leaves: int = 1, root_noise=None,
-                 solver: bool = False):
+                 solver: bool = False, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -57,7 +62,8 @@ class SearchSelfPlay:
         # GPU)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
                                        temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=reuse, tree_nodes=tree_nodes,
-                                       leaves=leaves, root_noise=root_noise, solver=solver)
+                                       leaves=leaves, root_noise=root_noise, solver=solver, gumbel=gumbel,
+                                       gumbel_c=gumbel_c, gumbel_scale=gumbel_scale)
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
@@ -70,6 +76,9 @@ class SearchSelfPlay:
         self.visits = torch.zeros((self.num_envs, C), dtype=torch.int32, device=dev)
         # reuse: {nodes kept, the kept root's visit count} of every row in the last ply's search ({0, 0}: it began afresh)
         self.carried = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=dev) if reuse else None
+        # gumbel: the search's improved policy, what mnk_search_selfplay_step_moves records
+        self.target = (torch.zeros((self.num_envs, C), dtype=torch.float32, device=dev)
+                       if self.policy.gumbel is not None else None)
         self.stats = torch.zeros((mnk_hip.STATS_REPLICAS, mnk_hip.STATS_STRIDE), dtype=torch.int64, device=dev)
         self._ones = torch.ones(1, dtype=torch.int64, device=dev)
 
@@ -78,6 +87,9 @@ class SearchSelfPlay:
         env, buf = self.env, self.buffer
         stream = mnk_hip.stream_ptr(env._dev)
         for _ in range(int(plies)):
+            if self.target is not None:
+                self._ply_gumbel(stream)
+                continue
             self.policy.act({"observation": self.obs, "action_mask": self.mask}, visits=self.visits, carried=self.carried)
             seed, seed_dev, step, step_dev, env_id0, _ = self.sampler.block()
             mnk_hip.call("mnk_search_selfplay_step", mnk_hip.ptr(env._planes), mnk_hip.ptr(env._meta), self.num_envs,
@@ -87,6 +99,19 @@ class SearchSelfPlay:
                          mnk_hip.ptr(env._err), stream)
             buf.plies.add_(self._ones)
             buf.plies_host += 1
+
+    def _ply_gumbel(self, stream) -> None:
+        """one ply of a search with a Gumbel root: the search's own move and its improved policy go to the step"""
+        env, buf = self.env, self.buffer
+        actions = self.policy.act({"observation": self.obs, "action_mask": self.mask}, visits=self.visits,
+                                  policy=self.target)
+        _, _, step, step_dev, _, _ = self.sampler.block()
+        mnk_hip.call("mnk_search_selfplay_step_moves", mnk_hip.ptr(env._planes), mnk_hip.ptr(env._meta), self.num_envs,
+                     self.m, self.n, self.k, mnk_hip.ptr(self.target), mnk_hip.ptr(actions), step, step_dev, buf.capacity,
+                     mnk_hip.ptr(buf.planes), mnk_hip.ptr(buf.visits), mnk_hip.ptr(buf.z), mnk_hip.ptr(self.obs),
+                     mnk_hip.OBS_F32, mnk_hip.ptr(self.mask), mnk_hip.ptr(self.stats), mnk_hip.ptr(env._err), stream)
+        buf.plies.add_(self._ones)
+        buf.plies_host += 1
 
     def reset_trees(self) -> None:
         """``reuse=True``: forget the kept trees, so that the next ply searches every row afresh -- for after the
