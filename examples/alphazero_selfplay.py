@@ -10,10 +10,14 @@ are renewed every ply) and drops the trees after each training round, since thei
 ``--solver`` proves wins, draws and losses inside the search (``SearchSelfPlay(solver=True)``): the policy targets drop
 the moves proven to lose.  ``--search gumbel`` searches with a Gumbel root (``SearchSelfPlay(gumbel=m)``): the Gumbel draw
 is the exploration (no root noise, no temperature) and the targets are the improved policy; the default ``puct`` is the
-run it was.
+run it was.  ``--fast-iterations F --full-prob P`` (both) play through ``AsyncSearchSelfPlay``: a ply is searched with
+``--iterations`` with probability P and is then a policy and value target, with F otherwise and is then a value target
+only, and every row plays on as soon as its own search is done (playout cap randomisation); the wrapper's root noise then
+goes to the rows the player marks ``fresh``.
 
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse] [--solver]
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --search gumbel --iterations 16
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25
 """
 import argparse
 import os
@@ -67,6 +71,24 @@ class RootNoise:
         return (1 - self.eps) * priors.float() + self.eps * noise, values
 
 
+class FreshRootNoise:
+    """``RootNoise`` for ``AsyncSearchSelfPlay``, whose rows reach their roots at different calls: the noise goes to the rows
+    of ``fresh()`` (uint8 [N], the player's ``fresh``), in every call; no host synchronisation"""
+
+    def __init__(self, inner, alpha=0.3, eps=0.25):
+        self.inner, self.alpha, self.eps, self.fresh = inner, alpha, eps, None
+
+    def __call__(self, leaf_obs, leaf_mask):
+        priors, values = self.inner(leaf_obs, leaf_mask)
+        if self.fresh is None or self.eps == 0:
+            return priors, values
+        conc = torch.full(priors.shape, self.alpha, dtype=torch.float32, device=priors.device)
+        noise = torch.distributions.Dirichlet(conc, validate_args=False).sample() * leaf_mask
+        noise = noise / noise.sum(dim=1, keepdim=True).clamp(min=1e-12)
+        eps = self.eps * self.fresh().to(torch.float32).unsqueeze(1)
+        return (1 - eps) * priors.float() + eps * noise, values
+
+
 def greedy(net):
     from selfplay.policy import Policy
 
@@ -80,11 +102,13 @@ def greedy(net):
 
 
 def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates=40, batch=512, lr=2e-3, seed=0,
-          noise=True, reuse=False, leaves=1, solver=False, search="puct", considered=4, log=print):
+          noise=True, reuse=False, leaves=1, solver=False, search="puct", considered=4, fast_iterations=None,
+          full_prob=None, log=print):
     """self-play and training rounds; returns the network.  ``noise``: True / "wrapper" (``RootNoise``), "builtin" (the
     search's own root noise, same alpha and eps) or False / "off" (none).  ``search``: "puct", or "gumbel" -- a Gumbel
     root over ``considered`` moves (``SearchSelfPlay(gumbel=...)``): the exploration is the Gumbel draw and the targets are
-    the improved policy, so ``noise`` is not used, and a small ``iterations`` (16) is what it is meant for"""
+    the improved policy, so ``noise`` is not used, and a small ``iterations`` (16) is what it is meant for.
+    ``fast_iterations`` and ``full_prob`` (both, or neither): play through ``AsyncSearchSelfPlay`` with per-ply budgets"""
     entry.build()
     from selfplay.policy import model_evaluator
     from selfplay.search_selfplay import SearchSelfPlay
@@ -100,6 +124,11 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
     noise = "off" if search == "gumbel" else {True: "wrapper", False: "off"}.get(noise, noise)
     if noise not in ("wrapper", "builtin", "off"):
         raise ValueError(f"noise must be 'wrapper', 'builtin' or 'off', got {noise!r}")
+    if (fast_iterations is None) != (full_prob is None):
+        raise ValueError("fast_iterations and full_prob go together")
+    if fast_iterations is not None:
+        return _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies,
+                            updates, batch, seed, noise, reuse or leaves != 1 or solver or search != "puct", log)
     if noise == "wrapper":
         evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
@@ -128,6 +157,47 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
         stats = sp.pop_game_stats()
         log(f"round {r}: games {stats['games']} black {stats['black_wins']} white {stats['white_wins']} "
             f"draws {stats['draws']} mean length {stats['mean_length']:.2f} loss {loss.item():.4f}")
+    net.eval()
+    return net
+
+
+def _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies, updates, batch,
+                 seed, noise, unsupported, log):
+    """``train`` through ``AsyncSearchSelfPlay``: a training round follows as many evaluator calls as ``plies`` plies of
+    every row cost on average; the loss is ``train``'s (a fast ply's policy target is all zero: only its value counts)"""
+    from selfplay.search_selfplay import AsyncSearchSelfPlay
+
+    if unsupported or noise == "builtin":
+        raise ValueError("per-ply budgets do not combine with reuse, leaves, solver, gumbel or the built-in noise yet")
+    dev = next(net.parameters()).device
+    C = m * n
+    if noise == "wrapper":
+        evaluator = FreshRootNoise(evaluator)
+    sp = AsyncSearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, fast_iterations=fast_iterations,
+                             full_prob=full_prob, temp_plies=max(1, C // 3), capacity=2 * C, seed=seed)
+    if noise == "wrapper":
+        evaluator.fresh = lambda: sp.fresh
+    per_ply = full_prob * (iterations + 1) + (1 - full_prob) * (fast_iterations + 1)
+    calls = max(1, round((C if plies is None else plies) * per_ply))
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(seed)
+    for r in range(rounds):
+        net.eval()
+        sp.advance(calls)
+        net.train()
+        for _ in range(updates):
+            b = sp.buffer.sample(batch, generator=gen)
+            logits, v = net.logits(b["observation"], b["action_mask"])
+            logp = torch.log_softmax(logits, dim=1)
+            loss_pi = -(b["policy"] * logp.masked_fill(~b["action_mask"], 0.0)).sum(dim=1)
+            loss = ((loss_pi + (v - b["value"]) ** 2) * b["weight"]).sum() / b["weight"].sum().clamp(min=1.0)
+            opt.zero_grad(set_to_none=True)
+            loss.backward()
+            opt.step()
+        stats = sp.pop_game_stats()
+        log(f"round {r}: {calls} evaluator calls, plies {int(sp.row_plies.min())}..{int(sp.row_plies.max())} games "
+            f"{stats['games']} black {stats['black_wins']} white {stats['white_wins']} draws {stats['draws']} mean length "
+            f"{stats['mean_length']:.2f} loss {loss.item():.4f}")
     net.eval()
     return net
 
@@ -164,10 +234,16 @@ def main():
                     help="gumbel: a Gumbel root with Sequential Halving and improved-policy targets (no root noise; try "
                          "--iterations 16)")
     ap.add_argument("--considered", type=int, default=4, help="--search gumbel: the root moves Sequential Halving considers")
+    ap.add_argument("--fast-iterations", type=int, default=None,
+                    help="with --full-prob: the budget of the plies that are not searched in full (value targets only)")
+    ap.add_argument("--full-prob", type=float, default=None,
+                    help="with --fast-iterations: the probability that a ply is searched with --iterations and becomes a "
+                         "policy target; rows then play on as soon as their own search is done")
     a = ap.parse_args()
     m, n, k = (int(x) for x in a.board.lower().split("x"))
     net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed,
-                noise=a.noise, reuse=a.reuse, leaves=a.leaves, solver=a.solver, search=a.search, considered=a.considered)
+                noise=a.noise, reuse=a.reuse, leaves=a.leaves, solver=a.solver, search=a.search, considered=a.considered,
+                fast_iterations=a.fast_iterations, full_prob=a.full_prob)
     for name, res in validate(net, m, n, k).items():
         print(f"vs {name}: win {res['win_rate']:.3f} loss {res['loss_rate']:.3f} draw {res['draw_rate']:.3f} "
               f"score {res['score_rate']:.3f}")

@@ -126,6 +126,7 @@ extern "C" {
 #define MNK_STREAM_SELFPLAY 6 /* the move of a search self-play ply (mnk_search_selfplay_step) */
 #define MNK_STREAM_NOISE 7    /* the Dirichlet noise on the PUCT player's root priors (mnk_puct_root_noise) */
 #define MNK_STREAM_GUMBEL 8   /* the Gumbel variables of the PUCT player's Gumbel root (mnk_puct_gumbel_root) */
+#define MNK_STREAM_BUDGET 9   /* is a self-play ply searched with the full budget? (mnk_search_selfplay_advance) */
 
 int mnk_abi_version(void);
 /* Developer knobs (MNK_ROLLOUT_PAIR, MNK_ROLLOUT_FORM, MNK_JIT, MNK_ROLLOUT_SADDR, MNK_EMIT_ENVS, MNK_EMIT_THREADS: A/B
@@ -654,6 +655,48 @@ int mnk_search_selfplay_step_moves(uint64_t* planes, uint32_t* meta, int64_t N, 
                                    const int64_t* actions, uint64_t step, const uint64_t* step_dev, int64_t T,
                                    uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* obs, int obs_dtype,
                                    uint8_t* legal_mask, int64_t* stats, int32_t* err, void* stream);
+/* Search self-play with a search budget per row and ply: ONE launch per evaluator call, in the place of mnk_puct_step and
+ * mnk_search_selfplay_step.  A row that has spent the budget of its ply plays it in this launch and starts the search of
+ * the position it reached at once, so rows finish their searches at different times ("playout cap randomisation": most
+ * plies get a small budget and only move the game on, a random fraction get the full one and become policy targets).
+ * The workspace is that of mnk_puct_begin with iterations (leaves = 1), set up by mnk_puct_begin on the current roots (the
+ * canonical views of planes / meta); priors [N][C] and values [N] (f32 or bf16) are the evaluator's outputs for the
+ * leaves of the call before (of mnk_puct_begin first).  row_plies u64 [N], in and out: p_i = the plies row i has played.
+ * 1 <= fast_iterations <= iterations <= MNK_PUCT_ITERS_MAX; full_threshold in [0, 2^32].  Row i of a launch:
+ *   1. backup: a pending evaluation is backed up by mnk_puct_step's rule, bit for bit, from batch row i.
+ *   2. budget: u = Philox(seed [or *seed_dev], env_id0 + i, p_i, MNK_STREAM_BUDGET); the ply is FULL iff (uint64)u <
+ *      full_threshold (0: never, 2^32: always); B = iterations when FULL, else fast_iterations.  Nothing is stored: the
+ *      budget of a ply is a function of (seed, row id, p_i) alone.
+ *   3. it = n_root - 1, the iterations backed up since the row's evaluation 0.
+ *      it < B: mnk_puct_step's selection; the new leaf's view goes to row i of leaf_obs / leaf_mask; fresh[i] = 0.
+ *      it >= B: the ply ends in this launch by mnk_search_selfplay_step's rule with p_i in the place of the global ply:
+ *        t = p_i mod T, x = Philox(seed, env_id0 + i, p_i, MNK_STREAM_SELFPLAY), n_a = the root children's visits
+ *        clamped to [0, 65535] on free cells, the move from n_a (temperature 1 while the game's move count g <
+ *        temp_plies, else 0).  Ring row (t, i): the planes before the ply, z unknown, and the visits -- n_a on a FULL ply,
+ *        all zero on a fast one (a value target only: mnk_search_gather gives a zero policy for a zero sum).  Then the
+ *        ply, the outcome labels of a game that ends (t - d mod T, d < L), stats and the reset, as there.  Then p_i += 1,
+ *        plies_max (optional device u64) = max(plies_max, p_i) -- the plies the most advanced row has written -- and
+ *        the row's tree is set up afresh on the position reached (what mnk_puct_begin writes: the root alone, its
+ *        evaluation pending), that root is the leaf, fresh[i] = 1.
+ *   4. a root without a legal cell (only a state handed in has one): MNK_ERR_VISITS, err[1] = i; nothing of the row
+ *      changes -- no backup, no ring record, p_i stays -- and it shows its root again, fresh[i] = 0, in every launch.  The
+ *      same holds for a row whose root has no visit on a free cell of planes when its budget is spent (a workspace that
+ *      was not set up on this position).  A selection that finds no leaf (a full tree: impossible in a workspace that
+ *      mnk_puct_begin set up, where nodes <= n_root <= iterations while the budget is unspent) leaves nothing pending, so
+ *      the row's n_root cannot advance: it shows its root again and reports MNK_ERR_VISITS in every launch as well.
+ * So with full_threshold = 2^32 and rows that start together, iterations + 1 launches are one ply of mnk_puct_begin,
+ * iterations + 1 mnk_puct_step and mnk_search_selfplay_step, bit for bit, without the two launches around the search.
+ * fresh (optional u8 [N]) tells the caller which rows of the next evaluator call are roots.  Rows are not in step: ring
+ * slot (t, i) is written when row i gets there, so a slot that a row has not reached yet holds whatever it held (z
+ * unknown in a new ring: weight 0).  T >= C; temp_plies >= 0; c as in mnk_puct_step.  One wave per row; every id read
+ * from the workspace is clamped to the row.  Every host check runs before anything is enqueued. */
+int mnk_search_selfplay_advance(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies, int64_t T,
+                                uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs,
+                                int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh, uint64_t* plies_max, int64_t* stats,
+                                int32_t* err, void* stream);
 /* A minibatch of ring records: sample b is the flat id idx[b] = t*N + i (negative ids wrap, an id outside [0, T*N) sets
  * MNK_ERR_ACTION_RANGE as in mnk_gather_obs and gives zero planes, policy, value and weight) under symmetry s = sym[b]
  * (sym int8 [B] or NULL = the identity).  Output cell (r, c) reads source cell (r', c'): start from (r, c); if s & 4,

@@ -8,80 +8,7 @@
 // draws and losses in the backup (a 2-bit proof per node, propagated up the leaf's path).  The rule: include/mnk_hip.h.
 #include "mnk_host.h"
 #include "mnk_wave_rows.h"
-
-// One tree node (12 B).  w is from the view of the player who moved into the node.
-struct MnkPuctNode {
-  uint32_t n;
-  float w;
-  uint32_t info;  // the move into the node | proof << 12 (k_puct_step_solver only; from w's point of view, 0: unknown,
-                  // 1: WIN, 2: DRAW, 3: LOSS) | term << 16 (0: not terminal; 1: the move won; 2: it filled the board) |
-                  // the parent's id << 18 (what k_puct_rebase marks a subtree by; the root's is 0)
-};
-#define MNK_PUCT_PROOF(info) (((info) >> 12) & 3u)
-#define MNK_PUCT_TERM(info) (((info) >> 16) & 3u)
-#define MNK_PUCT_PARENT(info) ((info) >> 18)
-static_assert(sizeof(MnkPuctNode) == 12, "node record");
-
-// The workspace of one row, at row * L.row bytes (every part 16-byte aligned, the row 256-byte aligned):
-//   header   u32[4]          nodes created, leaf depth, state (bit 0: a backup is pending; bits 1-2: the leaf's term, with
-//                            the solver its proof;
-//                            bit 3: the pending evaluation is of a root that k_puct_rebase carried over -- it only
-//                            renews the root's priors), live (the root has a legal cell)
-//   root     u32[2][NWg]     the root's guard-column bit planes (plane 0 = the root's side to move), NWg = MnkGeom::NW
-//   leaf     u32[2][NWg]     the pending leaf's planes
-//   path     u16[I + 2]      node ids root .. leaf
-//   node     MnkPuctNode[I + 1]
-//   prior    f32[I + 1][C]   the evaluator's prior of each legal cell of node v, at v * C (slot = node id)
-//   child    u16[I + 1][C]   the child of node v through each cell: 0 = none yet (node 0, the root, is never a child),
-//                            0xFFFF = an occupied cell
-// and, with Lv > 1 leaves per evaluation, behind all of that the state of slots 1 .. Lv - 1 (slot 0's is the header's
-// depth and state, `leaf` and `path`):
-//   xhdr     u32[Lv - 1][2]       leaf depth, state
-//   xleaf    u32[Lv - 1][2][NWg]  the slot's pending leaf's planes
-//   xpath    u16[Lv - 1][..]      its path, `pstride` bytes apart
-// About (I + 1) * 6 * C bytes per row.  The host (mnk_puct_workspace_bytes) and the kernels share this one function.
-struct MnkPuctLayout {
-  int64_t root, leaf, path, node, prior, child, xhdr, xleaf, xpath, pstride, row;
-};
-__host__ __device__ inline int64_t mnk_puct_al(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-__host__ __device__ inline MnkPuctLayout mnk_puct_layout(int NWg, int C, int I, int Lv = 1) {
-  MnkPuctLayout L;
-  L.root = 16;
-  L.leaf = L.root + 8 * NWg;
-  L.path = mnk_puct_al(L.leaf + 8 * NWg, 16);
-  L.node = mnk_puct_al(L.path + 2 * (int64_t)(I + 2), 16);
-  L.prior = mnk_puct_al(L.node + 12 * (int64_t)(I + 1), 16);
-  L.child = mnk_puct_al(L.prior + 4 * (int64_t)(I + 1) * C, 16);
-  L.row = mnk_puct_al(L.child + 2 * (int64_t)(I + 1) * C, 256);
-  L.pstride = mnk_puct_al(2 * (int64_t)(I + 2), 16);
-  L.xhdr = mnk_puct_al(L.child + 2 * (int64_t)(I + 1) * C, 16);
-  L.xleaf = mnk_puct_al(L.xhdr + 8 * (int64_t)(Lv - 1), 16);
-  L.xpath = mnk_puct_al(L.xleaf + 8 * (int64_t)NWg * (Lv - 1), 16);
-  if (Lv > 1) L.row = mnk_puct_al(L.xpath + L.pstride * (Lv - 1), 256);  // (Lv = 1: nothing behind `child`)
-  return L;
-}
-
-#define MNK_PUCT_ROWS 4  // rows (waves) per 256-lane workgroup
-#define MNK_PUCT_NONE 0xFFFFu
-
-// fsqrt((float)n) correctly rounded for a visit count n < 2^24.  The compiler lowers the square root of a converted
-// integer to a bare v_sqrt_f32, which may be an ulp off; sqrt(n) is compared with the midpoints around that result
-// exactly in f64 (a midpoint has 25 significant bits, its square 50) and the result moved by an ulp when it lies
-// outside.  (No midpoint is the square root of an integer below 2^48: there are no ties.)
-__device__ __forceinline__ float puct_sqrt_rn(uint32_t n) {
-  float r = __fsqrt_rn((float)n);
-  const uint32_t b = __float_as_uint(r);
-  const double dr = (double)r, dn = (double)n;
-  const double lo = (dr + (double)__uint_as_float(b ? b - 1u : 0u)) * 0.5;
-  const double hi = (dr + (double)__uint_as_float(b + 1u)) * 0.5;
-  if (__dmul_rn(lo, lo) > dn) r = __uint_as_float(b - 1u);
-  else if (__dmul_rn(hi, hi) < dn) r = __uint_as_float(b + 1u);
-  return r;
-}
-
-__device__ __forceinline__ float puct_read(const void* p, int dtype, int64_t q) {
-  return dtype == MNK_LOGITS_BF16 ? __uint_as_float((uint32_t)((const uint16_t*)p)[q] << 16) : ((const float*)p)[q];
-}
+#include "mnk_puct_tree.h"
 
 // ------------------------------------------------------------------ evaluation 0: the roots
 // row i of obs into guard-column bit planes in LDS (pos[2 * NW], the wave's own); returns its stone count
@@ -109,37 +36,6 @@ __device__ __forceinline__ int puct_row_planes(const MnkGeom& g, const void* obs
 #pragma unroll
   for (int w = 0; w < NW; ++w) stones += __popc(pos[w] | pos[NW + w]);
   return stones;
-}
-
-// pos as the row's root planes and as its pending leaf's
-template <int NW>
-__device__ __forceinline__ void puct_row_root(unsigned char* row, const MnkPuctLayout& L, const uint32_t* pos, int NWg,
-                                              int lane) {
-  uint32_t* root = (uint32_t*)(row + L.root);
-  uint32_t* leaf = (uint32_t*)(row + L.leaf);
-  for (int q = lane; q < 2 * NWg; q += 64) {
-    const uint32_t v = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
-    root[q] = v;
-    leaf[q] = v;
-  }
-}
-
-// a fresh tree: the root node alone, its evaluation pending
-template <int NW>
-__device__ __forceinline__ void puct_row_fresh(unsigned char* row, const MnkPuctLayout& L, const uint32_t* pos, int NWg,
-                                               bool legal, int lane) {
-  puct_row_root<NW>(row, L, pos, NWg, lane);
-  if (lane == 0) {
-    uint32_t* hdr = (uint32_t*)row;
-    hdr[0] = 1u;                     // the root
-    hdr[1] = 0u;                     // the leaf is the root
-    hdr[2] = 1u;                     // its evaluation is pending, not terminal
-    hdr[3] = legal ? 1u : 0u;        // a legal cell
-    ((uint16_t*)(row + L.path))[0] = 0;
-    MnkPuctNode r;
-    r.n = 0u; r.w = 0.0f; r.info = 0u;
-    *(MnkPuctNode*)(row + L.node) = r;
-  }
 }
 
 // slots 1 .. leaves - 1 of evaluation 0 are void: nothing pending, the root's view (pos) as batch rows i * leaves + j
@@ -405,66 +301,6 @@ k_puct_rebase_leaves(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I
 }
 
 // ------------------------------------------------------------------ one backup, then one selection (or the move)
-// The backup of one pending evaluation (state bit 0 set): batch row b of priors / values, the leaf's planes in pos (LDS).
-// SOLVER: the leaf's term is its proof (3: a proven loss of its mover, +1 for its side to move), and a proven leaf's
-// backup ends with the proofs of its path, leaf side first: one scan of a node's child row per level (the selection's
-// access shape, the children's info gathered, reduced over the wave), at most `depth` levels, over as soon as a node
-// stays unknown or was proven before.
-template <int NW, int CN, bool SOLVER = false>
-__device__ __forceinline__ void puct_backup(const MnkGeom& g, const uint32_t* pos, const uint16_t* path, MnkPuctNode* node,
-                                            float* prior, uint16_t* child, int nodes, int depth, uint32_t state,
-                                            const void* priors, int priors_dtype, const void* values, int values_dtype,
-                                            int64_t b, int lane) {
-  const int C = g.C;
-  const int lf = min((int)path[depth], nodes - 1);
-  const uint32_t term = (state >> 1) & 3u;
-  const bool renew = (state & 8u) != 0u;  // a carried root (k_puct_rebase): its priors again and nothing else
-  float v;
-  if (term) {
-    v = term == 1u ? -1.0f : 0.0f;  // the mover into the leaf won: a loss for its side to move
-    if constexpr (SOLVER)
-      if (term == 3u) v = 1.0f;
-  } else {
-    v = puct_read(values, values_dtype, b);
-    float* pr = prior + (int64_t)lf * C;
-    uint16_t* cl = child + (int64_t)lf * C;
-    for (int a = lane; a < C; a += 64) {
-      const bool occ = row_stone<CN>(g, pos, a) || row_stone<CN>(g, pos + NW, a);
-      if (!renew) cl[a] = occ ? (uint16_t)MNK_PUCT_NONE : (uint16_t)0;
-      if (!occ) pr[a] = puct_read(priors, priors_dtype, b * C + a);
-    }
-  }
-  for (int p = lane; p <= depth && !renew; p += 64) {  // depth - p odd: the mover into path[p] is the leaf's side to move
-    MnkPuctNode* k = &node[min((int)path[p], nodes - 1)];
-    k->n += 1u;
-    k->w = __fadd_rn(k->w, ((depth - p) & 1) ? v : -v);
-  }
-  row_wave_sync();
-  if constexpr (SOLVER) {
-    for (int p = depth - 1; p >= 0 && term; --p) {
-      const int x = min((int)path[p], nodes - 1);
-      const uint32_t info = node[x].info;
-      if (MNK_PUCT_PROOF(info)) break;
-      const uint16_t* cl = child + (int64_t)x * C;
-      bool win = false, open = false, held = false;  // a child that is WIN / missing or unknown / not LOSS
-      for (int a = lane; a < C; a += 64) {
-        const uint32_t ch = cl[a];
-        if (ch == MNK_PUCT_NONE) continue;
-        const uint32_t pf = ch ? MNK_PUCT_PROOF(node[min((int)ch, nodes - 1)].info) : 0u;
-        win |= pf == 1u;
-        open |= pf == 0u;
-        held |= pf != 3u;
-      }
-      uint32_t pf = 3u;  // a move that wins: the mover into x has lost
-      if (!__ballot(win)) {
-        if (__ballot(open)) break;
-        pf = __ballot(held) ? 2u : 1u;
-      }
-      if (lane == 0) node[x].info = info | (pf << 12);
-      row_wave_sync();  // (the next level gathers this proof)
-    }
-  }
-}
 
 // The move, the visits, the root value of row i, after its last backup.
 // SOLVER: the counts are the adjusted ones (`keep`: 0 = every child's n, 1 = the WIN children's, 2 = all but the LOSS
@@ -546,92 +382,6 @@ __device__ __forceinline__ void puct_move(int C, const MnkPuctNode* node, const 
     actions[i] = move;
     if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
   }
-}
-
-template <int NW>
-__device__ __forceinline__ void puct_env_root(MnkEnv<NW>& e, const uint32_t* root, int NWg) {
-  int stones = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    e.p[0][w] = w < NWg ? root[w] : 0u;
-    e.p[1][w] = w < NWg ? root[NWg + w] : 0u;
-    stones += __popc(e.p[0][w] | e.p[1][w]);
-  }
-  e.meta = (uint32_t)stones << 1;
-}
-
-// ------------------------------------------------------------------ the Gumbel root (k_puct_step_gumbel only)
-// What the root of row i reads besides the tree: its row of gscore (mnk_puct_gumbel_root), the table of considered visits
-// (mnk_puct_gumbel_schedule, [considered + 1][I]) and the constants of sigma.
-struct MnkPuctGumbel {
-  const float* gs;
-  const uint16_t* table;
-  int considered;
-  float c_visit, c_scale;
-};
-
-// The root's child of maximal key among the free cells of `want` visits -- LAST: of the most visits; else of
-// table[min(considered, F)][n_root - 1] visits -- or, when no free cell has that count, among all free cells; ties to the
-// lowest cell, 0x7fffffff for a root without a free cell.  Wave-uniform.  Two scans of the root's child row in the access
-// shape of the scoring loop (cells over the lanes, a child's record gathered): the first for F and the most visits, the
-// second for the two maxima, each reduced by __shfl_xor.
-template <bool LAST>
-__device__ __forceinline__ int puct_gumbel_pick(int C, int I, const MnkPuctNode* node, const uint16_t* cl, int nodes,
-                                                const MnkPuctGumbel& gm, int lane, uint32_t* maxn_out = nullptr) {
-  uint32_t F = 0u, maxn = 0u;
-  for (int a = lane; a < C; a += 64) {
-    const uint32_t ch = cl[a];
-    if (ch == MNK_PUCT_NONE) continue;
-    ++F;
-    if (ch) maxn = max(maxn, node[min((int)ch, nodes - 1)].n);
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    F += (uint32_t)__shfl_xor((int)F, off, 64);
-    maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
-  }
-  if (maxn_out) *maxn_out = maxn;
-  uint32_t want = maxn;
-  if (!LAST) {  // (clamped: whatever the workspace holds, the read stays inside the table)
-    const int t = min((int)max(node[0].n, 1u) - 1, I - 1);
-    want = gm.table[(int64_t)min((uint32_t)gm.considered, F) * I + t];
-  }
-  const float sigma = __fmul_rn(__fadd_rn(gm.c_visit, (float)maxn), gm.c_scale);
-  float bk = 0.0f, ak = 0.0f;  // the best key among the cells of `want` visits / among all free cells
-  int ba = 0x7fffffff, aa = 0x7fffffff;
-  for (int a = lane; a < C; a += 64) {
-    const uint32_t ch = cl[a];
-    if (ch == MNK_PUCT_NONE) continue;
-    float key = gm.gs[a];
-    uint32_t na = 0u;
-    if (ch) {
-      const MnkPuctNode k = node[min((int)ch, nodes - 1)];
-      na = k.n;
-      if (na) key = __fadd_rn(key, __fmul_rn(sigma, __fdiv_rn(k.w, (float)na)));
-    }
-    if (na == want && (ba == 0x7fffffff || key > bk)) {  // (a rises: ">" keeps the lowest cell of a tie)
-      bk = key;
-      ba = a;
-    }
-    if (aa == 0x7fffffff || key > ak) {
-      ak = key;
-      aa = a;
-    }
-  }
-#pragma unroll
-  for (int off = 32; off; off >>= 1) {
-    const float ob = __shfl_xor(bk, off, 64), oa = __shfl_xor(ak, off, 64);
-    const int obc = __shfl_xor(ba, off, 64), oac = __shfl_xor(aa, off, 64);
-    if (obc != 0x7fffffff && (ba == 0x7fffffff || ob > bk || (ob == bk && obc < ba))) {
-      bk = ob;
-      ba = obc;
-    }
-    if (oac != 0x7fffffff && (aa == 0x7fffffff || oa > ak || (oa == ak && oac < aa))) {
-      ak = oa;
-      aa = oac;
-    }
-  }
-  return __builtin_amdgcn_readfirstlane(ba != 0x7fffffff ? ba : aa);
 }
 
 // a sum over the wave, the same value in every lane
@@ -726,134 +476,6 @@ __device__ __forceinline__ void puct_move_gumbel(int C, int I, const MnkPuctNode
     if (y_of(a, y)) se += exp(y - my);
   se = puct_wave_sum(se);
   for (int a = lane; a < C; a += 64) policy[i * C + a] = y_of(a, y) ? (float)(exp(y - my) / se) : 0.0f;
-}
-
-// One walk from the root (e = the root's position on entry, the leaf's on return; wave-uniform): the new pending state
-// (0: no leaf), the leaf's depth in d, its path in path[1 .. d].  A new leaf becomes node `nodes`.
-// VL: the walk of a slot under the virtual visits of the round's earlier slots.  vl(x) is counted from their stored paths
-// (the tree has one path to a node: slot l's path holds x, a node at depth t, iff its entry t is x): `share` = the
-// earlier slots whose path runs through the walk's node v, slot l's path and depth are lane l's epath / edepth, and a
-// child's vl = how many slots of `share` go on to it.  nodes0 = the node count when the round began: a node of a higher
-// id that is not terminal has no evaluation yet, and reaching it ends the walk without a leaf.
-// SOLVER: a child that is proven LOSS (a move proven to lose for the player making it) is a candidate only when every
-// child is -- `bc`, the class of the best cell so far (1: not such a child), orders before the score -- and the walk ends
-// in a child with a proof as it ends in a terminal one; the new pending state carries the proof in the term's bits.
-// GUMBEL: at the root the cell is puct_gumbel_pick's (gm: the row's Gumbel inputs); from the chosen child on, the walk
-// below.
-template <int NW, int CN, int CK, bool VL, bool SOLVER = false, bool GUMBEL = false>
-__device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, int I, float c, MnkPuctNode* node,
-                                              const float* prior, uint16_t* child, uint16_t* path, int& nodes, int& d,
-                                              int lane, int nodes0 = 0, uint32_t share = 0u,
-                                              const uint16_t* epath = nullptr, int edepth = 0,
-                                              const MnkPuctGumbel* gm = nullptr) {
-  const int C = g.C;
-  int v = 0;
-  for (;;) {
-    uint32_t nxt = 0u;  // VL: where lane l's slot goes from v (0: not through v, or its leaf is v)
-    uint32_t nv = node[v].n;
-    if (VL) {
-      if (lane < MNK_PUCT_LEAVES_MAX && ((share >> lane) & 1u) && edepth > d) nxt = epath[d + 1];
-      nv += (uint32_t)__popc(share);
-    }
-    // the slots' next nodes as wave-uniform values, read here where every lane is active (the per-cell loop below is not)
-    uint32_t nx[MNK_PUCT_LEAVES_MAX];
-    if (VL) {
-#pragma unroll
-      for (int l = 0; l < MNK_PUCT_LEAVES_MAX; ++l) nx[l] = (uint32_t)__builtin_amdgcn_readlane((int)nxt, l);
-    }
-    const float sq = puct_sqrt_rn(nv);
-    const float* pr = prior + (int64_t)v * C;
-    const uint16_t* cl = child + (int64_t)v * C;
-    float best = 0.0f;
-    int ba = 0x7fffffff;
-    [[maybe_unused]] int bc = 0;
-    [[maybe_unused]] bool picked = false;  // GUMBEL, at the root: ba is the cell already, the same in every lane
-    if constexpr (GUMBEL) {
-      if (v == 0) {
-        ba = puct_gumbel_pick<false>(C, I, node, cl, nodes, *gm, lane);
-        picked = true;
-      }
-    }
-    if (!picked)  // (the loop keeps its indentation: below this line the scoring is the text it was)
-    for (int a = lane; a < C; a += 64) {
-      const uint32_t ch = cl[a];
-      if (ch == MNK_PUCT_NONE) continue;
-      uint32_t na = 0u;
-      float wa = 0.0f;
-      [[maybe_unused]] int cls = 1;
-      if (ch) {
-        const int kk = min((int)ch, nodes - 1);
-        const MnkPuctNode k = node[kk];
-        na = k.n;
-        wa = k.w;
-        if constexpr (SOLVER) cls = MNK_PUCT_PROOF(k.info) != 3u;
-        if (VL && share) {
-          uint32_t vl = 0u;  // (nx is 0, never a child's id, for a slot that is not in `share`)
-#pragma unroll
-          for (int l = 0; l < MNK_PUCT_LEAVES_MAX; ++l) vl += nx[l] == (uint32_t)kk;
-          na += vl;
-          wa = __fadd_rn(wa, -(float)vl);
-        }
-      }
-      const float q = na ? __fdiv_rn(wa, (float)na) : 0.0f;
-      const float s = __fadd_rn(q, __fdiv_rn(__fmul_rn(__fmul_rn(c, pr[a]), sq), (float)(1u + na)));
-      if constexpr (SOLVER) {
-        if (ba == 0x7fffffff || cls > bc || (cls == bc && s > best)) {
-          best = s;
-          ba = a;
-          bc = cls;
-        }
-      } else if (ba == 0x7fffffff || s > best) {  // (a rises: ">" keeps the lowest cell of a tie)
-        best = s;
-        ba = a;
-      }
-    }
-#pragma unroll
-    for (int off = 32; off; off >>= 1) {
-      const float ob = __shfl_xor(best, off, 64);
-      const int oa = __shfl_xor(ba, off, 64);
-      if constexpr (SOLVER) {
-        const int oc = __shfl_xor(bc, off, 64);
-        if (oa != 0x7fffffff &&
-            (ba == 0x7fffffff || oc > bc || (oc == bc && (ob > best || (ob == best && oa < ba))))) {
-          best = ob;
-          ba = oa;
-          bc = oc;
-        }
-      } else if (oa != 0x7fffffff && (ba == 0x7fffffff || ob > best || (ob == best && oa < ba))) {
-        best = ob;
-        ba = oa;
-      }
-    }
-    const int a = __builtin_amdgcn_readfirstlane(ba);
-    if (a == 0x7fffffff) return 0u;  // (an evaluated non-terminal node always has a legal cell)
-    const uint32_t ch = cl[a];
-    const MnkPly ply = env_play<NW, CN, CK, true>(g, e, a, false);
-    ++d;
-    if (ch == 0u) {  // a new node: the leaf
-      const uint32_t term = ply.win ? 1u : (ply.done ? 2u : 0u);
-      if (lane == 0) {
-        MnkPuctNode k;
-        k.n = 0u; k.w = 0.0f; k.info = (uint32_t)a | (term << 16) | ((uint32_t)v << 18);
-        if constexpr (SOLVER) k.info |= term << 12;
-        node[nodes] = k;
-        child[(int64_t)v * C + a] = (uint16_t)nodes;
-        path[d] = (uint16_t)nodes;
-      }
-      ++nodes;
-      return 1u | (term << 1);
-    }
-    const int k = min((int)ch, nodes - 1);
-    if (lane == 0) path[d] = (uint16_t)k;
-    const uint32_t term = SOLVER ? MNK_PUCT_PROOF(node[k].info) : MNK_PUCT_TERM(node[k].info);  // (a constant choice)
-    if (term) return 1u | (term << 1);  // an existing terminal child (SOLVER: a proven one): the leaf again
-    if (VL) {
-      if (k >= nodes0) return 0u;  // created in this round: not evaluated yet
-      share = (uint32_t)__ballot(nxt == (uint32_t)k);
-    }
-    v = k;
-    if (d >= I) return 0u;  // (cannot happen: a path holds at most one new node per iteration)
-  }
 }
 
 // One wave per row, MNK_PUCT_ROWS rows per workgroup.  Selection is wave-uniform: the position in registers, the scores

@@ -32,6 +32,7 @@ SEARCH_PLAYOUTS_MAX = 256  # MNK_SEARCH_PLAYOUTS_MAX: the largest playout count 
 PUCT_ITERS_MAX = 2048  # MNK_PUCT_ITERS_MAX: the largest iteration budget of mnk_puct_begin / mnk_puct_step
 PUCT_LEAVES_MAX = 16  # MNK_PUCT_LEAVES_MAX: the most leaves per row and evaluation of the mnk_puct_*_leaves entry points
 STREAM_GUMBEL = 8  # MNK_STREAM_GUMBEL: the Gumbel variables of the PUCT player's Gumbel root (mnk_puct_gumbel_root)
+STREAM_BUDGET = 9  # MNK_STREAM_BUDGET: is a self-play ply searched with the full budget? (mnk_search_selfplay_advance)
 PUCT_CONSIDERED_MAX = 1024  # MNK_PUCT_CONSIDERED_MAX: the most root moves mnk_puct_step_gumbel considers
 PUCT_NOISE_TRIES = 16  # MNK_PUCT_NOISE_TRIES: the most Marsaglia-Tsang candidates per cell of mnk_puct_root_noise
 STATS_REPLICAS, STATS_STRIDE, STATS_COUNTERS = 64, 8, 5
@@ -135,6 +136,11 @@ SIGNATURES = {
     # planes, ring visits, ring z, obs, obs dtype, legal mask, stats, err, stream
     "mnk_search_selfplay_step": [_vp, _vp, _i64, _i, _i, _i, _vp, _i, _u64, _vp, _u64, _vp, _i64, _i64, _vp, _vp, _vp, _vp,
                                  _i, _vp, _vp, _vp, _vp],
+    # workspace, planes, meta, N, m, n, k, iterations, fast iterations, full threshold, priors, priors dtype, values, values
+    # dtype, c, temp_plies, seed, seed_dev, env_id0, row plies (u64 [N]), T, ring planes, ring visits, ring z, leaf obs, leaf
+    # dtype, leaf mask, fresh (u8 [N]), plies max (u64 [1]), stats, err, stream
+    "mnk_search_selfplay_advance": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i, _u64, _vp, _i64,
+                                    _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     # ring planes, ring visits, ring z, T, N, m, n, idx, sym, B, obs, obs dtype, legal mask, policy, value, weight, err, stream
     "mnk_search_gather": [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],

@@ -30,6 +30,9 @@ proven wins where there is one.
 mnk_puct_step_gumbel) and plays through ``mnk_search_selfplay_step_moves``: the move is the search's own -- a sample from
 the improved policy, drawn at the ring's ply counter like the noise -- and the ring's u16 visits are that policy scaled to
 65 535, which ``mnk_search_gather`` turns back into the target.  ``temp_plies`` is then not read.
+
+``AsyncSearchSelfPlay`` (below) is the same loop without the lockstep: one launch per evaluator call, a search budget per
+row and ply, rows that play on as soon as their search is done.
 """
 from typing import Dict
 
@@ -147,3 +150,126 @@ class SearchSelfPlay:
         self.stats.copy_(state["stats"])
         self.reset_trees()
         self.env.observe_into(obs=self.obs, mask=self.mask, flip_side=(self.env._meta & 1).to(torch.int64))
+
+
+class AsyncSearchSelfPlay:
+    """Search self-play with a search budget per row and ply (the rule: include/mnk_hip.h, mnk_search_selfplay_advance).
+
+    ``SearchSelfPlay`` moves every row in lockstep: ``iterations + 1`` evaluator calls, then one ply of every row.  Here
+    a round is one evaluator call on every row's leaf and ONE launch that backs the evaluation up and, row by row,
+    either selects the next leaf or -- when the row's budget for its ply is spent -- plays the ply, records it, labels and
+    resets a finished game and starts the search of the position reached, whose root is the row's leaf of the next round.
+    Rows finish their searches at different times and go on at once, so plies can have different budgets ("playout cap
+    randomisation"): a ply is searched with ``iterations`` with probability ``full_prob`` and becomes a policy and value
+    target, and with ``fast_iterations`` otherwise, when its ring record carries zero visits -- ``SearchReplayBuffer``'s
+    gather then hands out an all-zero policy for it -- and is a value target only.  Which plies are full is a function of
+    (seed, row id, the row's ply count) alone (``mnk_hip.STREAM_BUDGET``).  With ``full_prob=1`` (the default) and
+    ``fast_iterations=None`` (= ``iterations``), ``P * (iterations + 1)`` rounds leave exactly what
+    ``SearchSelfPlay(same seed).play(P)`` leaves, with two launches fewer per ply.
+
+    ``row_plies`` (int64 ``[N]``) holds the plies every row has played since construction; row i's next record goes to
+    ring slot ``row_plies[i] % capacity``.  ``fresh`` (uint8 ``[N]``) tells which rows of ``leaf_obs`` / ``leaf_mask`` --
+    the batch the next evaluator call sees -- are roots: an evaluator that perturbs root priors reads it, there is no
+    "first call of an act" any more.  ``buffer.plies`` is the ply count of the most advanced row (a device word the
+    kernel keeps), which is what ``buffer.sample`` draws below: a slot a slower row has not written yet holds an unknown
+    outcome, weight 0.  ``buffer.plies_host`` advances by one per round: an upper bound of that count, exact only in
+    what ``sample`` uses it for -- whether anything was launched at all.  During the first ``fast_iterations + 1`` rounds
+    no row has played a ply yet and ``buffer.plies`` is still 0 while ``plies_host`` is not: a ``sample()`` in that window
+    is not refused as empty, every id it draws wraps to the ring's last slot, and that slot holds an unknown outcome, so
+    the whole batch has weight 0 -- harmless to a weighted loss, and over once the first ply is played.
+
+    No ``reuse``, ``leaves``, ``root_noise``, ``solver`` or ``gumbel`` yet."""
+
+    def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
+                 fast_iterations: int = None, full_prob: float = 1.0, c: float = 1.25, temp_plies: int = None,
+                 capacity: int = None, seed=None, leaf_dtype=torch.float32, device="cuda"):
+        self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
+        C = self.m * self.n
+        self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
+        if self.temp_plies < 0:
+            raise ValueError(f"temp_plies must be >= 0, got {temp_plies}")
+        if self.num_envs < 1:
+            raise ValueError(f"num_envs must be >= 1, got {num_envs}")
+        if not mnk_hip.geometry_supported(self.m, self.n, self.k) or self.n < 2:
+            raise ValueError(f"unsupported board {self.m}x{self.n} (k={self.k})")
+        capacity = 2 * C if capacity is None else int(capacity)
+        if capacity < C:
+            raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
+        # (the policy checks model / evaluator, iterations, c and leaf_dtype; it lends its evaluator call, its key and its
+        # workspace and is never asked to act)
+        self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
+                                       temperature=0, leaf_dtype=leaf_dtype, seed=seed)
+        self.iterations = self.policy.iterations
+        self.fast_iterations = self.iterations if fast_iterations is None else int(fast_iterations)
+        if not 1 <= self.fast_iterations <= self.iterations:
+            raise ValueError(f"fast_iterations must lie in [1, iterations] = [1, {self.iterations}], got {fast_iterations}")
+        self.full_prob = float(full_prob)
+        if not 0.0 <= self.full_prob <= 1.0:
+            raise ValueError(f"full_prob must lie in [0, 1], got {full_prob}")
+        self.full_threshold = int(round(self.full_prob * 2.0 ** 32))  # a ply is full iff its u32 lies below
+        self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
+        dev = self.env._dev
+        self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
+        self.sampler = self.policy._sampler
+        self.env.reset()
+        self.row_plies = torch.zeros(self.num_envs, dtype=torch.int64, device=dev)
+        self.fresh = torch.zeros(self.num_envs, dtype=torch.uint8, device=dev)
+        self.stats = torch.zeros((mnk_hip.STATS_REPLICAS, mnk_hip.STATS_STRIDE), dtype=torch.int64, device=dev)
+        self._roots = torch.empty((self.num_envs, 2, self.m, self.n), dtype=torch.float32, device=dev)
+        self.workspace, self.leaf_obs, self.leaf_mask, _ = self.policy._buffers(self.num_envs, self.m, self.n, dev)
+        self._begin()
+
+    def _begin(self) -> None:
+        """every row's search starts afresh on its current position (mnk_puct_begin): the roots are the next leaves"""
+        env = self.env
+        env.observe_into(obs=self._roots, flip_side=(env._meta & 1).to(torch.int64))
+        mnk_hip.call("mnk_puct_begin", mnk_hip.ptr(self._roots), mnk_hip.OBS_F32, self.num_envs, self.m, self.n, self.k,
+                     self.iterations, mnk_hip.ptr(self.workspace), mnk_hip.ptr(self.leaf_obs), self.policy._leaf_code,
+                     mnk_hip.ptr(self.leaf_mask), mnk_hip.stream_ptr(env._dev))
+        self.fresh.fill_(1)
+
+    def advance(self, rounds: int = 1) -> None:
+        """``rounds`` times: the evaluator on ``leaf_obs`` / ``leaf_mask``, then the kernel.  Enqueues work only;
+        ``torch.cuda.graph`` can capture it after one eager round when the evaluator is capturable"""
+        env, buf, N, C = self.env, self.buffer, self.num_envs, self.m * self.n
+        stream = mnk_hip.stream_ptr(env._dev)
+        for _ in range(int(rounds)):
+            priors, pcode, values, vcode = self.policy._evaluate(self.leaf_obs, self.leaf_mask, N, C)
+            seed, seed_dev, _, _, env_id0, _ = self.sampler.block()
+            mnk_hip.call("mnk_search_selfplay_advance", mnk_hip.ptr(self.workspace), mnk_hip.ptr(env._planes),
+                         mnk_hip.ptr(env._meta), N, self.m, self.n, self.k, self.iterations, self.fast_iterations,
+                         self.full_threshold, mnk_hip.ptr(priors), pcode, mnk_hip.ptr(values), vcode, self.policy.c,
+                         self.temp_plies, seed, seed_dev, env_id0, mnk_hip.ptr(self.row_plies), buf.capacity,
+                         mnk_hip.ptr(buf.planes), mnk_hip.ptr(buf.visits), mnk_hip.ptr(buf.z), mnk_hip.ptr(self.leaf_obs),
+                         self.policy._leaf_code, mnk_hip.ptr(self.leaf_mask), mnk_hip.ptr(self.fresh),
+                         mnk_hip.ptr(buf.plies), mnk_hip.ptr(self.stats), mnk_hip.ptr(env._err), stream)
+            buf.plies_host += 1
+
+    def note_replayed(self, rounds: int) -> None:
+        """a captured graph of ``advance`` has been replayed for ``rounds`` rounds in all: the host's count follows"""
+        self.buffer.plies_host += int(rounds)
+
+    def pop_game_stats(self) -> Dict[str, float]:
+        """games finished since the last call: games, black wins, white wins, draws and mean length (one sync)"""
+        tot = self.stats.sum(dim=0).tolist()
+        self.stats.zero_()
+        self.env.check_errors()
+        games = int(tot[0])
+        return {"games": games, "black_wins": int(tot[1]), "white_wins": int(tot[2]), "draws": int(tot[3]),
+                "mean_length": tot[4] / games if games else 0.0}
+
+    def state_dict(self) -> Dict[str, object]:
+        """env, ring, every row's ply count, the Philox key, ``temp_plies`` and the statistics.  The trees are not state:
+        ``load_state_dict`` starts every row's current search afresh, and since the budget of a ply is a function of (key,
+        row id, ply count) the search that starts again gets the budget the interrupted one had"""
+        return {"env": self.env.state_dict(), "buffer": self.buffer.state_dict(), "row_plies": self.row_plies.cpu(),
+                "seed": self.sampler.seed, "temp_plies": self.temp_plies, "stats": self.stats.cpu()}
+
+    def load_state_dict(self, state: Dict[str, object]) -> None:
+        self.env.load_state_dict(state["env"])
+        self.buffer.load_state_dict(state["buffer"])
+        self.row_plies.copy_(state["row_plies"])
+        self.sampler.seed = int(state["seed"])
+        self.temp_plies = int(state["temp_plies"])
+        self.stats.copy_(state["stats"])
+        self._begin()

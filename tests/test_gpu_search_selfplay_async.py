@@ -1,0 +1,264 @@
+"""GPU: search self-play with per-row budgets -- ``AsyncSearchSelfPlay`` / ``mnk_search_selfplay_advance``.  With every ply
+full it must leave, bit for bit, what the lockstep ``SearchSelfPlay`` of the same seed leaves; with mixed budgets it is
+compared round by round with the numpy rule (tests/search_selfplay_async_rule.py) on built-in and generic boards, every
+leaf dtype, bf16 priors and values and a device key word, the large boards from states near the end of games; a captured
+round replayed; a ``state_dict`` round trip; the refusals of the host and the row without a legal cell."""
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from player_cases import DEV, hip  # noqa: F401 (hip: the fixture)
+from search_selfplay_async_rule import AsyncSelfPlayRule, exact_np
+
+pytestmark = pytest.mark.gpu
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "search_selfplay_async_starts.npz")
+FULL, FAST, THRESHOLD = 6, 2, 3 * 2 ** 30  # the mixed budgets: a ply is full with probability 3/4
+
+
+def exact_torch(C, out_dtype=torch.float32):
+    """a capturable evaluator of plain torch ops: dyadic per-cell priors on the legal cells, a value from stone counts
+    (every number a multiple of 1/16 below 2: exact in bfloat16 too)"""
+    table = (((torch.arange(C) * 37) % 16 + 1).float() / 16).to(DEV)
+
+    def evaluate(leaf_obs, leaf_mask):
+        cnt = leaf_obs.float().reshape(len(leaf_obs), 2, -1).sum(dim=2)
+        priors, values = leaf_mask.float() * table, (torch.remainder(cnt[:, 0] - 2 * cnt[:, 1], 5) - 2) / 4
+        return priors.to(out_dtype), values.to(out_dtype)
+
+    return evaluate
+
+
+def new_async(hip, board, N, seed, full=FULL, fast=FAST, full_prob=0.75, leaf_dtype=torch.float32,
+              out_dtype=torch.float32, **kw):
+    from selfplay.search_selfplay import AsyncSearchSelfPlay
+
+    m, n, k = board
+    return AsyncSearchSelfPlay(m, n, k, N, evaluator=exact_torch(m * n, out_dtype), iterations=full, fast_iterations=fast,
+                               full_prob=full_prob, seed=seed, leaf_dtype=leaf_dtype, **kw)
+
+
+def assert_same_state(sp, rule, what=""):
+    """ring, env, ply counts, statistics and the device's count of written plies against the rule"""
+    buf = sp.buffer
+    assert np.array_equal(buf.planes.cpu().numpy().view(np.uint64), rule.ring_planes), what + " ring planes"
+    assert np.array_equal(buf.visits.cpu().numpy().view(np.uint16), rule.ring_visits), what + " ring visits"
+    assert np.array_equal(buf.z.cpu().numpy(), rule.ring_z), what + " ring z"
+    assert np.array_equal(sp.env._planes.cpu().numpy().view(np.uint64), rule.planes()), what + " env planes"
+    assert np.array_equal(sp.env._meta.cpu().numpy().astype(np.int64) & 0xFFFFFFFF, rule.meta()), what + " env meta"
+    assert sp.row_plies.tolist() == rule.row_plies.tolist(), what + " row_plies"
+    assert sp.stats.sum(dim=0)[:5].tolist() == rule.stats.tolist(), what + " stats"
+    assert buf.plies.item() == rule.plies_max, what + " plies_max"
+
+
+# ----------------------------------------------------------------------------- 1. every ply full: the lockstep player
+@pytest.mark.parametrize("board,N,plies,capacity", [((3, 3, 3), 6, 2 * 9 + 5, None), ((9, 9, 5), 5, 81 + 5, 81)])
+def test_with_every_ply_full_it_is_the_lockstep_player(hip, board, N, plies, capacity):
+    from selfplay.search_selfplay import SearchSelfPlay
+
+    m, n, k = board
+    I = 6
+    lock = SearchSelfPlay(m, n, k, N, evaluator=exact_torch(m * n), iterations=I, seed=13, temp_plies=3, capacity=capacity)
+    lock.play(plies)
+    sp = new_async(hip, board, N, 13, full=I, fast=None, full_prob=1.0, temp_plies=3, capacity=capacity)
+    sp.advance(plies * (I + 1))
+    torch.cuda.synchronize()
+    for t in ("planes", "visits", "z", "plies"):
+        assert torch.equal(getattr(sp.buffer, t), getattr(lock.buffer, t)), t
+    assert torch.equal(sp.env._planes, lock.env._planes) and torch.equal(sp.env._meta, lock.env._meta)
+    assert torch.equal(sp.stats.sum(dim=0), lock.stats.sum(dim=0))
+    assert torch.equal(sp.leaf_obs, lock.obs) and torch.equal(sp.leaf_mask, lock.mask)  # the next roots
+    assert sp.fresh.tolist() == [1] * N and sp.row_plies.tolist() == [plies] * N
+    assert sp.buffer.plies.item() == plies
+    assert lock.pop_game_stats() == sp.pop_game_stats() and lock.buffer.visits.any()
+
+
+# ----------------------------------------------------------------------------- 2. mixed budgets against the rule
+# board, rows, leaf dtype, dtype of priors and values, device key word, temp_plies, rounds, start ("golden": a stored env
+# state near the end of games), seed.  The seeds were chosen on the CPU with the rule so that in every case a game ends
+# and fast and full plies are recorded; the small boards run more than two laps of their T = C ring.
+CASES = [
+    ((3, 3, 3), 7, torch.float32, torch.float32, False, 2, 130, None, 6),
+    ((9, 9, 5), 5, torch.bfloat16, torch.float32, False, 6, 1150, None, 6),
+    ((7, 7, 4), 5, torch.uint8, torch.float32, True, 4, 700, None, 6),
+    ((12, 12, 5), 3, torch.float32, torch.bfloat16, False, 4, 150, "golden", 6),
+    ((19, 19, 5), 3, torch.float32, torch.float32, False, 4, 150, "golden", 6),
+]
+ENV_ID0 = 3
+
+
+def start_state(board, start):
+    if start is None:
+        return None
+    m, n, k = board
+    with np.load(GOLDEN) as z:
+        return z[f"{m}x{n}x{k}_planes"], z[f"{m}x{n}x{k}_meta"]
+
+
+def new_rule(board, N, temp, seed, start, T=None):
+    m, n, k = board
+    rule = AsyncSelfPlayRule(m, n, k, N, T or m * n, FULL, FAST, THRESHOLD, 1.25, temp, seed, ENV_ID0)
+    state = start_state(board, start)
+    if state is not None:
+        rule.load(*state)
+        rule.begin()
+    return rule
+
+
+@functools.lru_cache(maxsize=None)
+def rule_trace(board, N, temp, rounds, start, seed):
+    """the rule's run of a case, computed once: (rule at the end, [(leaf_obs, leaf_mask, fresh) of every round])"""
+    rule = new_rule(board, N, temp, seed, start)
+    ev = exact_np(rule.C)
+    obs, mask = rule.view()
+    trace = []
+    for _ in range(rounds):
+        obs, mask, fresh = rule.advance(*ev(obs, mask))
+        trace.append((obs, mask, fresh))
+    return rule, trace
+
+
+def load_start(sp, board, start):
+    state = start_state(board, start)
+    if state is not None:
+        s = sp.state_dict()
+        s["env"]["planes"] = torch.from_numpy(state[0].view(np.int64))
+        s["env"]["meta"] = torch.from_numpy(state[1].astype(np.int64)).to(s["env"]["meta"].dtype)
+        sp.load_state_dict(s)
+
+
+@pytest.mark.parametrize("board,N,leaf_dtype,out_dtype,key_word,temp,rounds,start,seed", CASES)
+def test_mixed_budgets_equal_the_rule_round_by_round(hip, board, N, leaf_dtype, out_dtype, key_word, temp, rounds, start,
+                                                     seed):
+    m, n, k = board
+    assert N % 4  # a partial workgroup
+    rule, trace = rule_trace(board, N, temp, rounds, start, seed)
+    sp = new_async(hip, board, N, seed + 100 if key_word else seed, leaf_dtype=leaf_dtype, out_dtype=out_dtype,
+                   temp_plies=temp, capacity=m * n)
+    sp.sampler.env_id0 = ENV_ID0
+    if key_word:  # the device word replaces the host's key
+        sp.sampler.seed_dev = torch.tensor([seed], dtype=torch.int64, device=DEV)
+    load_start(sp, board, start)
+    assert sp.full_threshold == THRESHOLD
+    for r, (obs, mask, fresh) in enumerate(trace):
+        sp.advance(1)
+        assert sp.leaf_obs.dtype == leaf_dtype
+        assert np.array_equal(sp.leaf_obs.float().cpu().numpy(), obs), f"leaves, round {r}"
+        assert np.array_equal(sp.leaf_mask.cpu().numpy(), mask), f"masks, round {r}"
+        assert sp.fresh.tolist() == fresh.tolist(), f"fresh, round {r}"
+    assert_same_state(sp, rule)
+    assert sp.env._err.tolist() == [0, 0] and not rule.errors
+    assert rule.stats[0] > 0 and rule.fast_records > 0 and rule.full_records > 0
+    assert len(set(rule.row_plies.tolist())) > 1  # the rows are out of step
+    if start is None:
+        assert rule.row_plies.min() > 2 * m * n  # more than two laps of the ring
+    assert sp.buffer.plies_host == rounds >= sp.buffer.plies.item()  # the host's count is an upper bound
+
+
+# ----------------------------------------------------------------------------- 3. a captured round
+def test_a_captured_round_replayed_equals_eager_rounds(hip):
+    R, board, N, seed = 90, (3, 3, 3), 6, 21
+    eager = new_async(hip, board, N, seed, temp_plies=2, capacity=9)
+    eager.advance(1 + R)
+    sp = new_async(hip, board, N, seed, temp_plies=2, capacity=9)
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        sp.advance(1)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        sp.advance(1)
+    sp.buffer.plies_host -= 1  # (the capture itself ran nothing)
+    for _ in range(R):
+        graph.replay()
+    sp.note_replayed(R)
+    torch.cuda.synchronize()
+    for t in ("planes", "visits", "z", "plies"):
+        assert torch.equal(getattr(sp.buffer, t), getattr(eager.buffer, t)), t
+    assert torch.equal(sp.env._planes, eager.env._planes) and torch.equal(sp.env._meta, eager.env._meta)
+    assert torch.equal(sp.row_plies, eager.row_plies) and torch.equal(sp.stats, eager.stats)
+    assert torch.equal(sp.leaf_obs, eager.leaf_obs) and torch.equal(sp.leaf_mask, eager.leaf_mask)
+    assert torch.equal(sp.fresh, eager.fresh) and torch.equal(sp.workspace, eager.workspace)
+    assert sp.buffer.plies_host == eager.buffer.plies_host == 1 + R
+    assert len(set(eager.row_plies.tolist())) > 1 and eager.pop_game_stats()["games"] > 0
+
+
+# ----------------------------------------------------------------------------- 4. state_dict
+def test_a_restored_state_continues_as_the_rule_does(hip):
+    board, N, seed, temp, before, after = (3, 3, 3), 6, 9, 2, 47, 60
+    a = new_async(hip, board, N, seed, temp_plies=temp, capacity=9)
+    a.advance(before)
+    state = a.state_dict()
+    b = new_async(hip, board, N, seed + 1, temp_plies=0, capacity=9)
+    b.load_state_dict(state)
+    assert b.fresh.tolist() == [1] * N and b.temp_plies == temp and b.sampler.seed == seed
+    # the rule, loaded from the same state: SelfPlayRule.load, the ring, the ply counts, then fresh trees
+    rule = AsyncSelfPlayRule(3, 3, 3, N, 9, FULL, FAST, THRESHOLD, 1.25, temp, seed)
+    rule.load(state["env"]["planes"].numpy().view(np.uint64), state["env"]["meta"].numpy())
+    rule.ring_planes[:] = state["buffer"]["planes"].numpy().view(np.uint64)
+    rule.ring_visits[:] = state["buffer"]["visits"].numpy().view(np.uint16)
+    rule.ring_z[:] = state["buffer"]["z"].numpy()
+    rule.row_plies[:] = state["row_plies"].numpy()
+    rule.plies_max = int(state["buffer"]["plies"].item())
+    rule.stats[:] = state["stats"].sum(dim=0)[:5].numpy()
+    assert len(set(rule.row_plies.tolist())) > 1  # saved in the middle of searches that were out of step
+    obs, mask = rule.begin()
+    ev = exact_np(9)
+    for r in range(after):
+        obs, mask, fresh = rule.advance(*ev(obs, mask))
+        b.advance(1)
+        assert np.array_equal(b.leaf_obs.cpu().numpy(), obs) and b.fresh.tolist() == fresh.tolist(), f"round {r}"
+    assert_same_state(b, rule)
+    assert b.pop_game_stats()["games"] > 0
+
+
+# ----------------------------------------------------------------------------- 5. refusals
+def test_the_host_refuses_bad_budgets_before_anything_is_enqueued(hip):
+    lib = hip.lib
+    sp = new_async(hip, (3, 3, 3), 5, 1, capacity=9)
+    sp.advance(3)
+    torch.cuda.synchronize()
+    before = [t.clone() for t in (sp.workspace, sp.row_plies, sp.leaf_obs, sp.buffer.z, sp.env._meta)]
+    priors, values = exact_torch(9)(sp.leaf_obs, sp.leaf_mask)
+    priors, values = priors.contiguous(), values.contiguous()
+
+    def adv(T=9, full=FULL, fast=FAST, threshold=THRESHOLD):
+        buf = sp.buffer
+        fn = lib.load().mnk_search_selfplay_advance
+        return fn(lib.ptr(sp.workspace), lib.ptr(sp.env._planes), lib.ptr(sp.env._meta), 5, 3, 3, 3, full, fast, threshold,
+                  lib.ptr(priors), 0, lib.ptr(values), 0, 1.25, 2, 1, None, 0, lib.ptr(sp.row_plies), T, lib.ptr(buf.planes),
+                  lib.ptr(buf.visits), lib.ptr(buf.z), lib.ptr(sp.leaf_obs), 0, lib.ptr(sp.leaf_mask), lib.ptr(sp.fresh),
+                  lib.ptr(buf.plies), lib.ptr(sp.stats), lib.ptr(sp.env._err), lib.stream_ptr(DEV))
+
+    EINVAL = -1
+    assert adv(T=8) == EINVAL and adv(fast=FULL + 1) == EINVAL and adv(fast=0) == EINVAL
+    assert adv(threshold=2 ** 32 + 1) == EINVAL
+    torch.cuda.synchronize()
+    for was, now in zip(before, (sp.workspace, sp.row_plies, sp.leaf_obs, sp.buffer.z, sp.env._meta)):
+        assert torch.equal(was, now)
+    assert adv() == 0 and adv(threshold=2 ** 32) == 0 and adv(threshold=0, fast=1) == 0
+
+
+def test_a_root_without_a_legal_cell_is_reported_and_left_alone(hip):
+    lib = hip.lib
+    N = 5
+    sp = new_async(hip, (3, 3, 3), N, 4, capacity=9)
+    s = sp.state_dict()
+    # row 2 holds a full board without a run (x o x / x o o / o x x), handed in by state
+    black, white = [0, 2, 3, 7, 8], [1, 4, 5, 6]
+    bits = lambda cells: sum(1 << (a + a // 3) for a in cells)  # noqa: E731
+    s["env"]["planes"][0, 0, 2], s["env"]["planes"][1, 0, 2] = bits(black), bits(white)
+    s["env"]["meta"][2] = (9 << 1) | 1
+    sp.load_state_dict(s)
+    sp.advance(25)
+    torch.cuda.synchronize()
+    assert sp.env._err.tolist() == [lib.ERR_VISITS, 2]
+    assert sp.row_plies[2].item() == 0 and sp.fresh[2].item() == 0 and (sp.row_plies > 0).sum().item() == N - 1
+    assert sp.env._meta[2].item() == (9 << 1) | 1
+    assert sp.env._planes[:, 0, 2].tolist() == [bits(black), bits(white)]
+    assert (sp.buffer.z[:, 2] == lib.Z_UNKNOWN).all() and not sp.buffer.visits[:, 2].any()
+    assert sp.leaf_mask[2].sum().item() == 0 and sp.leaf_obs[2].sum().item() == 9  # its root, shown again
+    sp.env._err.zero_()
