@@ -19,6 +19,12 @@ CASES = {
     "19x19x5": ((19, 19, 5), 3, 32, (4, 16)),            # C = 361; fewer rows than a workgroup holds
     "round": ((9, 9, 5), 5, 8, (8,)),                    # I = L: a single round
     "long": ((9, 9, 5), 1, 2048, (16,)),                 # the largest budget and the most leaves, one row
+    # boards that share a built-in variant with a board of another row count (tests/test_gpu_variant_siblings.py)
+    "8x3x3": ((8, 3, 3), 16, 32, (4, 16)),               # <1,3,3> with 24 cells
+    "7x9x5": ((7, 9, 5), 8, 48, (4, 16)),                # <3,9,5> with 63 cells
+    "16x15x5": ((16, 15, 5), 4, 32, (4,)),               # <8,15,5> with 240 cells: a plane that fills its last word
+    "12x13x5": ((12, 13, 5), 3, 32, (4,)),               # <6,13,5> with 156 cells; a partial workgroup
+    "18x19x5": ((18, 19, 5), 3, 32, (4,)),               # <12,19,5> with 342 cells; a partial workgroup
 }
 PARAMS = [(name, L) for name, (_, _, _, Ls) in CASES.items() for L in Ls]
 
@@ -34,7 +40,7 @@ def positions(name):
                 out.append(o)
         obs = np.stack(out)
     else:
-        obs = random_positions(m, n, k, rows, rng, max_fill=0.5 if name == "4x6x3" else 0.25)
+        obs = random_positions(m, n, k, rows, rng, max_fill=0.5 if name in ("4x6x3", "8x3x3") else 0.25)
     if name in ("4x6x3", "9x9x5"):  # an empty board, and a full one (no legal cell: void slots only)
         obs[0] = 0
         obs[1, 0].reshape(-1)[::2], obs[1, 1].reshape(-1)[::2] = 1, 0

@@ -8,7 +8,7 @@ import numpy as np
 from playout_rule import has_run
 from player_cases import board
 from puct_solver_rule import SolverPuct
-from tactical_rule import random_positions
+from tactical_rule import random_positions, tactical_sets
 from test_gpu_puct_reuse import advance, exact_np
 
 C_PUCT, SEED, ENV_ID0 = 1.25, 47, 3
@@ -19,10 +19,19 @@ CASES = {
     "5x5x4": ((5, 5, 4), 16, 96),      # the generic form
     "9x9x5": ((9, 9, 5), 16, 128),     # late in the game: at most 12 free cells; C > 64
     "19x19x5": ((19, 19, 5), 4, 32),   # the multi-word form; one immediate win on the board
+    # the boards that share a built-in variant with a board of another row count (tests/line_rule.py): the batch of
+    # ``sibling_positions``, which needs seven rows -- a partial workgroup on the three large boards
+    "8x3x3": ((8, 3, 3), 16, 48),      # <1,3,3>: 24 cells for the variant's 9; a plane that fills its word exactly
+    "7x9x5": ((7, 9, 5), 8, 64),       # <3,9,5>: 63 cells for 81
+    "12x13x5": ((12, 13, 5), 7, 32),   # <6,13,5>: 156 cells for 169
+    "16x15x5": ((16, 15, 5), 7, 32),   # <8,15,5>: 240 cells for 225, 256 bits
+    "18x19x5": ((18, 19, 5), 7, 32),   # <12,19,5>: 342 cells for 361
 }
+SIBLINGS = ("8x3x3", "7x9x5", "12x13x5", "16x15x5", "18x19x5")
 LEAVES = (1, 4)
 
 
+@functools.lru_cache(maxsize=None)
 def drawn_board(m, n, k):
     """a full board [2, m, n] without a run of k of either side: stripes of k - 1 cells (or fewer, where no shift from row
     to row keeps them from lining up), so that a stone taken off the end of a stripe leaves a winning cell"""
@@ -45,10 +54,49 @@ def late_positions(m, n, k, rows, rng, most_free):
     return out
 
 
+def last_row_win(m, n, k, rng, more=2):
+    """the drawn board less the stone of one side at the end of a stripe of the other in row m - 1 -- the other side, to
+    move, completes a run that lies in that row -- and less ``more`` stones above it.  Returns (obs [2, m, n], the cell)"""
+    full = drawn_board(m, n, k)
+    for cell in range(m * n - 1, (m - 1) * n - 1, -1):
+        for side in (0, 1):
+            row = full[side, m - 1].copy()
+            if row[cell - (m - 1) * n]:
+                continue
+            row[cell - (m - 1) * n] = True
+            if has_run(row.reshape(1, 1, n), k)[0]:
+                while True:  # (the stones taken off above must leave the side to move no other run to complete)
+                    keep = np.ones(m * n, bool)
+                    keep[cell] = False
+                    keep[rng.choice((m - 1) * n, size=more, replace=False)] = False
+                    obs = (full[:: 1 if side == 0 else -1] & keep.reshape(m, n)).astype(np.float32)
+                    if tactical_sets(obs[None], k)[1].sum() == 1:
+                        return obs, cell
+    raise AssertionError((m, n, k))
+
+
+def sibling_positions(m, n, k, rows, rng):
+    """what a kernel that took the variant's own cell or row count for the board's would get wrong: one free cell; two
+    and three free cells (with two, neither side can complete a run: the board fills inside the search, a draw at m * n
+    stones); a full board; a win at once whose run lies in row m - 1 (three free cells); mid-game rows"""
+    assert rows >= 7
+    obs = np.zeros((rows, 2, m, n), np.float32)
+    for _ in range(4096):  # (on 8x3x3 every stone off the drawn board leaves a winning cell: the last try stands)
+        obs[:3] = late_positions(m, n, k, 3, rng, 4)
+        if not tactical_sets(obs[1:2], k)[0].any():
+            break
+    obs[3] = drawn_board(m, n, k)
+    obs[4], _ = last_row_win(m, n, k, rng)
+    obs[5:] = random_positions(m, n, k, rows - 5, rng, max_fill=0.5)
+    return obs
+
+
 @functools.lru_cache(maxsize=None)
 def _positions(name):
     (m, n, k), rows, _ = CASES[name]
     rng = np.random.default_rng(sum(map(ord, name)) + 1)
+    if name in SIBLINGS:
+        return sibling_positions(m, n, k, rows, rng)
     if name == "9x9x5":
         return late_positions(m, n, k, rows, rng, 12)
     if name == "19x19x5":

@@ -28,7 +28,12 @@ C_PUCT, SEED, ENV_ID0, STEP, ROWS = 1.25, 53, 3, 2, 6
 #        name      board      I   considered
 CASES = {"3x3x3": ((3, 3, 3), 8, 4),     # NW = 1, C = 9: no multiple of 4
          "9x9x5": ((9, 9, 5), 16, 8),    # C > 64: every per-cell loop takes two trips; a built-in variant
-         "5x5x4": ((5, 5, 4), 16, 4)}    # the generic form
+         "5x5x4": ((5, 5, 4), 16, 4),    # the generic form
+         # boards that share a built-in variant with a board of another row count (tests/test_gpu_variant_siblings.py):
+         # not square, and on the k = 5 ones the Philox layout (C + 3) & ~3 of a cell count the variant's board has not
+         "8x3x3": ((8, 3, 3), 16, 4), "7x9x5": ((7, 9, 5), 16, 8), "16x15x5": ((16, 15, 5), 16, 8),
+         "12x13x5": ((12, 13, 5), 8, 8), "18x19x5": ((18, 19, 5), 8, 8)}
+SIBLINGS = ("8x3x3", "7x9x5", "16x15x5", "12x13x5", "18x19x5")
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
 
 
@@ -239,10 +244,11 @@ def test_without_gumbel_an_act_is_launch_for_launch_the_act_it_was(hip, name, mo
 
 
 # ----------------------------------------------------------------------------- 5. search self-play
-def test_search_selfplay_with_a_gumbel_root_equals_the_rule(hip):
+def run_selfplay(hip, board, N, I, cons, plies):
+    """``plies`` plies of ``SearchSelfPlay(gumbel=cons)`` with a T = C ring against the self-play rule; returns it"""
     from selfplay.search_selfplay import SearchSelfPlay
 
-    m, n, k, N, I, cons, plies = 3, 3, 3, 8, 8, 4, 12
+    m, n, k = board
     C, T, seed = m * n, m * n, 13
     sp = SearchSelfPlay(m, n, k, N, evaluator=exact_torch(C), iterations=I, c=C_PUCT, capacity=T, seed=seed, device=DEV,
                         gumbel=cons)
@@ -267,6 +273,13 @@ def test_search_selfplay_with_a_gumbel_root_equals_the_rule(hip):
     b = sp.buffer.sample(64, generator=torch.Generator(device=DEV).manual_seed(1))
     assert torch.all((b["policy"].sum(dim=1) - 1).abs() < 1e-4)
     sp.env.check_errors()
+    return sp
+
+
+def test_search_selfplay_with_a_gumbel_root_equals_the_rule(hip):
+    m, n, k, N, I, cons, plies = 3, 3, 3, 8, 8, 4, 12
+    C, T = m * n, m * n
+    sp = run_selfplay(hip, (m, n, k), N, I, cons, plies)
 
     # an occupied action sets the error and the row is not played; so does one out of range
     lib = hip.lib

@@ -147,10 +147,10 @@ def test_a_captured_act_replayed_equals_eager(hip):
 # ----------------------------------------------------------------------------- 5. dtypes
 @pytest.mark.parametrize("dtype,leaf_dtype,out_dtype,L", [
     (torch.float32, torch.uint8, torch.bfloat16, 8), (torch.uint8, torch.bfloat16, torch.bfloat16, 2)])
-def test_narrow_dtypes_on_one_board(hip, dtype, leaf_dtype, out_dtype, L):
+def test_narrow_dtypes_on_one_board(hip, dtype, leaf_dtype, out_dtype, L, name="9x9x5"):
     """(the evaluator's priors are powers of two and its values eighths: exact in bfloat16)"""
-    (m, n, k), rows, I, _ = CASES["9x9x5"]
-    obs, want, leaves, _ = reference("9x9x5", L)
+    (m, n, k), rows, I, _ = CASES[name]
+    obs, want, leaves, _ = reference(name, L)
     rec = []
     pol = policy(hip, k, I, m * n, L, rec, leaf_dtype, out_dtype, step=2)
     got = gpu_act(pol, obs, dtype)

@@ -85,7 +85,21 @@ CASES = [
     ((7, 7, 4), 5, torch.uint8, torch.float32, True, 4, 700, None, 6),
     ((12, 12, 5), 3, torch.float32, torch.bfloat16, False, 4, 150, "golden", 6),
     ((19, 19, 5), 3, torch.float32, torch.float32, False, 4, 150, "golden", 6),
+    # boards that share a built-in variant with a board of another row count (tests/test_gpu_variant_siblings.py), from
+    # the empty board.  The rule gives 46 games, 122 fast and 345 full records, row plies 65..69 on 8x3x3 and 14 games,
+    # 193 fast and 559 full records, row plies 148..156 on 7x9x5
+    ((8, 3, 3), 7, torch.uint8, torch.bfloat16, True, 2, 400, None, 6),
+    ((7, 9, 5), 5, torch.bfloat16, torch.float32, False, 6, 900, None, 6),
+    # and from stored states: three rows after 30 / 70 / 120 / 150 plies of random play and two rows two stones short of a
+    # drawn board, which fill and are drawn at m * n stones (make_golden_search_selfplay_async.py) -- where a rule with the
+    # variant's own cell count goes another way (tests/test_search_selfplay_async_cpu.py)
+    ((7, 9, 5), 5, torch.float32, torch.float32, False, 4, 150, "golden", 6),
+    ((12, 13, 5), 5, torch.uint8, torch.float32, False, 4, 150, "golden", 6),
+    ((16, 15, 5), 5, torch.float32, torch.bfloat16, True, 4, 150, "golden", 6),
+    ((18, 19, 5), 5, torch.bfloat16, torch.float32, False, 4, 150, "golden", 6),
 ]
+SIBLING_BOARDS = ((8, 3, 3), (7, 9, 5), (12, 13, 5), (16, 15, 5), (18, 19, 5))
+SIBLING_CASES = [case for case in CASES if case[0] in SIBLING_BOARDS]
 ENV_ID0 = 3
 
 
@@ -160,9 +174,17 @@ def test_mixed_budgets_equal_the_rule_round_by_round(hip, board, N, leaf_dtype, 
 # ----------------------------------------------------------------------------- 3. a captured round
 def test_a_captured_round_replayed_equals_eager_rounds(hip):
     R, board, N, seed = 90, (3, 3, 3), 6, 21
-    eager = new_async(hip, board, N, seed, temp_plies=2, capacity=9)
+    def new():
+        # (the workspace is compared whole below, and it is allocated uninitialised: the bytes no kernel writes are
+        # what an earlier tensor left there, so both start from zeros and set their roots up again)
+        sp = new_async(hip, board, N, seed, temp_plies=2, capacity=9)
+        sp.workspace.zero_()
+        sp._begin()
+        return sp
+
+    eager = new()
     eager.advance(1 + R)
-    sp = new_async(hip, board, N, seed, temp_plies=2, capacity=9)
+    sp = new()
     side = torch.cuda.Stream()
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):

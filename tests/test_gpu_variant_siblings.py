@@ -6,10 +6,18 @@ a sibling board has no run-time compiled twin (mnk_jit_prepare returns early for
 with a wrong result there but the oracle and the numpy rules, so this module takes every kernel family to them -- the
 win scan line by line (every line and every would-be wrap of the board, through env.step, wrapper.step and the tactical
 sampler), the API kernels at ragged batch sizes into aligned and misaligned outputs, self-play, the fused rollout in
-every form the board has, the row players -- bit for bit.  What the siblings add to the square boards: a plane that
-fills its last 32-bit word exactly (16x15 = 256 bits, 8x3 = 32), a cell count that differs from the row's own (240 vs
-225, 342 vs 361, 63 vs 81), output rows of odd byte sizes (504 B, 168 B, masks of 63 / 21 / 18 B) and valid cells that
-stop before the variant's last row.
+every form the board has, the row players -- bit for bit.  The row players are the Monte Carlo and UCT players, plain
+PUCT, search self-play and its gather on 8x3x3, 7x9x5 and 16x15x5, and the later forms of the PUCT player on those
+three and on 12x13x5 and 18x19x5: a kept tree (``mnk_puct_rebase``: sequences one and two plies on, the smallest
+workspace and ``SearchSelfPlay(reuse=True)`` on 7x9x5), several leaves (L = 4 everywhere, 16 on the two small boards,
+a kept tree and narrow dtypes), proofs (``mnk_puct_step_solver`` on batches with a board that fills inside the search
+and a win in row m - 1), root noise on 7x9x5, the Gumbel root (the prep kernel, an act, two shards,
+``mnk_search_selfplay_step_moves`` over more than a lap of the ring) and ``mnk_search_selfplay_advance`` (mixed budgets
+round by round: 8x3x3 and 7x9x5 from the empty board; 7x9x5, 12x13x5, 16x15x5 and 18x19x5 from stored states with rows
+that fill the board and are drawn at m * n stones; the lockstep form on 7x9x5).  What the siblings add to the square
+boards: a plane that fills its last 32-bit word exactly (16x15 = 256 bits, 8x3 = 32), a cell count that differs from
+the row's own (240 vs 225, 342 vs 361, 63 vs 81), output rows of odd byte sizes (504 B, 168 B, masks of 63 / 21 / 18 B)
+and valid cells that stop before the variant's last row.
 
 Which (board, form) pairs exist, from the source (csrc/mnk_rollout.hip, mnk_rollout_ws.hip, mnk_rollout_pairw.hip,
 mnk_host.h) -- a pair that does not exist is not parametrised, nothing here skips:
@@ -32,6 +40,12 @@ import test_gpu_fused_draw as fd
 import test_gpu_fuzz as fz
 import test_gpu_playout as gpl
 import test_gpu_puct as gpu
+import test_gpu_puct_gumbel as ggu
+import test_gpu_puct_leaves as gle
+import test_gpu_puct_noise as gno
+import test_gpu_puct_reuse as gre
+import test_gpu_puct_solver as gso
+import test_gpu_search_selfplay_async as gas
 import test_gpu_search as gse
 import test_gpu_search_selfplay as gss
 import test_gpu_selfplay as gsp
@@ -54,6 +68,7 @@ SIBLINGS = lr.sibling_boards(square=False)     # 4..8 x 3 x 3, 7x9x5, 8x9x5, 12x
 SQUARES = lr.sibling_boards(non_square=False)  # the boards the rows are named after: controls
 CONTROL = (7, 9, 7)                            # off the list: <3,9,5> for the kernels that never look at k, run-time compiled otherwise
 PLAYER_BOARDS = [(8, 3, 3), (7, 9, 5), (16, 15, 5)]
+WIDE = [(12, 13, 5), (18, 19, 5)]              # the <6,13,5> and <12,19,5> variants for the later forms of the PUCT player
 FORMS = {"lane": "one lane per env", "pair": "two lanes per env", "pairw": "two lanes per env, words split",
          "ws2": "two waves per env group", "ws4": "four waves per env group"}
 
@@ -787,12 +802,12 @@ def test_monte_carlo_and_tree_search_players_equal_their_rules(hip, board):
                                                                  (16, 15, 5): ((40, 8, 1.0),)}[board])
 
 
-@pytest.mark.parametrize("board", PLAYER_BOARDS, ids=_id)
+@pytest.mark.parametrize("board", PLAYER_BOARDS + WIDE, ids=_id)
 def test_puct_player_equals_its_rule(hip, board):
     """``mnk_puct_begin`` / ``mnk_puct_step`` through ``PUCTSearchPolicy.act`` against puct_rule: actions, visits, root
     values and every leaf, every observation / leaf / prior dtype"""
-    gpu.test_exact_evaluator_equals_the_rule(hip, board, {(8, 3, 3): 16, (7, 9, 5): 8, (16, 15, 5): 4}[board],
-                                             {(8, 3, 3): 40, (7, 9, 5): 64, (16, 15, 5): 40}[board])
+    gpu.test_exact_evaluator_equals_the_rule(hip, board, {(8, 3, 3): 16, (7, 9, 5): 8, (16, 15, 5): 4}.get(board, 3),
+                                             {(8, 3, 3): 40, (7, 9, 5): 64, (16, 15, 5): 40}.get(board, 16))
 
 
 @pytest.mark.parametrize("board", PLAYER_BOARDS, ids=_id)
@@ -804,3 +819,95 @@ def test_search_self_play_and_its_gather_equal_the_rule(hip, board):
     assert [s for s in range(8) if sym_ok(s, m, n)] == [0, 1, 2, 3]
     gss.test_the_gather_equals_the_rule(hip, board)
     gss.run(hip, m, n, k, 4, m * n + 9, torch.uint8, 3, True)
+
+
+# ----------------------------------------------------------------------------- 6b. the later forms of the PUCT player
+#            board        rows  J   plies
+SEQUENCES = [((8, 3, 3), 16, 10, 12), ((7, 9, 5), 8, 16, 40), ((16, 15, 5), 4, 16, 6), ((12, 13, 5), 3, 8, 6),
+             ((18, 19, 5), 3, 8, 6)]
+
+
+@pytest.mark.parametrize("distance", [1, 2])
+@pytest.mark.parametrize("board,rows,J,plies", SEQUENCES, ids=_id)
+def test_a_kept_tree_over_a_sequence_of_plies_equals_its_rule(hip, board, rows, J, plies, distance):
+    """``mnk_puct_rebase`` through ``PUCTSearchPolicy(reuse=True)`` against puct_reuse_rule at every ply, the next root one
+    and two plies on; on the two small boards games end and their rows start again inside the sequence"""
+    resets, carried = gre.run_sequence(hip, board, rows, J, plies, distance)
+    assert (carried[1:, :, 0] > 1).any() and not carried[0].any()
+    if board in ((8, 3, 3), (7, 9, 5)):
+        assert (resets >= 1).any(), resets
+        assert (carried[1:, :, 0] == 0).any()
+
+
+def test_the_smallest_workspace_and_self_play_with_a_kept_tree_on_7x9x5(hip):
+    gre.test_the_smallest_workspace_truncates_at_every_ply(hip, (7, 9, 5), 6, 16)
+    gre.test_search_selfplay_with_reuse_equals_the_rule(hip, (7, 9, 5), 5, 16, 6)
+
+
+LEAVES = [(_id(b), L) for b in PLAYER_BOARDS + WIDE for L in ((4, 16) if b in ((8, 3, 3), (7, 9, 5)) else (4,))]
+
+
+@pytest.mark.parametrize("name,L", LEAVES)
+def test_several_leaves_per_evaluation_equal_their_rule(hip, name, L):
+    """``mnk_puct_begin_leaves`` / ``mnk_puct_step_leaves`` against puct_leaves_rule on the cases of
+    tests/puct_leaves_cases.py"""
+    assert (name, L) in gle.PARAMS
+    gle.test_an_act_equals_the_rule(hip, name, L)
+
+
+def test_several_leaves_with_a_kept_tree_and_narrow_dtypes(hip):
+    for distance in (1, 2):
+        gle.test_a_sequence_of_plies_with_a_kept_tree_equals_the_rule(hip, (7, 9, 5), 6, 16, distance)
+    gle.test_narrow_dtypes_on_one_board(hip, torch.float32, torch.uint8, torch.bfloat16, 4, name="16x15x5")
+    gle.test_narrow_dtypes_on_one_board(hip, torch.uint8, torch.bfloat16, torch.bfloat16, 4, name="16x15x5")
+
+
+@pytest.mark.parametrize("temperature", [0, 1])
+@pytest.mark.parametrize("L", gso.LEAVES)
+@pytest.mark.parametrize("board", PLAYER_BOARDS + WIDE, ids=_id)
+def test_the_solver_equals_its_rule(hip, board, L, temperature):
+    """``mnk_puct_step_solver`` against puct_solver_rule on ``puct_solver_cases.sibling_positions``: one, two and three
+    free cells (the board fills inside the search and the draw is proven at m * n stones), a full board, a win at once in
+    row m - 1, mid-game rows.  tests/test_puct_solver_cpu.py shows that the rule with the variant's own cell and row count
+    answers otherwise on these batches."""
+    assert _id(board) in gso.CASES
+    gso.test_an_act_equals_the_rule(hip, _id(board), L, temperature)
+
+
+@pytest.mark.parametrize("L", [1, 4])
+@pytest.mark.parametrize("temperature", [0, 1])
+def test_a_noisy_act_equals_its_rule_on_7x9x5(hip, temperature, L):
+    gno.test_a_noisy_act_equals_the_rule_on_the_kernels_priors(hip, (7, 9, 5), 8, temperature, L)
+
+
+@pytest.mark.parametrize("dtype", list(ggu.DTYPES))
+@pytest.mark.parametrize("name", ggu.SIBLINGS)
+def test_the_gumbel_root_equals_its_rule(hip, name, dtype):
+    """``mnk_puct_gumbel_root`` and ``mnk_puct_step_gumbel``: C = 63, 156 and 342 are no multiple of 4"""
+    ggu.test_the_prep_kernel_equals_the_rule(hip, name, dtype)
+    ggu.test_an_act_equals_the_rule_fed_with_the_kernels_gscore(hip, name, dtype)
+
+
+def test_two_gumbel_shards_equal_one_call_on_7x9x5(hip):
+    ggu.test_two_shards_equal_one_call(hip, "7x9x5")
+
+
+@pytest.mark.parametrize("board,N,I,cons", [((8, 3, 3), 7, 8, 4), ((7, 9, 5), 5, 8, 8)], ids=_id)
+def test_self_play_from_the_gumbel_roots_moves_equals_its_rule(hip, board, N, I, cons):
+    """``mnk_search_selfplay_step_moves`` against ``GumbelSelfPlayRule`` for more than a lap of the T = C ring"""
+    m, n, k = board
+    ggu.run_selfplay(hip, board, N, I, cons, m * n + 9)
+
+
+def test_the_lockstep_form_of_per_row_budgets_on_7x9x5(hip):
+    gas.test_with_every_ply_full_it_is_the_lockstep_player(hip, (7, 9, 5), 5, 63 + 5, 63)
+
+
+@pytest.mark.parametrize("case", gas.SIBLING_CASES, ids=lambda c: _id(c[0]) + ("-stored" if c[7] else ""))
+def test_per_row_budgets_equal_their_rule_round_by_round(hip, case):
+    """``mnk_search_selfplay_advance`` against ``AsyncSelfPlayRule``: games end, fast and full plies are recorded, the rows
+    are out of step and, from the empty board (the two small boards), the T = C ring goes round more than twice; 7x9x5
+    and the three large boards start from stored states near the end of games, two rows of which fill the board and are
+    drawn at m * n stones -- the runs that a rule with the variant's own cell count plays otherwise
+    (tests/test_search_selfplay_async_cpu.py)"""
+    gas.test_mixed_budgets_equal_the_rule_round_by_round(hip, *case)

@@ -250,3 +250,15 @@ def test_the_policy_sums_to_one_over_the_free_cells(board, I, cons):
     assert (visits[np.arange(len(obs)), actions] == visits.max(axis=1)).all()
     g = gumbel_scores(np.full((2, 9), 1 / 9, np.float32), np.ones((2, 9), bool), 1.0, seed=1)[1]
     assert np.isfinite(g).all()
+
+
+def test_the_gpu_cases_hold_their_six_rows_on_every_board():
+    """``positions`` of tests/test_gpu_puct_gumbel.py asserts its own rows (the empty board, a full one, one free cell,
+    1 < F < considered, two rows with F > considered): on every case, the sibling boards included"""
+    import test_gpu_puct_gumbel as gpu
+
+    assert set(gpu.SIBLINGS) < set(gpu.CASES)
+    for name, ((m, n, k), _, _) in gpu.CASES.items():
+        obs = gpu.positions(name)
+        assert obs.shape == (gpu.ROWS, 2, m, n)
+        assert not has_run(obs[:, 0] != 0, k).any() and not has_run(obs[:, 1] != 0, k).any(), name

@@ -12,8 +12,10 @@ from puct_leaves_cases import CASES as LEAVES_CASES
 from puct_leaves_cases import reference as leaves_reference
 from puct_reuse_rule import ReusePuct
 from puct_rule import puct
-from puct_solver_cases import (C_PUCT, CASES, LEAVES, MISLED_BOARD, MISLED_FAR, MISLED_I, MISLED_OBS, MISLED_WIN,
-                               REUSE_CASES, misled_reference, positions, reference, reuse_reference)
+import puct_solver_rule
+from puct_solver_cases import (C_PUCT, CASES, ENV_ID0, LEAVES, MISLED_BOARD, MISLED_FAR, MISLED_I, MISLED_OBS, MISLED_WIN,
+                               REUSE_CASES, SEED, SIBLINGS, last_row_win, misled_reference, positions, reference,
+                               reuse_reference)
 from puct_solver_rule import PROOF_UNKNOWN, SolverPuct, negamax, puct_solver, value_after
 from tactical_rule import random_positions, tactical_sets
 from test_gpu_puct_reuse import advance, exact_np, start
@@ -148,6 +150,87 @@ def test_the_gpu_cases_hold_wins_losses_unless_blocked_and_last_cells():
             assert W[0].sum() == 1 and reference(name, 1)[1][4][0] == 1
     print(wins, blocks, last, proven, unknown)
     assert wins >= 10 and blocks >= 10 and last >= 3 and proven >= 50 and unknown >= 20
+
+
+# ----------------------------------------------------------------------------- the sibling boards
+VARIANT_ROWS = {3: 3, 9: 9, 13: 13, 15: 15, 19: 19}  # the board a built-in variant is named after is square: m = n
+
+
+def test_the_sibling_cases_hold_what_a_wrong_row_count_gets_wrong():
+    for name in SIBLINGS:
+        (m, n, k), rows, _ = CASES[name]
+        obs = positions(name)
+        free = (obs.reshape(rows, 2, -1) == 0).all(axis=1).sum(axis=1)
+        assert free[:5].tolist() == [1, 2, 3, 0, 3] and (free[5:] > 4).all(), (name, free)
+        _, W, _ = tactical_sets(obs, k)
+        _, cell = last_row_win(m, n, k, np.random.default_rng(0))
+        assert W[4, cell] and W[4].sum() == 1 and cell >= (m - 1) * n, name  # the one win at once, in the last row
+        mine = obs[4, 0].copy().reshape(-1)
+        mine[cell] = 1
+        assert has_run(mine.reshape(1, m, n)[:, m - 1:] != 0, k)[0], name  # the run lies in that row
+        for L in LEAVES:
+            rule = SolverPuct(k, CASES[name][2], C_PUCT, exact_np(m * n), L, seed=SEED, env_id0=ENV_ID0)
+            proof = rule.act(obs, step=2)[4]
+            assert proof[0] != PROOF_UNKNOWN, (name, L, proof)
+            # the board filled inside the search, a draw (k = 3: every free cell of a late position wins for a side)
+            assert 2 in rule.trees[1].term + rule.trees[2].term or k == 3, (name, L)
+            assert proof[4] == 1, (name, L, proof)  # the win in the last row was found
+
+
+STUCK = 4  # in the planted rule's trees: a full board that it did not call drawn
+
+
+def plant(monkeypatch, vm, vn):
+    """``puct_solver_rule`` as a kernel that took the variant's own board for the board would search: a new node is
+    terminal when its mover has a run in the first ``vm`` rows or ``vm * vn`` stones lie on the board.  A full board
+    that is then not terminal has no cell to go on to: the walk ends there every time, the node is evaluated again and
+    its proof stays unknown (marked STUCK in the tree for ``_select`` to stop at, read as unknown by ``decided``)."""
+    select, decided = puct_solver_rule._select, puct_solver_rule.decided
+
+    def planted_select(tree, root, m, n, k, c, vl, nodes0, solver):
+        before = len(tree.n)
+        got = select(tree, root, m, n, k, c, vl, nodes0, solver)
+        if got is None:
+            return got
+        path, pos, d, kind = got
+        if len(tree.n) > before:
+            won = bool(has_run(pos[(d - 1) & 1].reshape(1, m, n)[:, :vm], k)[0])
+            kind = 1 if won else (2 if (pos[0] | pos[1]).sum() >= vm * vn else 0)
+            tree.term[path[-1]] = kind
+            tree.proof[path[-1]] = kind or (STUCK if (pos[0] | pos[1]).all() else 0)
+        return path, pos, d, 0 if kind == STUCK else kind
+
+    def planted_decided(tree, x, occupied):
+        kept = tree.proof
+        tree.proof = [0 if pf == STUCK else pf for pf in kept]
+        try:
+            return decided(tree, x, occupied)
+        finally:
+            tree.proof = kept
+
+    monkeypatch.setattr(puct_solver_rule, "_select", planted_select)
+    monkeypatch.setattr(puct_solver_rule, "decided", planted_decided)
+
+
+@pytest.mark.parametrize("L", LEAVES)
+@pytest.mark.parametrize("name", SIBLINGS)
+def test_the_sibling_cases_reject_the_variants_own_board(name, L, monkeypatch):
+    """the one defect these boards are there to catch, planted in the rule: 9 cells / 3 rows for 8x3x3, 81 / 9 for 7x9x5,
+    169 / 13 for 12x13x5, 225 / 15 for 16x15x5, 361 / 19 for 18x19x5.  With fewer cells or rows than the board has, draws
+    are taken too early and the win in the last row is missed; with more, the boards that fill inside the search are not
+    drawn and their roots' proofs are lost.  Either way the proofs and the root values of the batch are other ones."""
+    (m, n, k), rows, I = CASES[name]
+    vm = VARIANT_ROWS[n]
+    assert vm != m
+    obs, want, leaves = reference(name, L)
+    plant(monkeypatch, vm, n)
+    rule = SolverPuct(k, I, C_PUCT, exact_np(m * n), L, seed=SEED, env_id0=ENV_ID0)
+    got = rule.act(obs, step=2)
+    differs = [j for j in range(5) if not np.array_equal(got[j], want[j])]
+    print(name, L, "differs in", differs, got[4][:5].tolist(), want[4][:5].tolist())
+    assert 2 in differs and 4 in differs, (name, differs)  # the root values and the proofs
+    if vm < m:
+        assert got[4][4] != 1 and 1 in differs  # the win in row m - 1 is not seen: other visits too
 
 
 @pytest.mark.parametrize("distance", [1, 2])

@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 from player_cases import check_header_and_binding, header_constants, lib  # noqa: F401 (lib: the fixture)
+import search_selfplay_async_rule
 from puct_rule import puct
 from search_selfplay_async_rule import STREAM_BUDGET, AsyncSelfPlayRule, budget_word, exact_np
 from search_selfplay_rule import Z_UNKNOWN, SelfPlayRule
@@ -94,6 +95,90 @@ def test_a_root_without_a_legal_cell_is_reported_and_left_alone():
     run_rule(rule, 12)
     assert set(rule.errors) == {(4, 1)} and rule.row_plies[1] == 0 and rule.row_plies[0] > 0
     assert np.array_equal(rule.boards[1], before[0]) and np.array_equal(rule.ring_z[:, 1], before[1][:, 1])
+
+
+def _planted_cases():
+    """one run of the GPU test per sibling board: 8x3x3 from the empty board, the others from their stored states"""
+    from test_gpu_search_selfplay_async import SIBLING_BOARDS, SIBLING_CASES
+
+    cases = [c for c in SIBLING_CASES if c[0] == (8, 3, 3) or c[7] == "golden"]
+    assert [c[0] for c in cases] == list(SIBLING_BOARDS)
+    return cases
+
+
+@pytest.mark.parametrize("case", _planted_cases(), ids=lambda c: "x".join(map(str, c[0])))
+def test_the_sibling_cases_reject_the_variants_own_board(case, monkeypatch):
+    """the GPU test's run on every sibling board (tests/test_gpu_search_selfplay_async.py) with the cell and row count of
+    the board its built-in variant is named after (9 / 3 for 8x3x3, 81 / 9 for 7x9x5, 169 / 13 for 12x13x5, 225 / 15 for
+    16x15x5, 361 / 19 for 18x19x5): a game ends at that many stones, a row is live below that many, a run is seen in that
+    many rows.  On 8x3x3 every game is cut short at 9 stones; on 16x15x5 the rows at 238 stones are not live; on the other
+    three the boards that fill are never drawn, their rows sit on a full board and are reported.  (7x9x5 from the empty
+    board fills no board: the stored start is the run that tells the rules apart there.)"""
+    from playout_rule import has_run
+    import test_gpu_search_selfplay_async as gpu_cases
+    from test_gpu_search_selfplay_async import new_rule
+
+    board, N, _, _, _, temp, rounds, start, seed = case
+    (m, n, k), vm = board, board[1]
+    assert vm != m
+
+    class Planted(AsyncSelfPlayRule):
+        def _ply(self, i, visits, full):
+            self.C = vm * n
+            try:
+                return super()._ply(i, visits, full)
+            finally:
+                self.C = m * n
+
+        def _fresh(self, i):
+            super()._fresh(i)
+            self.live[i] &= self.moves[i] < vm * n
+
+    true = new_rule(board, N, temp, seed, start)
+    run_rule(true, rounds)
+    assert true.stats[0] > 0 and not true.errors
+    assert true.stats[3] > 0 or board == (8, 3, 3)  # a board filled: a draw at m * n stones
+    monkeypatch.setattr(search_selfplay_async_rule, "has_run", lambda planes, run: has_run(planes[:, :vm], run))
+    monkeypatch.setattr(gpu_cases, "AsyncSelfPlayRule", Planted)
+    wrong = new_rule(board, N, temp, seed, start)
+    assert type(wrong) is Planted
+    run_rule(wrong, rounds)
+    print(board, true.stats.tolist(), wrong.stats.tolist(), len(wrong.errors))
+    assert wrong.stats.tolist() != true.stats.tolist() and not np.array_equal(wrong.ring_z, true.ring_z)
+    assert not np.array_equal(wrong.ring_planes, true.ring_planes) or not np.array_equal(wrong.planes(), true.planes())
+    assert wrong.row_plies.tolist() != true.row_plies.tolist() or board == (8, 3, 3)
+
+
+OLD_STARTS = {"12x12x5_meta": "1f5418751e261d337a1822836f24449adab097df432544ae05dec7e1464da01f",
+              "12x12x5_planes": "f0c533aff52d3acfa622b6d989dcb6c46e16adbecefb02476bc4e688d2785ba9",
+              "19x19x5_meta": "4402b87f47e4e9ba8fa460cea93dd1c265ea689ae68e6215beddb77cd047942c",
+              "19x19x5_planes": "303e727d92e9acf1fb44a4e691f205f8bea398f4477df248326e4cdbcb03be79"}
+
+
+def test_the_stored_starts_are_what_their_script_writes_and_the_first_two_are_unchanged():
+    """every entry of search_selfplay_async_starts.npz is what make_golden_search_selfplay_async.py computes today, and the
+    two entries the file held before the sibling boards were added are bit for bit the ones it held (SHA-256 of the array
+    bytes, taken from the file before it was written again)"""
+    import hashlib
+    import importlib.util
+    import os
+
+    from test_gpu_search_selfplay_async import GOLDEN
+
+    spec = importlib.util.spec_from_file_location("make_starts", os.path.join(os.path.dirname(GOLDEN),
+                                                                              "make_golden_search_selfplay_async.py"))
+    make = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(make)
+    with np.load(GOLDEN) as z:
+        stored = {name: z[name] for name in z.files}
+    assert set(stored) == {name + part for name in make.CASES for part in ("_planes", "_meta")}
+    for name, digest in OLD_STARTS.items():
+        assert hashlib.sha256(stored[name].tobytes()).hexdigest() == digest, name
+    assert stored["12x12x5_planes"].dtype == np.uint64 and stored["12x12x5_meta"].dtype == np.uint32
+    for name, (m, n, k, rows, plies, late) in make.CASES.items():
+        planes, meta = make.starts(m, n, k, rows, plies, late)
+        assert planes.dtype == stored[name + "_planes"].dtype and np.array_equal(planes, stored[name + "_planes"]), name
+        assert meta.dtype == stored[name + "_meta"].dtype and np.array_equal(meta, stored[name + "_meta"]), name
 
 
 def test_the_header_declares_the_entry_point_and_the_binding_has_it(lib):
