@@ -697,6 +697,44 @@ int mnk_search_selfplay_advance(void* workspace, uint64_t* planes, uint32_t* met
                                 uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs,
                                 int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh, uint64_t* plies_max, int64_t* stats,
                                 int32_t* err, void* stream);
+/* mnk_search_selfplay_advance with two of the lockstep player's options built in: Dirichlet noise on the roots and the
+ * solver.  Every argument up to err, and every rule not named here, is mnk_search_selfplay_advance's.
+ *   options off: with solver = 0 and noise_alpha = 0 the launch is mnk_search_selfplay_advance, bit for bit (root_priors,
+ *     when given, still receives the roots' plain priors as below).
+ *   noise: noise_alpha = 0 means off; otherwise alpha is finite and > 0 and noise_eps lies in [0, 1].  It applies to the
+ *     backup of a row's evaluation 0 -- the pending leaf that is the root of a fresh tree (what mnk_puct_begin and the
+ *     end of a ply leave pending).  The root is NOISED iff its ply p_i is FULL (step 2 above) or noise_fast != 0.  On a
+ *     NOISED root the priors stored on the root's free cells are mnk_puct_root_noise's P', by that rule word for word
+ *     (draws, Marsaglia and Tsang, the boost in log space, the maximum taken out before the sum, the three correctly
+ *     rounded f32 operations of the mix), with step = p_i, row id = env_id0 + i, seed [or *seed_dev], leaves = 1 and the
+ *     free cells those of the root's planes.  Nothing but the tree's own prior row is written: the evaluator's tensor is
+ *     not.  A root that is not NOISED stores the plain priors.  noise_fast = 0 is KataGo's rule: the fast searches only
+ *     move the game on and play at full strength; noise_fast = 1 noises every root.  So the noise of a ply is a function
+ *     of (seed, row id, p_i) alone, like its budget.  Precondition (the host cannot see row_plies): p_i < 2^52 / C4 - 1,
+ *     mnk_puct_root_noise's bound on step; no row reaches it.
+ *   root_priors (optional, f32 [N][C]): row i is written in exactly those launches that back up row i's evaluation 0,
+ *     NOISED or not, with the C values the root then holds; on occupied cells the evaluator's prior as given (a bf16
+ *     prior widened exactly), like `out` of mnk_puct_root_noise.
+ *   solver: with solver != 0 the backup and the selection are mnk_puct_step_solver's at leaves = 1.  In step 3 the ply of
+ *     row i ends in this launch iff it >= B or the root has a proof.  The n_a of the move and of the ring record are the
+ *     adjusted counts of mnk_puct_step_solver (if some root child is WIN, only the WIN children count; otherwise the
+ *     LOSS children are dropped; if that leaves nothing, the raw counts), clamped to [0, 65535] on free cells as before.
+ *     A FULL ply that ends by proof is a policy target like any FULL ply; a fast ply still records zero visits.  The
+ *     fresh tree of the position reached starts with no proof.  Ring slot, the Philox word of the move, outcome labels,
+ *     stats, the reset, plies_max, fresh and the rows that report MNK_ERR_VISITS are unchanged.
+ * So with full_threshold = 2^32 and rows that start together, iterations + 1 launches with noise are one ply of the
+ * lockstep player with mnk_puct_root_noise at step = the ply, bit for bit; with the solver the games are the lockstep
+ * solver's, played without the launches in which a proven root would idle.
+ * solver and noise_fast in {0, 1}; noise_alpha 0, or finite and > 0; noise_eps in [0, 1] (whether or not alpha is 0);
+ * C <= 1024; every host check, the old entry point's included, runs before anything is enqueued. */
+int mnk_search_selfplay_advance_opts(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                     int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                     int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                     uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
+                                     int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
+                                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                     uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                     float noise_eps, int noise_fast, float* root_priors, void* stream);
 /* A minibatch of ring records: sample b is the flat id idx[b] = t*N + i (negative ids wrap, an id outside [0, T*N) sets
  * MNK_ERR_ACTION_RANGE as in mnk_gather_obs and gives zero planes, policy, value and weight) under symmetry s = sym[b]
  * (sym int8 [B] or NULL = the identity).  Output cell (r, c) reads source cell (r', c'): start from (r, c); if s & 4,

@@ -315,36 +315,9 @@ __device__ __forceinline__ void puct_move(int C, const MnkPuctNode* node, const 
   if (seed_dev) seed = *seed_dev;
   const uint32_t x = deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(env_id0 + i), step, MNK_STREAM_SAMPLE);
   if constexpr (SOLVER) {
-    auto kid = [&](int a) {  // the root's child through cell a; n = 0 where there is none
-      MnkPuctNode k;
-      k.n = 0u; k.w = 0.0f; k.info = 0u;
-      const uint32_t ch = live && a < C ? child[a] : MNK_PUCT_NONE;
-      if (ch != 0u && ch != MNK_PUCT_NONE) k = node[min((int)ch, nodes - 1)];
-      return k;
-    };
-    auto count = [&](int a, int keep) {
-      const MnkPuctNode k = kid(a);
-      const uint32_t pf = MNK_PUCT_PROOF(k.info);
-      return (keep == 1 && pf != 1u) || (keep == 2 && pf == 3u) ? 0u : k.n;
-    };
-    bool win = false;
-    for (int a = lane; a < C; a += 64) win |= MNK_PUCT_PROOF(kid(a).info) == 1u;
-    int keep = __ballot(win) ? 1 : 2;
+    auto count = [&](int a, int keep) { return puct_kept_count(puct_root_kid(C, node, child, nodes, live, a), keep); };
     uint32_t maxn = 0u, tot = 0u;
-    for (int t = 0; t < 2 && !maxn; ++t) {  // the adjusted counts; were they all zero, the raw ones
-      if (t) keep = 0;
-      tot = 0u;
-      for (int a = lane; a < C; a += 64) {
-        const uint32_t na = count(a, keep);
-        maxn = max(maxn, na);
-        tot += na;
-      }
-#pragma unroll
-      for (int off = 32; off; off >>= 1) {
-        maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
-        tot += (uint32_t)__shfl_xor((int)tot, off, 64);
-      }
-    }
+    const int keep = puct_root_keep(C, node, child, nodes, live, lane, maxn, tot);
     if (visits)
       for (int a = lane; a < C; a += 64) visits[i * C + a] = (int32_t)count(a, keep);
     int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells

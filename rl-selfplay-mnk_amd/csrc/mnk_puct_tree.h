@@ -183,6 +183,49 @@ __device__ __forceinline__ void puct_env_root(MnkEnv<NW>& e, const uint32_t* roo
   e.meta = (uint32_t)stones << 1;
 }
 
+// ------------------------------------------------------------------ the solver's adjusted root counts
+// What a search that proves moves plays from and records (mnk_puct_step_solver): shared by its move, puct_move<true>,
+// and by the ply of search self-play with per-row budgets.
+// The root's child through cell a (child = the root's child row); n = 0 where there is none.
+__device__ __forceinline__ MnkPuctNode puct_root_kid(int C, const MnkPuctNode* node, const uint16_t* child, int nodes,
+                                                     bool live, int a) {
+  MnkPuctNode k;
+  k.n = 0u; k.w = 0.0f; k.info = 0u;
+  const uint32_t ch = live && a < C ? child[a] : MNK_PUCT_NONE;
+  if (ch != 0u && ch != MNK_PUCT_NONE) k = node[min((int)ch, nodes - 1)];
+  return k;
+}
+// child k's count under `keep`: 0 = every child's n, 1 = the WIN children's, 2 = all but the LOSS children's
+__device__ __forceinline__ uint32_t puct_kept_count(const MnkPuctNode& k, int keep) {
+  const uint32_t pf = MNK_PUCT_PROOF(k.info);
+  return (keep == 1 && pf != 1u) || (keep == 2 && pf == 3u) ? 0u : k.n;
+}
+// The root's `keep` (wave-uniform): 1 if some child is WIN, else 2; were those counts all zero, 0, the raw ones.  maxn and
+// tot: the maximum and the sum of the counts kept.
+__device__ __forceinline__ int puct_root_keep(int C, const MnkPuctNode* node, const uint16_t* child, int nodes, bool live,
+                                              int lane, uint32_t& maxn, uint32_t& tot) {
+  bool win = false;
+  for (int a = lane; a < C; a += 64) win |= MNK_PUCT_PROOF(puct_root_kid(C, node, child, nodes, live, a).info) == 1u;
+  int keep = __ballot(win) ? 1 : 2;
+  maxn = 0u;
+  tot = 0u;
+  for (int t = 0; t < 2 && !maxn; ++t) {  // the adjusted counts; were they all zero, the raw ones
+    if (t) keep = 0;
+    tot = 0u;
+    for (int a = lane; a < C; a += 64) {
+      const uint32_t na = puct_kept_count(puct_root_kid(C, node, child, nodes, live, a), keep);
+      maxn = max(maxn, na);
+      tot += na;
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+      maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
+      tot += (uint32_t)__shfl_xor((int)tot, off, 64);
+    }
+  }
+  return keep;
+}
+
 // ------------------------------------------------------------------ the Gumbel root (k_puct_step_gumbel only)
 // What the root of row i reads besides the tree: its row of gscore (mnk_puct_gumbel_root), the table of considered visits
 // (mnk_puct_gumbel_schedule, [considered + 1][I]) and the constants of sigma.

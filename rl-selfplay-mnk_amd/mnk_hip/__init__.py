@@ -141,6 +141,11 @@ SIGNATURES = {
     # dtype, leaf mask, fresh (u8 [N]), plies max (u64 [1]), stats, err, stream
     "mnk_search_selfplay_advance": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i, _u64, _vp, _i64,
                                     _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
+    # mnk_search_selfplay_advance's arguments up to err, then solver, noise alpha, noise eps, noise on fast plies, root
+    # priors (f32 [N][C], optional), stream
+    "mnk_search_selfplay_advance_opts": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i, _u64, _vp,
+                                         _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i,
+                                         _vp, _vp],
     # ring planes, ring visits, ring z, T, N, m, n, idx, sym, B, obs, obs dtype, legal mask, policy, value, weight, err, stream
     "mnk_search_gather": [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],

@@ -32,7 +32,9 @@ the improved policy, drawn at the ring's ply counter like the noise -- and the r
 65 535, which ``mnk_search_gather`` turns back into the target.  ``temp_plies`` is then not read.
 
 ``AsyncSearchSelfPlay`` (below) is the same loop without the lockstep: one launch per evaluator call, a search budget per
-row and ply, rows that play on as soon as their search is done.
+row and ply, rows that play on as soon as their search is done.  It takes ``root_noise`` and ``solver`` too, built into
+its one launch (``mnk_search_selfplay_advance_opts``): the noise of a row's ply is a function of (seed, row id, the row's
+ply count), and a row whose root is proven plays at once instead of idling until the slowest row is done.
 """
 from typing import Dict
 
@@ -178,11 +180,27 @@ class AsyncSearchSelfPlay:
     is not refused as empty, every id it draws wraps to the ring's last slot, and that slot holds an unknown outcome, so
     the whole batch has weight 0 -- harmless to a weighted loss, and over once the first ply is played.
 
-    No ``reuse``, ``leaves``, ``root_noise``, ``solver`` or ``gumbel`` yet."""
+    ``root_noise=(alpha, eps)`` mixes Dirichlet noise into the priors a fresh tree's root stores -- the draw and the mix
+    of ``PUCTSearchPolicy(root_noise=...)`` (the rule: include/mnk_hip.h, mnk_puct_root_noise), made inside the launch
+    that backs the root's evaluation up, keyed by (seed, row id, the row's ply count).  The evaluator's tensor is not
+    written and no torch op is added to a round.  By default only the roots of full plies are noised (the fast searches
+    only move the game on and play at full strength, as KataGo's do); ``noise_on_fast=True`` noises every root.
+    ``root_priors`` (float32 ``[N, C]``) then shows, for every row, the priors its current root holds: a row is written
+    by the launch that backs up its root's evaluation, noised or not.  With every ply full the games are those of
+    ``SearchSelfPlay(root_noise=...)`` of the same seed, bit for bit.
+
+    ``solver=True`` searches with exact proofs (``PUCTSearchPolicy(solver=True)``, the rule: include/mnk_hip.h,
+    mnk_puct_step_solver) and ends a row's ply as soon as its root is proven: the row plays from the adjusted counts --
+    which are also what a full ply records -- and starts its next search in the same launch, where the lockstep player
+    would idle until the ply of the slowest row ends.
+
+    With neither option ``advance`` calls ``mnk_search_selfplay_advance``, as before; with either it calls
+    ``mnk_search_selfplay_advance_opts``.  No ``reuse``, ``leaves`` or ``gumbel`` yet."""
 
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  fast_iterations: int = None, full_prob: float = 1.0, c: float = 1.25, temp_plies: int = None,
-                 capacity: int = None, seed=None, leaf_dtype=torch.float32, device="cuda"):
+                 capacity: int = None, seed=None, leaf_dtype=torch.float32, device="cuda", root_noise=None,
+                 noise_on_fast: bool = False, solver: bool = False):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -207,6 +225,11 @@ class AsyncSearchSelfPlay:
         if not 0.0 <= self.full_prob <= 1.0:
             raise ValueError(f"full_prob must lie in [0, 1], got {full_prob}")
         self.full_threshold = int(round(self.full_prob * 2.0 ** 32))  # a ply is full iff its u32 lies below
+        self.root_noise = PUCTSearchPolicy._checked_root_noise(root_noise)
+        self.noise_on_fast = bool(noise_on_fast)
+        if self.noise_on_fast and self.root_noise is None:
+            raise ValueError("noise_on_fast=True needs root_noise=(alpha, eps)")
+        self.solver = bool(solver)
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
@@ -217,6 +240,9 @@ class AsyncSearchSelfPlay:
         self.stats = torch.zeros((mnk_hip.STATS_REPLICAS, mnk_hip.STATS_STRIDE), dtype=torch.int64, device=dev)
         self._roots = torch.empty((self.num_envs, 2, self.m, self.n), dtype=torch.float32, device=dev)
         self.workspace, self.leaf_obs, self.leaf_mask, _ = self.policy._buffers(self.num_envs, self.m, self.n, dev)
+        # root_noise: the priors every row's current root holds (written by the launch that backs its evaluation up)
+        self.root_priors = (torch.zeros((self.num_envs, C), dtype=torch.float32, device=dev)
+                            if self.root_noise is not None else None)
         self._begin()
 
     def _begin(self) -> None:
@@ -236,13 +262,18 @@ class AsyncSearchSelfPlay:
         for _ in range(int(rounds)):
             priors, pcode, values, vcode = self.policy._evaluate(self.leaf_obs, self.leaf_mask, N, C)
             seed, seed_dev, _, _, env_id0, _ = self.sampler.block()
-            mnk_hip.call("mnk_search_selfplay_advance", mnk_hip.ptr(self.workspace), mnk_hip.ptr(env._planes),
-                         mnk_hip.ptr(env._meta), N, self.m, self.n, self.k, self.iterations, self.fast_iterations,
-                         self.full_threshold, mnk_hip.ptr(priors), pcode, mnk_hip.ptr(values), vcode, self.policy.c,
-                         self.temp_plies, seed, seed_dev, env_id0, mnk_hip.ptr(self.row_plies), buf.capacity,
-                         mnk_hip.ptr(buf.planes), mnk_hip.ptr(buf.visits), mnk_hip.ptr(buf.z), mnk_hip.ptr(self.leaf_obs),
-                         self.policy._leaf_code, mnk_hip.ptr(self.leaf_mask), mnk_hip.ptr(self.fresh),
-                         mnk_hip.ptr(buf.plies), mnk_hip.ptr(self.stats), mnk_hip.ptr(env._err), stream)
+            args = (mnk_hip.ptr(self.workspace), mnk_hip.ptr(env._planes), mnk_hip.ptr(env._meta), N, self.m, self.n,
+                    self.k, self.iterations, self.fast_iterations, self.full_threshold, mnk_hip.ptr(priors), pcode,
+                    mnk_hip.ptr(values), vcode, self.policy.c, self.temp_plies, seed, seed_dev, env_id0,
+                    mnk_hip.ptr(self.row_plies), buf.capacity, mnk_hip.ptr(buf.planes), mnk_hip.ptr(buf.visits),
+                    mnk_hip.ptr(buf.z), mnk_hip.ptr(self.leaf_obs), self.policy._leaf_code, mnk_hip.ptr(self.leaf_mask),
+                    mnk_hip.ptr(self.fresh), mnk_hip.ptr(buf.plies), mnk_hip.ptr(self.stats), mnk_hip.ptr(env._err))
+            if self.root_noise is None and not self.solver:
+                mnk_hip.call("mnk_search_selfplay_advance", *args, stream)
+            else:
+                alpha, eps = self.root_noise or (0.0, 0.0)
+                mnk_hip.call("mnk_search_selfplay_advance_opts", *args, int(self.solver), alpha, eps,
+                             int(self.noise_on_fast), mnk_hip.ptr(self.root_priors), stream)
             buf.plies_host += 1
 
     def note_replayed(self, rounds: int) -> None:
@@ -261,7 +292,8 @@ class AsyncSearchSelfPlay:
     def state_dict(self) -> Dict[str, object]:
         """env, ring, every row's ply count, the Philox key, ``temp_plies`` and the statistics.  The trees are not state:
         ``load_state_dict`` starts every row's current search afresh, and since the budget of a ply is a function of (key,
-        row id, ply count) the search that starts again gets the budget the interrupted one had"""
+        row id, ply count) the search that starts again gets the budget the interrupted one had -- and, with
+        ``root_noise``, which is a function of the same three, redraws the noise the interrupted one had"""
         return {"env": self.env.state_dict(), "buffer": self.buffer.state_dict(), "row_plies": self.row_plies.cpu(),
                 "seed": self.sampler.seed, "temp_plies": self.temp_plies, "stats": self.stats.cpu()}
 
