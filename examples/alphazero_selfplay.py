@@ -14,13 +14,16 @@ run it was.  ``--fast-iterations F --full-prob P`` (both) play through ``AsyncSe
 ``--iterations`` with probability P and is then a policy and value target, with F otherwise and is then a value target
 only, and every row plays on as soon as its own search is done (playout cap randomisation); the wrapper's root noise then
 goes to the rows the player marks ``fresh``.  They combine with ``--noise builtin`` (``AsyncSearchSelfPlay(root_noise=...)``:
-the noise is drawn inside the player's one launch, on the roots of the full plies) and with ``--solver`` (a row whose root
-is proven plays at once); not with ``--reuse``, ``--leaves`` or ``--search gumbel``.
+the noise is drawn inside the player's one launch, on the roots of the full plies), with ``--solver`` (a row whose root
+is proven plays at once) and with ``--reuse`` (``AsyncSearchSelfPlay(keep_tree=True)``: a fast ply searches on top of the
+subtree the searches before it left; the trees are dropped after each training round here too); not with ``--leaves`` or
+``--search gumbel``.
 
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse] [--solver]
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --search gumbel --iterations 16
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25 --noise builtin --solver
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25 --reuse
 """
 import argparse
 import os
@@ -131,7 +134,7 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
         raise ValueError("fast_iterations and full_prob go together")
     if fast_iterations is not None:
         return _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies,
-                            updates, batch, seed, noise, solver, reuse or leaves != 1 or search != "puct", log)
+                            updates, batch, seed, noise, solver, reuse, leaves != 1 or search != "puct", log)
     if noise == "wrapper":
         evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
@@ -165,20 +168,20 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
 
 
 def _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies, updates, batch,
-                 seed, noise, solver, unsupported, log):
+                 seed, noise, solver, reuse, unsupported, log):
     """``train`` through ``AsyncSearchSelfPlay``: a training round follows as many evaluator calls as ``plies`` plies of
     every row cost on average; the loss is ``train``'s (a fast ply's policy target is all zero: only its value counts)"""
     from selfplay.search_selfplay import AsyncSearchSelfPlay
 
     if unsupported:
-        raise ValueError("per-ply budgets do not combine with reuse, leaves or gumbel yet")
+        raise ValueError("per-ply budgets do not combine with leaves or gumbel yet")
     dev = next(net.parameters()).device
     C = m * n
     if noise == "wrapper":
         evaluator = FreshRootNoise(evaluator)
     sp = AsyncSearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, fast_iterations=fast_iterations,
                              full_prob=full_prob, temp_plies=max(1, C // 3), capacity=2 * C, seed=seed, solver=solver,
-                             root_noise=(0.3, 0.25) if noise == "builtin" else None)
+                             root_noise=(0.3, 0.25) if noise == "builtin" else None, keep_tree=reuse)
     if noise == "wrapper":
         evaluator.fresh = lambda: sp.fresh
     per_ply = full_prob * (iterations + 1) + (1 - full_prob) * (fast_iterations + 1)
@@ -198,6 +201,8 @@ def _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations
             opt.zero_grad(set_to_none=True)
             loss.backward()
             opt.step()
+        if reuse:
+            sp.reset_trees()  # the kept visits and values are the old weights': search afresh with the new ones
         stats = sp.pop_game_stats()
         log(f"round {r}: {calls} evaluator calls, plies {int(sp.row_plies.min())}..{int(sp.row_plies.max())} games "
             f"{stats['games']} black {stats['black_wins']} white {stats['white_wins']} draws {stats['draws']} mean length "

@@ -735,6 +735,58 @@ int mnk_search_selfplay_advance_opts(void* workspace, uint64_t* planes, uint32_t
                                      void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
                                      uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
                                      float noise_eps, int noise_fast, float* root_priors, void* stream);
+/* mnk_search_selfplay_advance_opts for rows that keep the played move's subtree from ply to ply (the lockstep player's
+ * mnk_puct_rebase, inside the one launch).  Every argument up to root_priors, and every rule not named here, is
+ * mnk_search_selfplay_advance_opts's; iterations stays the full budget I.
+ *   tree_iterations: the workspace's layout parameter, node capacity - 1: the number given to mnk_puct_workspace_bytes and
+ *     to mnk_puct_begin, which sets the workspace up.  iterations <= tree_iterations <= MNK_PUCT_ITERS_MAX; every id read
+ *     from the workspace is clamped by it.
+ *   keep_nodes: the most nodes a row carries over a ply, 1 <= keep_nodes <= tree_iterations + 1 - iterations, so that the
+ *     tree cannot fill within a ply.
+ *   carried (int32 [N][2], required, caller-owned): an output and the row's state -- {the nodes kept, the new root's n} of
+ *     row i's current search, {0, 0} when it began afresh.  Zero it when mnk_puct_begin sets the workspace up.
+ *   end of a ply: after the move, the ring record, the labels and the reset, exactly as before -- if the game did not end
+ *     and the root's child through the move exists and is not terminal, the row keeps that child's subtree: what
+ *     mnk_puct_rebase does for a path of one ply (the nodes stay in creation order, the first keep_nodes of them; a kept
+ *     node keeps n, w, its move, its terminal kind, its proof, its priors and its children; a dropped child becomes "none
+ *     yet"; the kept child is node 0 with info 0), the header says "pending, renew" (state 1 | 8), and carried[i] = {nodes
+ *     kept, the new root's n}.  With the solver the new root keeps one thing more: the proof it had as a child, when the
+ *     kept children still justify it -- a root proven a win for its side to move has a kept WIN child, a drawn one a kept
+ *     DRAW child, a lost one any kept child (the truncation keeps the oldest nodes, so the child that proved the root may
+ *     be gone: the root is then unknown, as in mnk_puct_rebase, and searches on).  Otherwise -- a game that
+ *     ended, a missing child -- the row's tree is set up afresh as before and carried[i] = {0, 0}.  fresh[i] = 1 either
+ *     way: it means "this row of the next batch is a root".
+ *   budget: n0 = max(carried[i][1], 1); it = n_root - n0, the iterations run in the row's ply (a saturating subtraction:
+ *     whatever carried holds, nothing leaves the row).  The ply ends iff it >= B or, with the solver, the root has a proof;
+ *     B is I or fast_iterations by the same Philox word.  On a fresh row this is n_root - 1 as before.  The backup of a
+ *     carried root's evaluation only renews its priors (mnk_puct_rebase's evaluation 0), so it = 0 in that launch; with the
+ *     solver a carried root that has a proof plays in that launch.  The budget counts the iterations of this ply, not the
+ *     root's total visits: the lockstep player's rule.
+ *   noise and root_priors act on "the pending leaf is the row's root, depth 0", carried or not: the noised priors replace
+ *     a carried root's priors on its free cells.
+ * So with full_threshold = 2^32 and rows that start together, iterations + 1 launches are one ply of mnk_puct_rebase (with
+ *   tree_iterations and keep_nodes), iterations + 1 mnk_puct_step and mnk_search_selfplay_step, bit for bit -- without
+ *   the solver: with it a ply ends as soon as its root is proven, and a carried root starts with its proof where the
+ *   lockstep solver's starts unknown, so the games are not the lockstep solver's launch for launch.
+ * LDS: a workgroup holds, besides its static stage, 4 * C doubles when noise_alpha > 0 and the carry's two id maps,
+ *   4 * 2 * (tree_iterations + 2, rounded up to even) u16, all dynamic.  The host computes the total and returns MNK_EINVAL
+ *   before anything is enqueued when it exceeds what a plain launch may ask for on the current device (the device's
+ *   limit, read once; 64 KiB where no device answers): at 64 KiB, 32 x 31 with noise and tree_iterations = 2048 is the
+ *   one kind of case (4 * 992 * 8 + 4 * 2 * 2050 * 2 + 1024 static = 65 568 B); 19 x 19 at tree_iterations = 512 asks for
+ *   8 608 B without noise and 20 160 B with it.  The limit is that of the device current at the first call, kept for the
+ *   process.  A device that reports more than 64 KiB is taken at its word; no launch above 64 KiB has been run (it would
+ *   fail through the launch status, MNK_ELAUNCH, not fault).
+ * Every host check -- those of mnk_search_selfplay_advance_opts, the two ranges, carried != NULL, the LDS total -- runs
+ * before anything is enqueued; N = 0 returns MNK_OK after them. */
+int mnk_search_selfplay_advance_keep(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                     int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                     int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                     uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
+                                     int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
+                                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                     uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                     float noise_eps, int noise_fast, float* root_priors, int tree_iterations,
+                                     int keep_nodes, int32_t* carried, void* stream);
 /* A minibatch of ring records: sample b is the flat id idx[b] = t*N + i (negative ids wrap, an id outside [0, T*N) sets
  * MNK_ERR_ACTION_RANGE as in mnk_gather_obs and gives zero planes, policy, value and weight) under symmetry s = sym[b]
  * (sym int8 [B] or NULL = the identity).  Output cell (r, c) reads source cell (r', c'): start from (r, c); if s & 4,

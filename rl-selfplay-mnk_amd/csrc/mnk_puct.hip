@@ -90,15 +90,8 @@ k_puct_begin_leaves(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I,
 
 // ------------------------------------------------------------------ evaluation 0 of a search that keeps its tree
 // One wave per row.  The row is matched against the stored root (the rule: include/mnk_hip.h, mnk_puct_rebase); a row
-// that continues it keeps the subtree of the node it reached, compacted in place to ids 0 .. kept - 1 in creation order:
-//   1. marking: a pass over the node records in chunks of 64.  A node is in the subtree when it is the new root or its
-//      parent (info >> 18, always a lower id) is: parents of earlier chunks are read from the LDS table, parents inside
-//      the chunk by pointer jumping over the lanes (at most 6 rounds).  The first `keep` marked nodes get new ids by a
-//      ballot rank; map[old] = new id or NONE, inv[new] = old id, both in LDS.
-//   2. the node records move in chunks of 64 new ids (every load of a chunk before its stores: lane j's destination j may
-//      be a lower lane's source), the prior and child rows eight nodes at a time, a cell per lane.  new <= old, and a
-//      destination slot was itself moved or dropped before, so no second workspace is needed; a cell's column of the
-//      prior and child rows is only ever touched by the one lane that owns the cell.
+// that continues it keeps the subtree of the node it reached, compacted in place to ids 0 .. kept - 1 in creation order
+// (puct_carry_subtree, mnk_puct_tree.h: the marking and the compaction, eight nodes of the prior and child rows in flight).
 template <int NW, int CN>
 __device__ __forceinline__ void puct_rebase_row(const MnkGeom& g, const void* obs, int obs_dtype, int64_t i, int I, int keep,
                                                 int leaves, unsigned char* ws, void* leaf_obs, int leaf_dtype,
@@ -111,7 +104,6 @@ __device__ __forceinline__ void puct_rebase_row(const MnkGeom& g, const void* ob
   uint32_t* hdr = (uint32_t*)row;
   const uint32_t* root = (const uint32_t*)(row + L.root);
   MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
-  float* prior = (float*)(row + L.prior);
   uint16_t* child = (uint16_t*)(row + L.child);
   // (clamped, as in k_puct_step: whatever the workspace holds, no id leaves the row)
   const int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
@@ -176,96 +168,8 @@ __device__ __forceinline__ void puct_rebase_row(const MnkGeom& g, const void* ob
     puct_row_void_slots<NW, CN>(g, row, L, pos, i, leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
     return;
   }
-  const uint32_t root_n = node[v].n;
-
-  // ---- 1. marking
-  int cnt = 0;
-  for (int base = 0; base < nodes; base += 64) {
-    const int id = base + lane;
-    const bool valid = id < nodes;
-    int p = valid && id > 0 ? min((int)MNK_PUCT_PARENT(node[id].info), id - 1) : 0;
-    bool in = id == v;
-    bool known = !valid || id <= v;  // (a lower id is never in the subtree)
-    if (!known && p < base) {
-      in = map[p] != MNK_PUCT_NONE;
-      known = true;
-    }
-    for (int r = 0; r < 6 && __ballot(!known); ++r) {
-      const int from = known ? lane : p - base;
-      const int fknown = __shfl((int)known, from, 64), fin = __shfl((int)in, from, 64), fp = __shfl(p, from, 64);
-      if (!known) {
-        if (fknown) {
-          in = fin != 0;
-          known = true;
-        } else {
-          p = fp;  // (the parent is neither the new root nor decided: the same answer as its own parent, in the chunk too)
-        }
-      }
-    }
-    in = in && known;
-    const uint64_t marked = __ballot(in);
-    const int rank = cnt + (int)__popcll(marked & ((1ull << lane) - 1ull));
-    const bool kept = in && rank < keep;  // (a dropped node's descendants have higher ranks: dropped as well)
-    if (valid) map[id] = kept ? (uint16_t)rank : (uint16_t)MNK_PUCT_NONE;
-    if (kept) inv[rank] = (uint16_t)id;
-    cnt += (int)__popcll(marked);
-    row_wave_sync();
-  }
-  const int kept = min(cnt, keep);  // >= 1: the new root
-
-  // ---- 2. compaction in place
-  for (int base = 0; base < kept; base += 64) {
-    const int j = base + lane;
-    MnkPuctNode k;
-    k.n = 0u; k.w = 0.0f; k.info = 0u;
-    if (j < kept) k = node[inv[j]];
-    row_wave_sync();
-    if (j < kept) {
-      const uint32_t up = map[min((int)MNK_PUCT_PARENT(k.info), nodes - 1)];  // (kept: the node is in the subtree)
-      k.info = j ? ((k.info & 0x3FFFFu) | ((up == MNK_PUCT_NONE ? 0u : up) << 18)) : 0u;  // (the root: as a fresh one's)
-      node[j] = k;
-    }
-  }
-  constexpr int B = 8;
-  for (int j0 = 0; j0 < kept; j0 += B) {
-    for (int a = lane; a < C; a += 64) {
-      float pr[B];
-      uint32_t cl[B];
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        const int64_t o = (int64_t)inv[min(j0 + b, kept - 1)] * C + a;
-        pr[b] = prior[o];
-        cl[b] = child[o];
-      }
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        if (j0 + b < kept) {
-          uint32_t ch = cl[b];
-          if (ch != 0u && ch != MNK_PUCT_NONE) {
-            ch = map[min((int)ch, nodes - 1)];
-            if (ch == MNK_PUCT_NONE) ch = 0u;  // a dropped child: none yet
-          }
-          const int64_t o = (int64_t)(j0 + b) * C + a;
-          prior[o] = pr[b];
-          child[o] = (uint16_t)ch;
-        }
-      }
-    }
-  }
-
-  // ---- the new root as evaluation 0
-  puct_row_root<NW>(row, L, pos, NWg, lane);
-  if (lane == 0) {
-    hdr[0] = (uint32_t)kept;
-    hdr[1] = 0u;
-    hdr[2] = 1u | 8u;  // pending, and only the priors of it are used
-    hdr[3] = 1u;       // (a node that is not terminal has a legal cell)
-    ((uint16_t*)(row + L.path))[0] = 0;
-    if (carried) {
-      carried[2 * i] = kept;
-      carried[2 * i + 1] = (int32_t)root_n;
-    }
-  }
+  // ---- the subtree of node v, carried over (mnk_puct_tree.h)
+  puct_carry_subtree<NW>(C, NWg, row, L, pos, nodes, v, keep, i, carried, map, inv, lane);
   row_write_view<NW, CN>(g, pos, 0, i * leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
   puct_row_void_slots<NW, CN>(g, row, L, pos, i, leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
 }

@@ -34,7 +34,9 @@ the improved policy, drawn at the ring's ply counter like the noise -- and the r
 ``AsyncSearchSelfPlay`` (below) is the same loop without the lockstep: one launch per evaluator call, a search budget per
 row and ply, rows that play on as soon as their search is done.  It takes ``root_noise`` and ``solver`` too, built into
 its one launch (``mnk_search_selfplay_advance_opts``): the noise of a row's ply is a function of (seed, row id, the row's
-ply count), and a row whose root is proven plays at once instead of idling until the slowest row is done.
+ply count), and a row whose root is proven plays at once instead of idling until the slowest row is done.  ``keep_tree=True`` is its
+``reuse`` (``mnk_search_selfplay_advance_keep``): the launch that plays a row's ply carries the played move's subtree into
+the row's next search.
 """
 from typing import Dict
 
@@ -194,13 +196,25 @@ class AsyncSearchSelfPlay:
     which are also what a full ply records -- and starts its next search in the same launch, where the lockstep player
     would idle until the ply of the slowest row ends.
 
-    With neither option ``advance`` calls ``mnk_search_selfplay_advance``, as before; with either it calls
-    ``mnk_search_selfplay_advance_opts``.  No ``reuse``, ``leaves`` or ``gumbel`` yet."""
+    ``keep_tree=True`` is ``SearchSelfPlay``'s ``reuse``: a row keeps the subtree of the move it played (the rule:
+    include/mnk_hip.h, mnk_search_selfplay_advance_keep), carried over inside the launch that plays the ply, so a fast ply
+    searches ``fast_iterations`` on top of what the searches before it left there.  The budget of a ply counts the
+    iterations of that ply, not the root's total visits, and with every ply full the games are those of
+    ``SearchSelfPlay(reuse=True, tree_nodes=...)`` of the same seed, bit for bit.  ``tree_nodes`` is the workspace's node
+    capacity per row (default ``2 * iterations + 1``, ``PUCTSearchPolicy``'s range); a ply carries at most ``tree_nodes -
+    iterations`` nodes over, the oldest first.  ``carried`` (int32 ``[N, 2]``) holds {nodes kept, the kept root's visit
+    count} of every row's current search, {0, 0} for one that began afresh.  ``reset_trees()`` drops the kept trees --
+    for after the evaluator's weights changed.  With the solver a carried root keeps the proof it had as a child and
+    plays in the launch that renews it.
+
+    With neither option ``advance`` calls ``mnk_search_selfplay_advance``, as before; with ``root_noise`` or ``solver`` it
+    calls ``mnk_search_selfplay_advance_opts``; with ``keep_tree`` it calls ``mnk_search_selfplay_advance_keep``, which
+    takes the other two.  No ``leaves`` or ``gumbel`` yet."""
 
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  fast_iterations: int = None, full_prob: float = 1.0, c: float = 1.25, temp_plies: int = None,
                  capacity: int = None, seed=None, leaf_dtype=torch.float32, device="cuda", root_noise=None,
-                 noise_on_fast: bool = False, solver: bool = False):
+                 noise_on_fast: bool = False, solver: bool = False, keep_tree: bool = False, tree_nodes: int = None):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -213,11 +227,14 @@ class AsyncSearchSelfPlay:
         capacity = 2 * C if capacity is None else int(capacity)
         if capacity < C:
             raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
-        # (the policy checks model / evaluator, iterations, c and leaf_dtype; it lends its evaluator call, its key and its
-        # workspace and is never asked to act)
+        self.keep_tree = bool(keep_tree)
+        # (the policy checks model / evaluator, iterations, c, leaf_dtype and tree_nodes -- its range, and that it comes
+        # with keep_tree; it lends its evaluator call, its key and its workspace and is never asked to act)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
-                                       temperature=0, leaf_dtype=leaf_dtype, seed=seed)
+                                       temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=self.keep_tree,
+                                       tree_nodes=tree_nodes)
         self.iterations = self.policy.iterations
+        self.tree_nodes = self.policy.tree_nodes  # (iterations + 1 without keep_tree)
         self.fast_iterations = self.iterations if fast_iterations is None else int(fast_iterations)
         if not 1 <= self.fast_iterations <= self.iterations:
             raise ValueError(f"fast_iterations must lie in [1, iterations] = [1, {self.iterations}], got {fast_iterations}")
@@ -243,6 +260,8 @@ class AsyncSearchSelfPlay:
         # root_noise: the priors every row's current root holds (written by the launch that backs its evaluation up)
         self.root_priors = (torch.zeros((self.num_envs, C), dtype=torch.float32, device=dev)
                             if self.root_noise is not None else None)
+        # keep_tree: {nodes kept, the kept root's visit count} of every row's current search ({0, 0}: it began afresh)
+        self.carried = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=dev) if self.keep_tree else None
         self._begin()
 
     def _begin(self) -> None:
@@ -250,9 +269,16 @@ class AsyncSearchSelfPlay:
         env = self.env
         env.observe_into(obs=self._roots, flip_side=(env._meta & 1).to(torch.int64))
         mnk_hip.call("mnk_puct_begin", mnk_hip.ptr(self._roots), mnk_hip.OBS_F32, self.num_envs, self.m, self.n, self.k,
-                     self.iterations, mnk_hip.ptr(self.workspace), mnk_hip.ptr(self.leaf_obs), self.policy._leaf_code,
+                     self.tree_nodes - 1, mnk_hip.ptr(self.workspace), mnk_hip.ptr(self.leaf_obs), self.policy._leaf_code,
                      mnk_hip.ptr(self.leaf_mask), mnk_hip.stream_ptr(env._dev))
         self.fresh.fill_(1)
+        if self.carried is not None:
+            self.carried.zero_()
+
+    def reset_trees(self) -> None:
+        """``keep_tree=True``: forget the kept trees, so that every row's current search starts afresh on its position --
+        for after the evaluator's weights changed"""
+        self._begin()
 
     def advance(self, rounds: int = 1) -> None:
         """``rounds`` times: the evaluator on ``leaf_obs`` / ``leaf_mask``, then the kernel.  Enqueues work only;
@@ -268,7 +294,12 @@ class AsyncSearchSelfPlay:
                     mnk_hip.ptr(self.row_plies), buf.capacity, mnk_hip.ptr(buf.planes), mnk_hip.ptr(buf.visits),
                     mnk_hip.ptr(buf.z), mnk_hip.ptr(self.leaf_obs), self.policy._leaf_code, mnk_hip.ptr(self.leaf_mask),
                     mnk_hip.ptr(self.fresh), mnk_hip.ptr(buf.plies), mnk_hip.ptr(self.stats), mnk_hip.ptr(env._err))
-            if self.root_noise is None and not self.solver:
+            if self.keep_tree:
+                alpha, eps = self.root_noise or (0.0, 0.0)
+                mnk_hip.call("mnk_search_selfplay_advance_keep", *args, int(self.solver), alpha, eps,
+                             int(self.noise_on_fast), mnk_hip.ptr(self.root_priors), self.tree_nodes - 1,
+                             self.tree_nodes - self.iterations, mnk_hip.ptr(self.carried), stream)
+            elif self.root_noise is None and not self.solver:
                 mnk_hip.call("mnk_search_selfplay_advance", *args, stream)
             else:
                 alpha, eps = self.root_noise or (0.0, 0.0)
@@ -293,7 +324,9 @@ class AsyncSearchSelfPlay:
         """env, ring, every row's ply count, the Philox key, ``temp_plies`` and the statistics.  The trees are not state:
         ``load_state_dict`` starts every row's current search afresh, and since the budget of a ply is a function of (key,
         row id, ply count) the search that starts again gets the budget the interrupted one had -- and, with
-        ``root_noise``, which is a function of the same three, redraws the noise the interrupted one had"""
+        ``root_noise``, which is a function of the same three, redraws the noise the interrupted one had.  With
+        ``keep_tree`` that search starts without the subtree the interrupted one was carried with (``carried`` is zero
+        after ``load_state_dict``)"""
         return {"env": self.env.state_dict(), "buffer": self.buffer.state_dict(), "row_plies": self.row_plies.cpu(),
                 "seed": self.sampler.seed, "temp_plies": self.temp_plies, "stats": self.stats.cpu()}
 
