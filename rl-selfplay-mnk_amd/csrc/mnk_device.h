@@ -297,19 +297,79 @@ __device__ __forceinline__ int bs_select(const uint32_t (&x)[NW], int r) {
 // ---------------------------------------------------------------- Philox4x32-10
 struct Philox4 { uint32_t v[4]; };
 
-// 32 x 32 -> 64 in one instruction (the compiler spells it v_mul_lo_u32 + v_mul_hi_u32: two issue slots)
+// 32 x 32 -> 64 in one instruction (the compiler spells it v_mul_lo_u32 + v_mul_hi_u32: two issue slots).
+// Two spellings that differ only in where the (unused) carry-out goes: an SGPR pair of the compiler's choice, or vcc.
+// After an inline-assembly statement the compiler wants one wait state before a VALU instruction that names any
+// register the statement defines (it cannot see inside the statement, so it assumes a forwarding hazard), and fills
+// it with an s_nop when nothing else is there.  A Philox round multiplies twice: with the two carry-outs apart the
+// multiplies share no register and may stand back to back (philox4x32_10_from; and an assembly statement in between
+// does not count as a wait state, so that form also keeps an xor away from the multiply it reads).
 __device__ __forceinline__ uint64_t mnk_mul_wide(uint32_t a, uint32_t m) {
   uint64_t product, carry;
   asm("v_mad_u64_u32 %0, %1, %2, %3, 0" : "=v"(product), "=s"(carry) : "v"(a), "s"(m));
   return product;
 }
+__device__ __forceinline__ uint64_t mnk_mul_wide_vcc(uint32_t a, uint32_t m) {
+  uint64_t product;
+  asm("v_mad_u64_u32 %0, vcc, %1, %2, 0" : "=v"(product) : "v"(a), "s"(m) : "vcc");
+  return product;
+}
 
+#define MNK_PHILOX_M0 0xD2511F53u
+#define MNK_PHILOX_M1 0xCD9E8D57u
+
+// round 1's first product, c0 * M0.  The rollout's c0 is the low word of the lane's env id -- the same in every block
+// of a launch -- so its loops compute this once and hand it to philox4x32_10_from.
+__device__ __forceinline__ uint64_t philox_first_product(uint32_t c0) { return mnk_mul_wide_vcc(c0, MNK_PHILOX_M0); }
+
+// the ten rounds, given round 1's first product p0_first = philox_first_product(c0).
+// Round r multiplies twice, A[r] = c0 * M0 and B[r] = c2 * M1, and xors twice, n0[r] off B[r]'s high half and n2[r]
+// off A[r]'s; A[r + 1] takes n0[r], B[r + 1] takes n2[r].  So the block is two chains that only exchange low halves
+// a round late, and the statements below walk them half a round apart -- multiply of one chain, xor of the other --
+// so that an xor never directly follows the multiply whose product it reads (see mnk_mul_wide).
+// The words are those of philox4x32_10, bit for bit: tests/test_gpu_rollout_lean2.py holds the loops that use this
+// form to the oracle's Philox (oracle/philox.py), the env id's low word wrapping inside a wave included.
+__device__ __forceinline__ Philox4 philox4x32_10_from(uint64_t p0_first, uint32_t c1, uint32_t c2, uint32_t c3,
+                                                      uint32_t k0, uint32_t k1) {
+  uint64_t A[11], B[11];
+  uint32_t n0[11], n2[11];
+  // the xors of round r (keys of round r; c1 / c3 of round r are the low halves of round r - 1's products)
+#define MNK_PHILOX_N0(r) \
+  n0[r] = __builtin_amdgcn_bitop3_b32((uint32_t)(B[r] >> 32), (r) == 1 ? c1 : (uint32_t)B[(r) - 1], k0 + ((r) - 1) * 0x9E3779B9u, 0x96)
+#define MNK_PHILOX_N2(r) \
+  n2[r] = __builtin_amdgcn_bitop3_b32((uint32_t)(A[r] >> 32), (r) == 1 ? c3 : (uint32_t)A[(r) - 1], k1 + ((r) - 1) * 0xBB67AE85u, 0x96)
+  A[1] = p0_first;
+  B[1] = mnk_mul_wide(c2, MNK_PHILOX_M1);
+  MNK_PHILOX_N2(1);
+#pragma unroll
+  for (int r = 2; r <= 10; r += 2) {
+    B[r] = mnk_mul_wide(n2[r - 1], MNK_PHILOX_M1);
+    MNK_PHILOX_N0(r - 1);
+    A[r] = mnk_mul_wide_vcc(n0[r - 1], MNK_PHILOX_M0);
+    MNK_PHILOX_N0(r);
+    if (r < 10) {
+      A[r + 1] = mnk_mul_wide_vcc(n0[r], MNK_PHILOX_M0);
+      MNK_PHILOX_N2(r);
+      B[r + 1] = mnk_mul_wide(n2[r], MNK_PHILOX_M1);
+      MNK_PHILOX_N2(r + 1);
+    }
+  }
+  MNK_PHILOX_N2(10);
+#undef MNK_PHILOX_N0
+#undef MNK_PHILOX_N2
+  Philox4 o;
+  o.v[0] = n0[10]; o.v[1] = (uint32_t)B[10]; o.v[2] = n2[10]; o.v[3] = (uint32_t)A[10];
+  return o;
+}
+
+// the block as every other kernel computes it: round after round, both multiplies with their carry-out in an SGPR
+// pair.  Left as it was: where this form sits among a ply's record stores (19x19, two lanes per env) the skewed one
+// measured 1 % slower, and elsewhere the waves of other envs cover the wait states.
 __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3,
                                                  uint32_t k0, uint32_t k1) {
-  const uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u;
 #pragma unroll
   for (int r = 0; r < 10; ++r) {
-    const uint64_t p0 = mnk_mul_wide(c0, M0), p1 = mnk_mul_wide(c2, M1);
+    const uint64_t p0 = mnk_mul_wide(c0, MNK_PHILOX_M0), p1 = mnk_mul_wide(c2, MNK_PHILOX_M1);
     // three-input xor in one slot (v_bitop3_b32, truth table 0x96); left alone the compiler emits two v_xor_b32
     const uint32_t n0 = __builtin_amdgcn_bitop3_b32((uint32_t)(p1 >> 32), c1, k0, 0x96);
     const uint32_t n2 = __builtin_amdgcn_bitop3_b32((uint32_t)(p0 >> 32), c3, k1, 0x96);
@@ -326,6 +386,14 @@ __device__ __forceinline__ Philox4 mnk_rng_block(uint64_t seed, uint64_t env, ui
   return philox4x32_10((uint32_t)env, (uint32_t)(env >> 32), (uint32_t)q,
                        stream | ((uint32_t)((q >> 32) & 0xFFFFFFu) << 8),
                        (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// the same block with env_p0 = philox_first_product((uint32_t)env) computed by the caller, once for many blocks
+__device__ __forceinline__ Philox4 mnk_rng_block_from(uint64_t seed, uint64_t env_p0, uint64_t env, uint64_t q,
+                                                      uint32_t stream) {
+  return philox4x32_10_from(env_p0, (uint32_t)(env >> 32), (uint32_t)q,
+                            stream | ((uint32_t)((q >> 32) & 0xFFFFFFu) << 8),
+                            (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
 __device__ __forceinline__ uint32_t philox_word(const Philox4& b, uint32_t i) {

@@ -329,8 +329,10 @@ struct RolloutLane {
       win = mnk_plane_wins<NW, CN, CK>(g, cur) ? 1u : 0u;
     }
     const uint32_t done = win | ((FAST ? nlegal == 1u : moves >= (uint32_t)g.C) ? 1u : 0u);   // :72-73
+    // FAST: the side to move is not carried either -- in a consistent game it is the parity of the stone count
+    const uint32_t mover = FAST ? (((uint32_t)g.C ^ nlegal) & 1u) : side;
     if (RECORD) {
-      const uint32_t mword = (uint32_t)a | (win << MNK_REC_REWARD_SHIFT) | (done << MNK_REC_DONE_BIT) | (side << MNK_REC_SIDE_BIT);
+      const uint32_t mword = (uint32_t)a | (win << MNK_REC_REWARD_SHIFT) | (done << MNK_REC_DONE_BIT) | (mover << MNK_REC_SIDE_BIT);
       if constexpr (OFF32) {
         __builtin_nontemporal_store(mword, (uint32_t*)(mbase + (uint64_t)moff));
         moff += (uint32_t)N * 4u;
@@ -340,7 +342,12 @@ struct RolloutLane {
       }
     }
     acc_dw += done | (win << 16);
-    acc_white += win & side;
+    // FAST: white's wins count in the high half, off the win bit the meta word already holds at bit 16 (one 24-bit
+    // multiply-add: the bit times the mover); finish_fast() moves the count down
+    // (as assembly: from C++ the compiler makes a multiply and, per two plies, a three-input add of it)
+    static_assert(MNK_REC_REWARD_SHIFT == 16, "the FAST white-win count multiplies the meta word's win bit, taken to be bit 16");
+    if (FAST) asm("v_mad_u32_u24 %0, %1, %2, %0" : "+v"(acc_white) : "v"(win << 16), "v"(mover));
+    else acc_white += win & side;
     // the other side is to move (:82) -- or a fresh game
 #pragma unroll
     for (int w = 0; w < NW; ++w) {
@@ -348,50 +355,81 @@ struct RolloutLane {
       cur[w] = done ? 0u : oth[w];
       oth[w] = done ? 0u : c;
     }
-    side = done ? 0u : (side ^ 1u);
-    if (!FAST) moves = done ? 0u : moves;
+    if (!FAST) {
+      side = done ? 0u : (side ^ 1u);
+      moves = done ? 0u : moves;
+    }
   }
 
   __device__ __forceinline__ uint32_t acc_done() const { return acc_dw & 0xFFFFu; }
   __device__ __forceinline__ uint32_t acc_win() const { return acc_dw >> 16; }
 
-  // is this lane's game consistent (stones on the board == plies counted < C)?  -> the wave may take the FAST loop
+  // is this lane's game consistent (stones on the board == plies counted < C, black to move on even counts)?  -> the
+  // wave may take the FAST loop
   __device__ __forceinline__ bool consistent() const {
     uint32_t occ[NW];
 #pragma unroll
     for (int w = 0; w < NW; ++w) occ[w] = cur[w] | oth[w];
-    return (uint32_t)bs_popcount<NW>(occ) == moves && moves < (uint32_t)g.C;
+    return (uint32_t)bs_popcount<NW>(occ) == moves && moves < (uint32_t)g.C && side == (moves & 1u);
   }
 
-  // after a FAST loop: the ply counter of a consistent game is its stone count
+  // after a FAST loop: the ply counter of a consistent game is its stone count, the side to move its parity; white's
+  // wins were counted in the high half
   __device__ __forceinline__ void finish_fast() {
     uint32_t occ[NW];
 #pragma unroll
     for (int w = 0; w < NW; ++w) occ[w] = cur[w] | oth[w];
     moves = (uint32_t)bs_popcount<NW>(occ);
+    side = moves & 1u;
+    acc_white >>= 16;
   }
 };
 
 // the T plies of one lane: head (finish the Philox block the previous launch stopped in), groups of four plies on
 // one Philox block each with the word picked at compile time, tail
-template <bool FAST, typename Lane>
+template <bool FAST, bool LEAN = FAST, typename Lane>
 __device__ __forceinline__ void rollout_plies(Lane& L, int T, uint64_t seed, uint64_t step0, uint64_t env) {
   int t = 0;
   uint64_t step = step0;
+  // LEAN (both loops of the kernels that have a FAST loop: the instruction-bound boards): round 1's lane-invariant
+  // product once per launch, the rounds without wait states.  The kernels of the larger boards keep the block as it
+  // was: their time hangs on the compiler's schedule around the record stores, which this would change.
+  uint64_t env_p0 = 0;
+  if constexpr (LEAN) env_p0 = philox_first_product((uint32_t)env);
+  auto block = [&](uint64_t q) {
+    if constexpr (LEAN) return mnk_rng_block_from(seed, env_p0, env, q, MNK_STREAM_MOVE);
+    else return mnk_rng_block(seed, env, q, MNK_STREAM_MOVE);
+  };
   if (step & 3) {
-    const Philox4 blk = mnk_rng_block(seed, env, step >> 2, MNK_STREAM_MOVE);
+    const Philox4 blk = block(step >> 2);
     for (; t < T && (step & 3); ++t, ++step)
       L.template ply<FAST>(philox_word(blk, (uint32_t)(step & 3)), (int)(step & 3));
   }
-  for (; t + 4 <= T; t += 4, step += 4) {
-    const Philox4 blk = mnk_rng_block(seed, env, step >> 2, MNK_STREAM_MOVE);
-    L.template ply<FAST>(blk.v[0], 0);
-    L.template ply<FAST>(blk.v[1], 1);
-    L.template ply<FAST>(blk.v[2], 2);
-    L.template ply<FAST>(blk.v[3], 3);
+  if constexpr (FAST) {
+    // the instruction-bound loops count blocks, not plies and steps: one counter down to zero and the block number
+    // up by one, where `t` against T and `step` cost the trip a second counter and two 64-bit shifts
+    const int blocks = (T - t) >> 2;
+    uint64_t q = step >> 2;
+    for (int left = blocks; left > 0; --left, ++q) {
+      const Philox4 blk = block(q);
+      L.template ply<FAST>(blk.v[0], 0);
+      L.template ply<FAST>(blk.v[1], 1);
+      L.template ply<FAST>(blk.v[2], 2);
+      L.template ply<FAST>(blk.v[3], 3);
+    }
+    t += blocks << 2;
+    step += (uint64_t)blocks << 2;
+  } else {
+    for (; t + 4 <= T; t += 4, step += 4) {
+      const Philox4 blk = block(step >> 2);
+      L.template ply<FAST>(blk.v[0], 0);
+      L.template ply<FAST>(blk.v[1], 1);
+      L.template ply<FAST>(blk.v[2], 2);
+      L.template ply<FAST>(blk.v[3], 3);
+    }
   }
   if (t < T) {
-    const Philox4 blk = mnk_rng_block(seed, env, step >> 2, MNK_STREAM_MOVE);
+    const Philox4 blk = block(step >> 2);
     for (uint32_t j = 0; t < T; ++t, ++j) L.template ply<FAST>(philox_word(blk, j), (int)j);
   }
 }
@@ -424,7 +462,7 @@ __device__ __forceinline__ void rollout_random_body(const MnkGeom& g, uint64_t* 
       rollout_plies<true>(L, T, seed, step0, env);
       L.finish_fast();
     } else {
-      rollout_plies<false>(L, T, seed, step0, env);
+      rollout_plies<false, TRY_FAST>(L, T, seed, step0, env);
     }
     L.log_finish(T);  // T not a multiple of 4: the last word is partly filled
     L.store(planes, meta, i);
@@ -447,16 +485,19 @@ __device__ __forceinline__ void rollout_random_body(const MnkGeom& g, uint64_t* 
 
 // ------------------------------------------------------------------ two lanes per env (scan directions split)
 // the T plies of one lane pair (FAST: see mnk_rollout_lane.h -- every game of the wave consistent)
-template <bool FAST, typename Lane>
+template <bool FAST, bool LEAN = FAST, typename Lane>
 __device__ __forceinline__ void pair_plies(Lane& L, int T, uint64_t seed, uint64_t step0, uint64_t env, uint32_t role) {
   int t = 0;
   uint64_t step = step0;
+  uint64_t env_p0 = 0;
+  if constexpr (LEAN) env_p0 = philox_first_product((uint32_t)env);  // see rollout_plies: once per launch
   // unshared Philox until the step counter sits on a multiple of 8 (two blocks)
   for (; t < T && (step & 7); ++t, ++step)
     L.template ply<FAST>(mnk_rand_u32(seed, env, step, MNK_STREAM_MOVE), (int)(step & 3));
   for (; t + 8 <= T; t += 8, step += 8) {
     // lane `role` computes block (step/4 + role); the partner's four words arrive by DPP
-    const Philox4 mine = mnk_rng_block(seed, env, (step >> 2) + role, MNK_STREAM_MOVE);
+    const Philox4 mine = LEAN ? mnk_rng_block_from(seed, env_p0, env, (step >> 2) + role, MNK_STREAM_MOVE)
+                              : mnk_rng_block(seed, env, (step >> 2) + role, MNK_STREAM_MOVE);
     uint32_t lo[4], hi[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -492,7 +533,7 @@ __device__ __forceinline__ void rollout_random_pair_body(const MnkGeom& g, uint6
       pair_plies<true>(L, T, seed, step0, env, role);
       L.finish_fast();
     } else {
-      pair_plies<false>(L, T, seed, step0, env, role);
+      pair_plies<false, TRY_FAST>(L, T, seed, step0, env, role);
     }
     if (ACT && (T & 3)) L.log_flush();
     L.store(planes, meta, i);  // lane `role` stores plane `role`; the meta word is written by both

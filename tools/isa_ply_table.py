@@ -3,7 +3,8 @@
 usage: python tools/isa_ply_table.py [asm file]      (default: compiles csrc/mnk_rollout.hip with -S into /tmp)
 Finds k_rollout_random<3, 9, 5, true, 0, true> (the headline kernel: 9x9x5, records, 32-bit-offset stores), takes its
 innermost loops that hold four plies (16 global stores), and counts the instructions of one trip by class / 4.
-The kernel has two such loops since round 3: the FAST one (waves of consistent games) comes first in the text."""
+The kernel has two such loops since round 3: the FAST one (waves of consistent games) has no branch but its own, the
+general one keeps the "no legal cell" branch in every ply."""
 import collections
 import os
 import re
@@ -48,7 +49,10 @@ def main():
     # basic blocks that belong to one "Inner Loop Header": from the header label to the backward branch to it
     loops = []
     for i, line in enumerate(lines):
-        m = re.match(r"^(\.LBB\d+_\d+):.*Inner Loop Header", line)
+        if "Inner Loop Header" not in line:
+            continue
+        # (the label stands on the header line, or on the line before it when the loop is nested in another)
+        m = re.match(r"^(\.LBB\d+_\d+):", line) or re.match(r"^(\.LBB\d+_\d+):", lines[i - 1])
         if not m:
             continue
         label = m.group(1)
@@ -58,6 +62,7 @@ def main():
                 loops.append((label, body))
                 break
     four = [(lab, b) for lab, b in loops if sum(x.startswith("global_store") for x in b) == 16]
+    four.sort(key=lambda lb: sum(bool(re.match(r"s_(cbranch|branch)", x)) for x in lb[1]))  # the FAST loop first
     print("# Per-ply instruction table of the headline rollout kernel, from the ISA\n")
     print("`python tools/isa_ply_table.py`: hipcc -O3 -S of `csrc/mnk_rollout.hip`, kernel `k_rollout_random<3, 9, 5, true, 0, true>` "
           "(9x9x5, records on, 32-bit-offset record stores); the loops that hold four plies per trip (16 global stores), "
@@ -83,8 +88,8 @@ def main():
     valu = [sum(v[i] for c, v in table.items() if c.split()[0] not in ("global", "scalar", "branches", "s_nop")) for i in range(len(four))]
     print("| **VALU total** | " + " | ".join(f"**{v:.2f}**" for v in valu) + " |")
     print("| **all instructions** | " + " | ".join(f"**{v:.2f}**" for v in totals) + " |")
-    print("\nPer four plies the trip also holds one Philox4x32-10 block: 20 `v_mad_u64_u32` (inline assembly) + 20 `v_bitop3_b32` "
-          "(three-input xor), counted above under integer arithmetic / bit logic; the r-th-set-bit select is 23 instructions "
+    print("\nPer four plies the trip also holds one Philox4x32-10 block, `v_mad_u64_u32` (inline assembly) and `v_bitop3_b32` "
+          "(three-input xor; what of round 1 does not change from block to block is made outside the loop), counted above under integer arithmetic / bit logic; the r-th-set-bit select is 23 instructions "
           "of inline assembly per ply (5 per halving level).")
 
 
