@@ -971,6 +971,11 @@ int mnk_probe_record_writes(uint64_t* rec, int64_t N, int T, int rows, void* str
 int mnk_probe_select_bits(const uint32_t* words, int nw, int64_t count, const int32_t* ranks, int32_t* bits, uint32_t* hot,
                           void* stream);
 
+/* Test aid: the byte table that ends that select in the rollout kernels which have a FAST loop (MnkSelectTable in
+ * csrc/mnk_device.h), as its generator makes it, to out u8[256][8] in HOST memory: out[b][r] = position of the r-th
+ * set bit of byte b, 0 where r >= popcount(b).  Needs no device. */
+int mnk_probe_select_table(uint8_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -246,6 +246,60 @@ __device__ __forceinline__ uint32_t select_bit32_nr(uint32_t x, uint32_t nr, uin
       : [x] "v"(x), [base] "v"(base));
   return pos;
 }
+// The tail of the same search as one LDS byte read: the last three levels (8 -> 4 -> 2 -> 1, 13 slots) only answer
+// "where is the r-th set bit of this byte, r < 8", a function of 11 bits.  MnkSelectTable is that function as a table,
+// t[b][r] = position of the r-th (0-based) set bit of byte b, 0 where r >= popcount(b); mnk_select_table_fill copies it
+// into 2 KB of a one-wave workgroup's LDS, and select_bit32_nr_tab runs the 16- and 8-level steps as above, then reads
+// t[byte at pos][~nr].  The read is plain C++, not part of the assembly: the compiler counts it in its own s_waitcnt,
+// which it puts before the first use -- behind the caller's cover(), see below.
+struct MnkSelectTable {
+  uint8_t t[256][8];
+  constexpr MnkSelectTable() : t() {
+    for (int b = 0; b < 256; ++b) {
+      int r = 0;
+      for (int p = 0; p < 8; ++p)
+        if ((b >> p) & 1) t[b][r++] = (uint8_t)p;
+    }
+  }
+};
+#define MNK_SELECT_TABLE_BYTES 2048
+static __device__ const MnkSelectTable mnk_select_table_rom = MnkSelectTable();
+
+// all 64 threads of a one-wave workgroup: 32 bytes each, global -> LDS; the caller's __syncthreads() publishes it
+__device__ __forceinline__ void mnk_select_table_fill(uint32_t* lds_table) {
+  const uint4* src = (const uint4*)&mnk_select_table_rom.t[0][0];
+  uint4* dst = (uint4*)lds_table;
+  dst[threadIdx.x] = src[threadIdx.x];
+  dst[threadIdx.x + 64u] = src[threadIdx.x + 64u];
+}
+
+// `cover()` stands between the read and the first use of what it returns: work of the caller's that does not hang on the
+// pick, pinned there (the scheduler left to itself puts a few instructions behind the read and waits; a lone wave then
+// sits out most of the read's ~50 cycles)
+struct MnkNoCover {
+  __device__ __forceinline__ void operator()() const {}
+};
+template <typename Cover>
+__device__ __forceinline__ uint32_t select_bit32_nr_tab(uint32_t x, uint32_t nr, uint32_t base, const uint8_t* tab,
+                                                        Cover&& cover) {
+  uint32_t pos, t;
+  asm("v_and_b32 %[t], 0xffff, %[x]\n\t"
+      "v_bcnt_u32_b32 %[t], %[t], %[nr]\n\t"
+      "v_max_u32 %[nr], %[nr], %[t]\n\t"
+      "v_ashrrev_i32 %[t], 31, %[t]\n\t"
+      "v_and_or_b32 %[pos], %[t], 16, %[base]\n\t"
+      MNK_SELECT_LEVEL(8)
+      "v_bfe_u32 %[t], %[x], %[pos], 8\n\t"     // the byte the bit lies in ...
+      "v_not_b32 %[nr], %[nr]\n\t"               // ... its rank there, 0 .. 7 ...
+      "v_lshl_add_u32 %[t], %[t], 3, %[nr]"      // ... and the table's index
+      : [pos] "=&v"(pos), [t] "=&v"(t), [nr] "+v"(nr)
+      : [x] "v"(x), [base] "v"(base));
+  const uint32_t in_byte = tab[t];
+  __builtin_amdgcn_sched_barrier(0);
+  cover();
+  __builtin_amdgcn_sched_barrier(0);
+  return pos | in_byte;
+}
 #undef MNK_SELECT_LEVEL
 
 __device__ __forceinline__ int select_bit32(uint32_t x, int r) { return (int)select_bit32_nr(x, ~(uint32_t)r, 0u); }
@@ -266,8 +320,11 @@ __device__ __forceinline__ int bs_popcount(const uint32_t (&x)[NW]) {
 // smaller), one v_max3 per two words; the word and its bit offset are bit-field inserts on the masks; and the one-hot
 // is one & m[w] & ~m[w + 1] -- one logic op per word, no compare, no select.  (v_bitop3 truth tables are indexed by
 // src0 * 4 + src1 * 2 + src2.  Spelled as plain C++ the masks went back to v_cmp + v_cndmask: 3 more slots per ply.)
-template <int NW>
-__device__ __forceinline__ int bs_select_hot(const uint32_t (&x)[NW], int r_, uint32_t (&hot)[NW]) {
+// TAB: the search inside the chosen word ends with a read of `tab`, an LDS copy of MnkSelectTable, and `cover()` runs
+// behind that read (select_bit32_nr_tab).
+template <int NW, bool TAB = false, typename Cover = MnkNoCover>
+__device__ __forceinline__ int bs_select_hot(const uint32_t (&x)[NW], int r_, uint32_t (&hot)[NW],
+                                             const uint8_t* tab = nullptr, Cover&& cover = Cover()) {
   const uint32_t nr = ~(uint32_t)r_;
   uint32_t m[NW + 1], word = x[0], base = 0u, rank = nr, pre = 0u;
   m[0] = ~0u;
@@ -281,7 +338,9 @@ __device__ __forceinline__ int bs_select_hot(const uint32_t (&x)[NW], int r_, ui
     word = __builtin_amdgcn_bitop3_b32(m[w], x[w], word, 0xca);  // m ? x[w] : word
     base = __builtin_amdgcn_bitop3_b32(m[w], 32u * w, base, 0xca);    // m ? 32 w : base
   }
-  const uint32_t pos = select_bit32_nr(word, rank, base);
+  uint32_t pos;
+  if constexpr (TAB) pos = select_bit32_nr_tab(word, rank, base, tab, cover);
+  else pos = select_bit32_nr(word, rank, base);
   const uint32_t one = 1u << (pos & 31u);
 #pragma unroll
   for (int w = 0; w < NW; ++w) hot[w] = __builtin_amdgcn_bitop3_b32(one, m[w], m[w + 1], 0x40);  // one & m[w] & ~m[w + 1]
@@ -329,11 +388,63 @@ __device__ __forceinline__ uint64_t philox_first_product(uint32_t c0) { return m
 // so that an xor never directly follows the multiply whose product it reads (see mnk_mul_wide).
 // The words are those of philox4x32_10, bit for bit: tests/test_gpu_rollout_lean2.py holds the loops that use this
 // form to the oracle's Philox (oracle/philox.py), the env id's low word wrapping inside a wave included.
+// PhiloxSteps: the block as a list of its 39 statements, numbered in the order philox4x32_10_from below has them, so
+// that a caller may run it in pieces (run<FROM, TO>(): the rollout's FAST loop makes the next trip's block a quarter
+// per ply, behind the ply's table read).
+struct PhiloxSteps {
+  static constexpr int COUNT = 39;
+  uint64_t A[11], B[11];
+  uint32_t n0[11], n2[11];
+  uint32_t c1, c2, c3, k0, k1;
+  __device__ __forceinline__ PhiloxSteps(uint64_t p0_first, uint32_t c1_, uint32_t c2_, uint32_t c3_, uint32_t k0_,
+                                         uint32_t k1_)
+      : c1(c1_), c2(c2_), c3(c3_), k0(k0_), k1(k1_) {
+    A[1] = p0_first;
+  }
+  // the xors of round r (keys of round r; c1 / c3 of round r are the low halves of round r - 1's products)
+  __device__ __forceinline__ void xor_n0(int r) {
+    n0[r] = __builtin_amdgcn_bitop3_b32((uint32_t)(B[r] >> 32), r == 1 ? c1 : (uint32_t)B[r - 1],
+                                        k0 + (uint32_t)(r - 1) * 0x9E3779B9u, 0x96);
+  }
+  __device__ __forceinline__ void xor_n2(int r) {
+    n2[r] = __builtin_amdgcn_bitop3_b32((uint32_t)(A[r] >> 32), r == 1 ? c3 : (uint32_t)A[r - 1],
+                                        k1 + (uint32_t)(r - 1) * 0xBB67AE85u, 0x96);
+  }
+  // statement s (a compile-time constant once unrolled): 0 and 1 open, then eight per pair of rounds r - 1, r
+  __device__ __forceinline__ void statement(int s) {
+    if (s == 0) { B[1] = mnk_mul_wide(c2, MNK_PHILOX_M1); return; }
+    if (s == 1) { xor_n2(1); return; }
+    if (s == 38) { xor_n2(10); return; }
+    const int r = 2 + 2 * ((s - 2) >> 3);
+    switch ((s - 2) & 7) {
+      case 0: B[r] = mnk_mul_wide(n2[r - 1], MNK_PHILOX_M1); break;
+      case 1: xor_n0(r - 1); break;
+      case 2: A[r] = mnk_mul_wide_vcc(n0[r - 1], MNK_PHILOX_M0); break;
+      case 3: xor_n0(r); break;
+      case 4: A[r + 1] = mnk_mul_wide_vcc(n0[r], MNK_PHILOX_M0); break;
+      case 5: xor_n2(r); break;
+      case 6: B[r + 1] = mnk_mul_wide(n2[r], MNK_PHILOX_M1); break;
+      default: xor_n2(r + 1); break;
+    }
+  }
+  template <int FROM, int TO>
+  __device__ __forceinline__ void run() {
+#pragma unroll
+    for (int s = FROM; s < TO; ++s) statement(s);
+  }
+  __device__ __forceinline__ Philox4 words() const {
+    Philox4 o;
+    o.v[0] = n0[10]; o.v[1] = (uint32_t)B[10]; o.v[2] = n2[10]; o.v[3] = (uint32_t)A[10];
+    return o;
+  }
+};
+
+// the block in one piece, for every other user of this form (kept as its own text: spelled through PhiloxSteps the
+// two-lane kernels came out with another register allocation, and they are to keep their code)
 __device__ __forceinline__ Philox4 philox4x32_10_from(uint64_t p0_first, uint32_t c1, uint32_t c2, uint32_t c3,
                                                       uint32_t k0, uint32_t k1) {
   uint64_t A[11], B[11];
   uint32_t n0[11], n2[11];
-  // the xors of round r (keys of round r; c1 / c3 of round r are the low halves of round r - 1's products)
 #define MNK_PHILOX_N0(r) \
   n0[r] = __builtin_amdgcn_bitop3_b32((uint32_t)(B[r] >> 32), (r) == 1 ? c1 : (uint32_t)B[(r) - 1], k0 + ((r) - 1) * 0x9E3779B9u, 0x96)
 #define MNK_PHILOX_N2(r) \
@@ -394,6 +505,13 @@ __device__ __forceinline__ Philox4 mnk_rng_block_from(uint64_t seed, uint64_t en
   return philox4x32_10_from(env_p0, (uint32_t)(env >> 32), (uint32_t)q,
                             stream | ((uint32_t)((q >> 32) & 0xFFFFFFu) << 8),
                             (uint32_t)seed, (uint32_t)(seed >> 32));
+}
+
+// ... and the same block not yet run: the caller runs its statements where it wants them
+__device__ __forceinline__ PhiloxSteps mnk_rng_steps_from(uint64_t seed, uint64_t env_p0, uint64_t env, uint64_t q,
+                                                          uint32_t stream) {
+  return PhiloxSteps(env_p0, (uint32_t)(env >> 32), (uint32_t)q, stream | ((uint32_t)((q >> 32) & 0xFFFFFFu) << 8),
+                     (uint32_t)seed, (uint32_t)(seed >> 32));
 }
 
 __device__ __forceinline__ uint32_t philox_word(const Philox4& b, uint32_t i) {

@@ -178,6 +178,14 @@ int mnk_probe_select_bits(const uint32_t* words, int nw, int64_t count, const in
   return mnk_launch_status("probe_select_bits");
 }
 
+int mnk_probe_select_table(uint8_t* out) {
+  if (!out) return MNK_EINVAL;
+  static constexpr MnkSelectTable table = MnkSelectTable();  // the generator the device's copy is made by
+  static_assert(sizeof(table.t) == MNK_SELECT_TABLE_BYTES, "the LDS copy is filled 2 KB at a time");
+  memcpy(out, &table.t[0][0], sizeof(table.t));
+  return MNK_OK;
+}
+
 int mnk_abi_version(void) { return MNK_ABI_VERSION; }
 
 int mnk_reload_config(void) {

@@ -47,9 +47,15 @@
 // SADDR (one-lane form only): the record stores address `uniform base + 32-bit lane offset` (global_store ... s[base])
 // instead of a 64-bit pointer per lane -- two address instructions fewer per ply; one launch may then write at
 // most 4 GiB of record rows (the launcher checks).
-template <int NW, int CN, int CK, bool RECORD, int ACT = 0, bool PAIR = false, int WS = 1, bool SADDR = false>
+// SELTAB (one-lane form, boards of at most three words, in both of their loops): the r-th-legal-cell select ends with
+// one byte read from `seltab`, the workgroup's LDS copy of MnkSelectTable (mnk_device.h), in place of its last three
+// halving levels.  The kernel fills the table before its first ply.  The record of the position and, in the FAST
+// loop, a quarter of the next trip's Philox block stand behind the read and cover its latency.
+template <int NW, int CN, int CK, bool RECORD, int ACT = 0, bool PAIR = false, int WS = 1, bool SADDR = false,
+          bool SELTAB = false>
 struct RolloutLane {
   static constexpr bool EXACT = CN != 0;
+  static constexpr bool TABLE = SELTAB;
   const MnkGeom& g;
   // The env in "mover first" form: cur = plane of the side to move, oth = the other plane.  A ply then ORs
   // one bit into cur, scans cur and swaps the two names (free: the loop is unrolled) -- no per-word selects
@@ -61,6 +67,7 @@ struct RolloutLane {
   uint32_t role = 0;       // PAIR: 0 / 1 within the lane pair
   uint32_t wrole = 0;      // WS > 1: this wave's index in its workgroup (wave-uniform)
   uint32_t* vx = nullptr;  // WS > 1: LDS verdicts u32[2][64][WS] (double-buffered by ply parity)
+  const uint8_t* seltab = nullptr;  // SELTAB: the select's byte table in LDS
   uint64_t* rp = nullptr;  // rec_planes[t][0][i]
   uint32_t* rm = nullptr;  // rec_meta[t][i]
   static constexpr bool OFF32 = SADDR || PAIR;  // the two-lane form always addresses its records this way
@@ -232,8 +239,9 @@ struct RolloutLane {
 
   // uniform legal cell from one u32 (oracle/philox.py pick_legal; selfplay/policy.py:18-29): the action, and
   // the cell's bit as a one-hot string
-  template <bool FAST = false>
-  __device__ __forceinline__ int pick(uint32_t x, uint32_t (&hot)[NW], uint32_t& nlegal) const {
+  // SELTAB: `cover()` runs behind the select's table read
+  template <bool FAST = false, typename Cover = MnkNoCover>
+  __device__ __forceinline__ int pick(uint32_t x, uint32_t (&hot)[NW], uint32_t& nlegal, Cover&& cover = Cover()) const {
     uint32_t legal[NW];
 #pragma unroll
     for (int w = 0; w < NW; ++w) legal[w] = ~(cur[w] | oth[w]) & g.valid[w];
@@ -249,17 +257,22 @@ struct RolloutLane {
       n = nl ? nl : g.C;
     }
     const int r = (int)__umulhi(x, (uint32_t)n);
-    const uint32_t bit = (uint32_t)bs_select_hot<NW>(legal, r, hot);
+    const uint32_t bit = (uint32_t)bs_select_hot<NW, SELTAB>(legal, r, hot, seltab, cover);
     return mnk_bit_cell<CN>(g, bit);
   }
 
   // field = position of this ply inside its group of four (= step & 3; a compile-time constant in
   // the unrolled main loop, so the log costs one shift-or per ply and one wide store per four)
-  template <bool FAST = false>
-  __device__ __forceinline__ void ply(uint32_t x, int field) {
+  // SELTAB: the record of the position before the move -- it does not hang on the pick -- is stored behind the select's
+  // table read, after `ahead()`, work of the caller's that does not hang on it either (a share of the next Philox block)
+  template <bool FAST = false, typename Ahead = MnkNoCover>
+  __device__ __forceinline__ void ply(uint32_t x, int field, Ahead&& ahead = Ahead()) {
     uint32_t hot[NW];
     uint32_t nlegal;
-    const int a = pick<FAST>(x, hot, nlegal);
+    const int a = pick<FAST>(x, hot, nlegal, [&]() {
+      ahead();
+      if (RECORD) store_record();
+    });
     if constexpr (ACT == 3) {
       q32 |= (uint32_t)a << (7 * field);
       if (field == 3) log_flush();
@@ -271,7 +284,7 @@ struct RolloutLane {
       quad |= (uint64_t)(uint32_t)a << (8 * ACT * field);
       if (field == 3) log_flush();
     }
-    ply_hot<FAST>(a, hot, nlegal);
+    ply_hot<FAST, SELTAB>(a, hot, nlegal);
   }
 
   // one ply with a known-good action (from an action log the sampler wrote)
@@ -291,9 +304,10 @@ struct RolloutLane {
   // env/torch_vector_mnk_env.py:60-84 for the mover, then env.reset(nonzero(done)) :34-44
   // FAST (see the top of this file): `moves` is not maintained -- the board is full after this ply iff the move took
   // the last legal cell (nlegal == 1); finish_fast() restores the counter from the board when the loop is over
-  template <bool FAST = false>
+  // STORED: the caller has stored the position's record already
+  template <bool FAST = false, bool STORED = false>
   __device__ __forceinline__ void ply_hot(int a, const uint32_t (&hot)[NW], uint32_t nlegal = 0) {
-    if (RECORD) store_record();
+    if (RECORD && !STORED) store_record();
 #pragma unroll
     for (int w = 0; w < NW; ++w) cur[w] |= hot[w];                    // :68
     if (!FAST) ++moves;                                               // :69
@@ -410,12 +424,26 @@ __device__ __forceinline__ void rollout_plies(Lane& L, int T, uint64_t seed, uin
     // up by one, where `t` against T and `step` cost the trip a second counter and two 64-bit shifts
     const int blocks = (T - t) >> 2;
     uint64_t q = step >> 2;
-    for (int left = blocks; left > 0; --left, ++q) {
-      const Philox4 blk = block(q);
-      L.template ply<FAST>(blk.v[0], 0);
-      L.template ply<FAST>(blk.v[1], 1);
-      L.template ply<FAST>(blk.v[2], 2);
-      L.template ply<FAST>(blk.v[3], 3);
+    if constexpr (Lane::TABLE && LEAN) {
+      // the block of the NEXT trip is made during this one, a quarter behind each ply's table read: its rounds hang on
+      // nothing the plies compute, so they cover the read's latency (the last trip makes one block that nobody uses)
+      Philox4 blk = block(q);
+      for (int left = blocks; left > 0; --left) {
+        PhiloxSteps next = mnk_rng_steps_from(seed, env_p0, env, ++q, MNK_STREAM_MOVE);
+        L.template ply<FAST>(blk.v[0], 0, [&]() { next.template run<0, 10>(); });
+        L.template ply<FAST>(blk.v[1], 1, [&]() { next.template run<10, 20>(); });
+        L.template ply<FAST>(blk.v[2], 2, [&]() { next.template run<20, 30>(); });
+        L.template ply<FAST>(blk.v[3], 3, [&]() { next.template run<30, PhiloxSteps::COUNT>(); });
+        blk = next.words();
+      }
+    } else {
+      for (int left = blocks; left > 0; --left, ++q) {
+        const Philox4 blk = block(q);
+        L.template ply<FAST>(blk.v[0], 0);
+        L.template ply<FAST>(blk.v[1], 1);
+        L.template ply<FAST>(blk.v[2], 2);
+        L.template ply<FAST>(blk.v[3], 3);
+      }
     }
     t += blocks << 2;
     step += (uint64_t)blocks << 2;
@@ -444,10 +472,21 @@ __device__ __forceinline__ void rollout_random_body(const MnkGeom& g, uint64_t* 
   // (gfx950 does not skip the idle half of a wave64), see DESIGN.md
   __shared__ unsigned int lds_stats[MNK_STATS_COUNTERS];
   if (threadIdx.x < MNK_STATS_COUNTERS) lds_stats[threadIdx.x] = 0u;
+  // the boards of at most three words end their select with a table read: every thread of the wave fills its share, a
+  // partly filled last wave included.  Not 13x13, the other kernel with a FAST loop: with the table it measured
+  // 130.2 -> 131.0 us per 256 plies at 65 536 envs, so it keeps its arithmetic select.
+  constexpr bool SELTAB = NW <= 3;
+  const uint8_t* seltab = nullptr;
+  if constexpr (SELTAB) {
+    __shared__ uint32_t lds_seltab[MNK_SELECT_TABLE_BYTES / 4];
+    mnk_select_table_fill(lds_seltab);
+    seltab = (const uint8_t*)lds_seltab;
+  }
   __syncthreads();
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < N) {
-    RolloutLane<NW, CN, CK, RECORD, ACT, false, 1, SADDR> L(g, N, i, rec_planes, rec_meta, act_log);
+    RolloutLane<NW, CN, CK, RECORD, ACT, false, 1, SADDR, SELTAB> L(g, N, i, rec_planes, rec_meta, act_log);
+    L.seltab = seltab;
     L.log_begin(act_log, T, i);
     L.load(planes, meta, i);
     const uint64_t env = (uint64_t)(env_id0 + i);

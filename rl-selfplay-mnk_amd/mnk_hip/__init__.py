@@ -176,6 +176,7 @@ SIGNATURES = {
     "mnk_comm_version": [],
     "mnk_probe_record_writes": [_vp, _i64, _i, _i, _vp],
     "mnk_probe_select_bits": [_vp, _i, _i64, _vp, _vp, _vp, _vp],
+    "mnk_probe_select_table": [_vp],
 }
 
 _STATUS = {-1: "invalid argument (null pointer / negative size)", -2: "unsupported board geometry",

@@ -4,7 +4,9 @@ usage: python tools/isa_ply_table.py [asm file]      (default: compiles csrc/mnk
 Finds k_rollout_random<3, 9, 5, true, 0, true> (the headline kernel: 9x9x5, records, 32-bit-offset stores), takes its
 innermost loops that hold four plies (16 global stores), and counts the instructions of one trip by class / 4.
 The kernel has two such loops since round 3: the FAST one (waves of consistent games) has no branch but its own, the
-general one keeps the "no legal cell" branch in every ply."""
+general one keeps the "no legal cell" branch in every ply.
+Where the select ends with an LDS table read it also prints, ply by ply, how many instructions stand between the
+`ds_read` and the `s_waitcnt lgkmcnt` that retires it: the cover for the read's latency."""
 import collections
 import os
 import re
@@ -22,6 +24,7 @@ CLASSES = [
     ("integer arithmetic (v_add / sub / mad / mul / add3)", r"v_(add|sub|mad|mul|add3)"),
     ("moves (v_mov)", r"v_mov"),
     ("other VALU", r"v_"),
+    ("LDS (ds_read / ds_write)", r"ds_"),
     ("global stores", r"global_store"),
     ("global loads", r"global_load"),
     ("scalar ALU / moves", r"s_(?!cbranch|branch|nop|waitcnt|barrier)"),
@@ -85,12 +88,22 @@ def main():
     print("|---|" + "---|" * len(four))
     for cname, vals in table.items():
         print(f"| {cname} | " + " | ".join(f"{v:.2f}" for v in vals) + " |")
-    valu = [sum(v[i] for c, v in table.items() if c.split()[0] not in ("global", "scalar", "branches", "s_nop")) for i in range(len(four))]
+    valu = [sum(v[i] for c, v in table.items() if c.split()[0] not in ("LDS", "global", "scalar", "branches", "s_nop")) for i in range(len(four))]
     print("| **VALU total** | " + " | ".join(f"**{v:.2f}**" for v in valu) + " |")
     print("| **all instructions** | " + " | ".join(f"**{v:.2f}**" for v in totals) + " |")
     print("\nPer four plies the trip also holds one Philox4x32-10 block, `v_mad_u64_u32` (inline assembly) and `v_bitop3_b32` "
           "(three-input xor; what of round 1 does not change from block to block is made outside the loop), counted above under integer arithmetic / bit logic; the r-th-set-bit select is 23 instructions "
-          "of inline assembly per ply (5 per halving level).")
+          "of inline assembly per ply (5 per halving level); where it ends with the LDS byte table, 13 and one `ds_read_u8`.")
+    # how much stands between a ply's table read and the wait that retires it: the cover for the read's latency
+    for name, (lab, body) in zip(names, four):
+        gaps = []
+        for i, ins in enumerate(body):
+            if ins.startswith("ds_read"):
+                wait = next((j for j in range(i + 1, len(body)) if re.match(r"s_waitcnt\s+.*lgkmcnt", body[j])), None)
+                gaps.append("no wait in the trip" if wait is None else str(wait - i - 1))
+        if gaps:
+            print(f"\nInstructions between each `ds_read` and the `s_waitcnt lgkmcnt` that retires it, {name.split(' (')[0]}, "
+                  "ply by ply: " + ", ".join(gaps) + ".")
 
 
 if __name__ == "__main__":
