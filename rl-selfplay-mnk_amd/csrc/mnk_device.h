@@ -248,7 +248,7 @@ __device__ __forceinline__ uint32_t select_bit32_nr(uint32_t x, uint32_t nr, uin
 }
 // The tail of the same search as one LDS byte read: the last three levels (8 -> 4 -> 2 -> 1, 13 slots) only answer
 // "where is the r-th set bit of this byte, r < 8", a function of 11 bits.  MnkSelectTable is that function as a table,
-// t[b][r] = position of the r-th (0-based) set bit of byte b, 0 where r >= popcount(b); mnk_select_table_fill copies it
+// t[b][r] = position of the r-th (0-based) set bit of byte b, 0 where r >= popcount(b); mnk_select_table_fetch / _put copy it
 // into 2 KB of a one-wave workgroup's LDS, and select_bit32_nr_tab runs the 16- and 8-level steps as above, then reads
 // t[byte at pos][~nr].  The read is plain C++, not part of the assembly: the compiler counts it in its own s_waitcnt,
 // which it puts before the first use -- behind the caller's cover(), see below.
@@ -265,12 +265,20 @@ struct MnkSelectTable {
 #define MNK_SELECT_TABLE_BYTES 2048
 static __device__ const MnkSelectTable mnk_select_table_rom = MnkSelectTable();
 
-// all 64 threads of a one-wave workgroup: 32 bytes each, global -> LDS; the caller's __syncthreads() publishes it
-__device__ __forceinline__ void mnk_select_table_fill(uint32_t* lds_table) {
+// all 64 threads of a one-wave workgroup: 32 bytes each, global -> LDS; the caller's __syncthreads() publishes it.
+// In two halves, so that the caller can issue other loads of its own (the env's state) between the table's loads and
+// the wait that the LDS writes need: one round trip to memory for both, not one after the other.
+struct MnkSelectTableShare {
+  uint4 lo, hi;
+};
+__device__ __forceinline__ MnkSelectTableShare mnk_select_table_fetch() {
   const uint4* src = (const uint4*)&mnk_select_table_rom.t[0][0];
+  return {src[threadIdx.x], src[threadIdx.x + 64u]};
+}
+__device__ __forceinline__ void mnk_select_table_put(uint32_t* lds_table, const MnkSelectTableShare& s) {
   uint4* dst = (uint4*)lds_table;
-  dst[threadIdx.x] = src[threadIdx.x];
-  dst[threadIdx.x + 64u] = src[threadIdx.x + 64u];
+  dst[threadIdx.x] = s.lo;
+  dst[threadIdx.x + 64u] = s.hi;
 }
 
 // `cover()` stands between the read and the first use of what it returns: work of the caller's that does not hang on the
@@ -301,6 +309,55 @@ __device__ __forceinline__ uint32_t select_bit32_nr_tab(uint32_t x, uint32_t nr,
   return pos | in_byte;
 }
 #undef MNK_SELECT_LEVEL
+
+// ---------------------------------------------------------------- the rollout statistics of a wave
+// The five counters of `stats` (episodes, black wins, white wins, draws, summed lengths) from per-lane counts, without
+// a pass over the lanes: an atomicAdd of a per-lane value on one LDS word makes the compiler scan the active lanes one
+// by one (find the lane, v_readlane, add, branch: seven scalar-side instructions and a taken branch per lane and
+// counter -- some 250 trips a wave at the headline).  mnk_wave_sum is gfx9's DPP add ladder instead: every lane of a
+// row of 16 gets the sum of its row up to itself (row_shr 1 / 2 / 3 of the value, then row_shr 4 and 8 of the partial
+// sums), row_bcast:15 carries a row's total into the next row, row_bcast:31 the first half's into the second: lane
+// 63 ends with the wave's total.  Lanes that a shift leaves without a source add the `old` operand, zero.
+// ALL 64 LANES MUST BE ACTIVE (a lane that is switched off sends nothing): callers zero the counts of lanes that carry
+// no env and fold outside their `i < N` branch.
+template <int CTRL, int ROW_MASK = 0xF, int BANK_MASK = 0xF>
+__device__ __forceinline__ uint32_t mnk_dpp_or_zero(uint32_t v) {
+  return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, ROW_MASK, BANK_MASK, false);
+}
+__device__ __forceinline__ uint32_t mnk_wave_sum(uint32_t v) {  // the total, in lane 63
+  uint32_t s = v + mnk_dpp_or_zero<0x111>(v);  // row_shr:1
+  s += mnk_dpp_or_zero<0x112>(v);              // row_shr:2
+  s += mnk_dpp_or_zero<0x113>(v);              // row_shr:3 -- lanes hold v[l-3 .. l] of their row
+  s += mnk_dpp_or_zero<0x114, 0xF, 0xE>(s);    // row_shr:4, not into lanes 0-3 of a row
+  s += mnk_dpp_or_zero<0x118, 0xF, 0xC>(s);    // row_shr:8, into lanes 8-15 of a row: lane 15 has the row's sum
+  s += mnk_dpp_or_zero<0x142, 0xA>(s);         // row_bcast:15 into rows 1 and 3
+  s += mnk_dpp_or_zero<0x143, 0xC>(s);         // row_bcast:31 into rows 2 and 3
+  return s;
+}
+// Lane c < MNK_STATS_COUNTERS of the wave gets the wave's total of counter c (every other lane 0).  The four sums fit
+// 32 bits for every legal launch: 64 lanes x (C + 65 535) at the most.  Draws are episodes minus wins, of the totals.
+__device__ __forceinline__ uint32_t mnk_stats_wave_totals(uint32_t done, uint32_t black, uint32_t white, uint32_t len) {
+  const uint32_t d = (uint32_t)__builtin_amdgcn_readlane((int)mnk_wave_sum(done), 63);
+  const uint32_t b = (uint32_t)__builtin_amdgcn_readlane((int)mnk_wave_sum(black), 63);
+  const uint32_t w = (uint32_t)__builtin_amdgcn_readlane((int)mnk_wave_sum(white), 63);
+  const uint32_t l = (uint32_t)__builtin_amdgcn_readlane((int)mnk_wave_sum(len), 63);
+  uint32_t v = 0;  // (one v_writelane per counter: a chain of selects on the lane number became a tree of branches)
+  asm("v_writelane_b32 %0, %1, 0\n\t"
+      "v_writelane_b32 %0, %2, 1\n\t"
+      "v_writelane_b32 %0, %3, 2\n\t"
+      "v_writelane_b32 %0, %4, 3\n\t"
+      "v_writelane_b32 %0, %5, 4"
+      : "+v"(v)
+      : "s"(d), "s"(b), "s"(w), "s"(d - b - w), "s"(l));
+  return v;
+}
+// a one-wave workgroup's totals into its replica of `stats`: one global atomic per counter that is not zero (spread
+// over MNK_STATS_REPLICAS cache lines: thousands of adds on five addresses would serialise at ~11 ns each -- measured:
+// 56 us per launch)
+__device__ __forceinline__ void mnk_stats_wave_commit(unsigned long long* stats, uint32_t total) {
+  if (threadIdx.x < MNK_STATS_COUNTERS && total)
+    atomicAdd(&stats[(size_t)(blockIdx.x % MNK_STATS_REPLICAS) * MNK_STATS_STRIDE + threadIdx.x], (unsigned long long)total);
+}
 
 __device__ __forceinline__ int select_bit32(uint32_t x, int r) { return (int)select_bit32_nr(x, ~(uint32_t)r, 0u); }
 

@@ -127,6 +127,27 @@ struct RolloutLane {
     }
   }
 
+  // the same from a state that env_load has fetched: a kernel can then issue the loads early and consume them behind
+  // other work
+  __device__ __forceinline__ void take(const MnkEnv<NW>& e) {
+    side = e.meta & 1u;
+    moves = moves_in = e.meta >> 1;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      cur[w] = side ? e.p[1][w] : e.p[0][w];
+      oth[w] = side ? e.p[0][w] : e.p[1][w];
+    }
+  }
+
+  // this lane's counts of the launch as the wave fold takes them (mnk_stats_wave_totals): episodes, black wins, white
+  // wins, summed lengths
+  __device__ __forceinline__ void stat_counts(int T, uint32_t (&c)[4]) const {
+    c[0] = acc_done();
+    c[1] = acc_win() - acc_white;
+    c[2] = acc_white;
+    c[3] = moves_in + (uint32_t)T - moves;
+  }
+
   // (black, white) planes of the current position to memory at `dst`
   __device__ __forceinline__ void store_planes(uint64_t* dst, int64_t i) const {
     uint32_t p0[NW], p1[NW];
@@ -470,25 +491,32 @@ __device__ __forceinline__ void rollout_random_body(const MnkGeom& g, uint64_t* 
                                                     void* act_log) {
   // one full wave of 64 envs per workgroup: half-filled waves were measured and are slower
   // (gfx950 does not skip the idle half of a wave64), see DESIGN.md
-  __shared__ unsigned int lds_stats[MNK_STATS_COUNTERS];
-  if (threadIdx.x < MNK_STATS_COUNTERS) lds_stats[threadIdx.x] = 0u;
   // the boards of at most three words end their select with a table read: every thread of the wave fills its share, a
   // partly filled last wave included.  Not 13x13, the other kernel with a FAST loop: with the table it measured
   // 130.2 -> 131.0 us per 256 plies at 65 536 envs, so it keeps its arithmetic select.
   constexpr bool SELTAB = NW <= 3;
+  using Lane = RolloutLane<NW, CN, CK, RECORD, ACT, false, 1, SADDR, SELTAB>;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const uint8_t* seltab = nullptr;
+  // SELTAB: the table's loads and the state's are in flight together -- one round trip to memory before the first ply,
+  // where filling the table first and loading the state behind its barrier made two, one after the other
+  MnkEnv<NW> start;
   if constexpr (SELTAB) {
     __shared__ uint32_t lds_seltab[MNK_SELECT_TABLE_BYTES / 4];
-    mnk_select_table_fill(lds_seltab);
+    const MnkSelectTableShare share = mnk_select_table_fetch();
+    env_clear(start);
+    if (i < N) env_load<NW, Lane::EXACT>(start, planes, meta, N, g.W, i);
+    mnk_select_table_put(lds_seltab, share);
     seltab = (const uint8_t*)lds_seltab;
+    __syncthreads();
   }
-  __syncthreads();
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  uint32_t counts[4] = {0u, 0u, 0u, 0u};  // a lane without an env counts nothing
   if (i < N) {
-    RolloutLane<NW, CN, CK, RECORD, ACT, false, 1, SADDR, SELTAB> L(g, N, i, rec_planes, rec_meta, act_log);
+    Lane L(g, N, i, rec_planes, rec_meta, act_log);
     L.seltab = seltab;
     L.log_begin(act_log, T, i);
-    L.load(planes, meta, i);
+    if constexpr (SELTAB) L.take(start);
+    else L.load(planes, meta, i);
     const uint64_t env = (uint64_t)(env_id0 + i);
     // every lane of this wave in a consistent game (any state the env produced itself): the FAST loop; a wave that
     // holds a poked state plays this launch on the general loop.  Same records either way.
@@ -505,21 +533,10 @@ __device__ __forceinline__ void rollout_random_body(const MnkGeom& g, uint64_t* 
     }
     L.log_finish(T);  // T not a multiple of 4: the last word is partly filled
     L.store(planes, meta, i);
-    if (stats) {
-      const uint32_t len_sum = L.moves_in + (uint32_t)T - L.moves;
-      if (L.acc_done()) atomicAdd(&lds_stats[0], L.acc_done());
-      if (L.acc_win() - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win() - L.acc_white);
-      if (L.acc_white) atomicAdd(&lds_stats[2], L.acc_white);
-      if (L.acc_done() - L.acc_win()) atomicAdd(&lds_stats[3], L.acc_done() - L.acc_win());
-      if (len_sum) atomicAdd(&lds_stats[4], len_sum);
-    }
+    L.stat_counts(T, counts);
   }
-  __syncthreads();
-  // one global atomic per counter per wave, spread over MNK_STATS_REPLICAS cache lines: thousands
-  // of adds on five addresses would serialise at ~11 ns each (measured: 56 us per launch)
-  if (stats && threadIdx.x < MNK_STATS_COUNTERS && lds_stats[threadIdx.x])
-    atomicAdd(&stats[(size_t)(blockIdx.x % MNK_STATS_REPLICAS) * MNK_STATS_STRIDE + threadIdx.x],
-              (unsigned long long)lds_stats[threadIdx.x]);
+  // the whole wave again: the fold needs every lane (mnk_device.h)
+  if (stats) mnk_stats_wave_commit(stats, mnk_stats_wave_totals(counts[0], counts[1], counts[2], counts[3]));
 }
 
 // ------------------------------------------------------------------ two lanes per env (scan directions split)
@@ -556,11 +573,9 @@ template <int NW, int CN, int CK, bool RECORD, int ACT>
 __device__ __forceinline__ void rollout_random_pair_body(const MnkGeom& g, uint64_t* planes, uint32_t* meta, int64_t N, int T,
                                                          uint64_t seed, uint64_t step0, int64_t env_id0, uint64_t* rec_planes,
                                                          uint32_t* rec_meta, unsigned long long* stats, void* act_log) {
-  __shared__ unsigned int lds_stats[MNK_STATS_COUNTERS];
-  if (threadIdx.x < MNK_STATS_COUNTERS) lds_stats[threadIdx.x] = 0u;
-  __syncthreads();
   const uint32_t role = threadIdx.x & 1u;
   const int64_t i = (int64_t)blockIdx.x * 32 + (threadIdx.x >> 1);  // env of this lane pair
+  uint32_t counts[4] = {0u, 0u, 0u, 0u};  // a lane without an env, and the second lane of every pair, count nothing
   if (i < N) {
     RolloutLane<NW, CN, CK, RECORD, ACT, true> L(g, N, i, rec_planes, rec_meta, act_log, role);
     L.load(planes, meta, i);
@@ -576,19 +591,9 @@ __device__ __forceinline__ void rollout_random_pair_body(const MnkGeom& g, uint6
     }
     if (ACT && (T & 3)) L.log_flush();
     L.store(planes, meta, i);  // lane `role` stores plane `role`; the meta word is written by both
-    if (stats && role == 0) {
-      const uint32_t len_sum = L.moves_in + (uint32_t)T - L.moves;
-      if (L.acc_done()) atomicAdd(&lds_stats[0], L.acc_done());
-      if (L.acc_win() - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win() - L.acc_white);
-      if (L.acc_white) atomicAdd(&lds_stats[2], L.acc_white);
-      if (L.acc_done() - L.acc_win()) atomicAdd(&lds_stats[3], L.acc_done() - L.acc_win());
-      if (len_sum) atomicAdd(&lds_stats[4], len_sum);
-    }
+    if (role == 0) L.stat_counts(T, counts);
   }
-  __syncthreads();
-  if (stats && threadIdx.x < MNK_STATS_COUNTERS && lds_stats[threadIdx.x])
-    atomicAdd(&stats[(size_t)(blockIdx.x % MNK_STATS_REPLICAS) * MNK_STATS_STRIDE + threadIdx.x],
-              (unsigned long long)lds_stats[threadIdx.x]);
+  if (stats) mnk_stats_wave_commit(stats, mnk_stats_wave_totals(counts[0], counts[1], counts[2], counts[3]));
 }
 
 // ------------------------------------------------------------------ replay of an action log (one lane per env)

@@ -316,11 +316,9 @@ __global__ void __launch_bounds__(64)
 k_rollout_random_pairw(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int T, uint64_t seed, uint64_t step0,
                        int64_t env_id0, uint64_t* rec_planes, uint32_t* rec_meta, unsigned long long* stats,
                        void* act_log) {
-  __shared__ unsigned int lds_stats[MNK_STATS_COUNTERS];
-  if (threadIdx.x < MNK_STATS_COUNTERS) lds_stats[threadIdx.x] = 0u;
-  __syncthreads();
   const uint32_t role = threadIdx.x & 1u;
   const int64_t i = (int64_t)blockIdx.x * 32 + (threadIdx.x >> 1);  // env of this lane pair
+  uint32_t counts[4] = {0u, 0u, 0u, 0u};  // a lane without an env, and the second lane of every pair, count nothing
   if (i < N) {
     RolloutPairW<NW, CN, CK, RECORD, ACT> L(g, N, i, role, rec_planes, rec_meta, act_log);
     L.log_begin(act_log, T, i);
@@ -337,19 +335,15 @@ k_rollout_random_pairw(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, i
     }
     L.log_finish(T);
     L.store(planes, meta, i);
-    if (stats && role == 0) {
-      const uint32_t len_sum = L.moves_in + (uint32_t)T - L.moves;
-      if (L.acc_done) atomicAdd(&lds_stats[0], L.acc_done);
-      if (L.acc_win - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win - L.acc_white);
-      if (L.acc_white) atomicAdd(&lds_stats[2], L.acc_white);
-      if (L.acc_done - L.acc_win) atomicAdd(&lds_stats[3], L.acc_done - L.acc_win);
-      if (len_sum) atomicAdd(&lds_stats[4], len_sum);
+    if (role == 0) {
+      counts[0] = L.acc_done;
+      counts[1] = L.acc_win - L.acc_white;
+      counts[2] = L.acc_white;
+      counts[3] = L.moves_in + (uint32_t)T - L.moves;
     }
   }
-  __syncthreads();
-  if (stats && threadIdx.x < MNK_STATS_COUNTERS && lds_stats[threadIdx.x])
-    atomicAdd(&stats[(size_t)(blockIdx.x % MNK_STATS_REPLICAS) * MNK_STATS_STRIDE + threadIdx.x],
-              (unsigned long long)lds_stats[threadIdx.x]);
+  // the whole wave again: the fold needs every lane (mnk_device.h)
+  if (stats) mnk_stats_wave_commit(stats, mnk_stats_wave_totals(counts[0], counts[1], counts[2], counts[3]));
 }
 
 }  // namespace

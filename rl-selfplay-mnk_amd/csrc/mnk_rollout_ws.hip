@@ -28,6 +28,7 @@ k_rollout_random_ws(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int 
   __syncthreads();
   const uint32_t wrole = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   const int64_t i = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  uint32_t counts[4] = {0u, 0u, 0u, 0u};  // a lane without an env counts nothing
   if (i < N) {
     RolloutLane<NW, CN, CK, RECORD, ACT, false, WS> L(g, N, i, rec_planes, rec_meta, act_log, 0, wrole, lds_verdict);
     L.load(planes, meta, i);
@@ -50,17 +51,14 @@ k_rollout_random_ws(MnkGeom g, uint64_t* planes, uint32_t* meta, int64_t N, int 
       for (uint32_t j = 0; t < T; ++t, ++j) L.ply(philox_word(blk, j), (int)j);
     }
     if (ACT && (T & 3)) L.log_flush();
-    if (wrole == 0) {  // every wave of the group ends in the same state
-      L.store(planes, meta, i);
-      if (stats) {
-        const uint32_t len_sum = L.moves_in + (uint32_t)T - L.moves;
-        if (L.acc_done()) atomicAdd(&lds_stats[0], L.acc_done());
-        if (L.acc_win() - L.acc_white) atomicAdd(&lds_stats[1], L.acc_win() - L.acc_white);
-        if (L.acc_white) atomicAdd(&lds_stats[2], L.acc_white);
-        if (L.acc_done() - L.acc_win()) atomicAdd(&lds_stats[3], L.acc_done() - L.acc_win());
-        if (len_sum) atomicAdd(&lds_stats[4], len_sum);
-      }
-    }
+    if (wrole == 0) L.store(planes, meta, i);  // every wave of the group ends in the same state
+    L.stat_counts(T, counts);
+  }
+  // every wave of the group holds the same games: wave 0 counts them, with all of its lanes (mnk_device.h), and feeds
+  // the stage between the waves one add per counter -- lanes 0-4, each on its own word
+  if (stats && wrole == 0) {
+    const uint32_t total = mnk_stats_wave_totals(counts[0], counts[1], counts[2], counts[3]);
+    if (threadIdx.x < MNK_STATS_COUNTERS && total) atomicAdd(&lds_stats[threadIdx.x], total);
   }
   __syncthreads();
   if (stats && threadIdx.x < MNK_STATS_COUNTERS && lds_stats[threadIdx.x])

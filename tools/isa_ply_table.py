@@ -64,6 +64,7 @@ def main():
                 body = [x.strip() for x in lines[i + 1:j + 1] if x.startswith("\t") and not x.strip().startswith((";", "."))]
                 loops.append((label, body))
                 break
+    outside = outside_the_ply_loops(lines)
     four = [(lab, b) for lab, b in loops if sum(x.startswith("global_store") for x in b) == 16]
     four.sort(key=lambda lb: sum(bool(re.match(r"s_(cbranch|branch)", x)) for x in lb[1]))  # the FAST loop first
     print("# Per-ply instruction table of the headline rollout kernel, from the ISA\n")
@@ -104,6 +105,31 @@ def main():
         if gaps:
             print(f"\nInstructions between each `ds_read` and the `s_waitcnt lgkmcnt` that retires it, {name.split(' (')[0]}, "
                   "ply by ply: " + ", ".join(gaps) + ".")
+    before, after, stray, scans = outside
+    print(f"\nOutside the ply loops (every loop that holds a record store: the two above, and the head and tail loops of a launch "
+          f"that does not start or end on a Philox block), in the order of the text: {before} instructions before the first, "
+          f"{after} after the last; {stray} loops outside them, {scans} of which step through the lanes with `v_readlane_b32`.")
+
+
+def is_instruction(line):
+    return line.startswith("\t") and not line.strip().startswith((";", "."))
+
+
+def outside_the_ply_loops(lines):
+    """(instructions before the first ply loop, after the last, loops that are not ply loops and not inside one, how many
+    of those read one lane per trip).  A loop: a label and the last branch back to it; a ply loop: one that holds a
+    global store."""
+    at = {m.group(1): i for i, line in enumerate(lines) for m in [re.match(r"^(\.LBB\d+_\d+):", line)] if m}
+    spans = {}
+    for j, line in enumerate(lines):
+        m = re.search(r"s_c?branch\w*\s+(\.LBB\d+_\d+)\b", line)
+        if m and m.group(1) in at and at[m.group(1)] < j:
+            spans[at[m.group(1)]] = j
+    ply = [(i, j) for i, j in spans.items() if any("global_store" in x for x in lines[i:j])]
+    first, last = min(i for i, _ in ply), max(j for _, j in ply)
+    stray = [(i, j) for i, j in spans.items() if (i, j) not in ply and not any(a < i and j <= b for a, b in ply)]
+    scans = sum(any("v_readlane_b32" in x for x in lines[i:j]) for i, j in stray)
+    return (sum(map(is_instruction, lines[:first])), sum(map(is_instruction, lines[last + 1:])), len(stray), scans)
 
 
 if __name__ == "__main__":
