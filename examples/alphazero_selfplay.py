@@ -16,14 +16,17 @@ only, and every row plays on as soon as its own search is done (playout cap rand
 goes to the rows the player marks ``fresh``.  They combine with ``--noise builtin`` (``AsyncSearchSelfPlay(root_noise=...)``:
 the noise is drawn inside the player's one launch, on the roots of the full plies), with ``--solver`` (a row whose root
 is proven plays at once) and with ``--reuse`` (``AsyncSearchSelfPlay(keep_tree=True)``: a fast ply searches on top of the
-subtree the searches before it left; the trees are dropped after each training round here too); not with ``--leaves`` or
-``--search gumbel``.
+subtree the searches before it left; the trees are dropped after each training round here too) and with ``--leaves L``
+(``AsyncSearchSelfPlay(leaves=L)``: the network sees envs * L positions per call and a ply of budget B takes ceil(B / L) +
+1 calls; the wrapper's noise then goes to slot 0 of the fresh rows, batch row i * L); not ``--leaves`` with ``--reuse``, and
+not with ``--search gumbel``.
 
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse] [--solver]
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --search gumbel --iterations 16
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25 --noise builtin --solver
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25 --reuse
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 6 --full-prob 0.25 --leaves 4 --noise builtin --solver
 """
 import argparse
 import os
@@ -79,10 +82,11 @@ class RootNoise:
 
 class FreshRootNoise:
     """``RootNoise`` for ``AsyncSearchSelfPlay``, whose rows reach their roots at different calls: the noise goes to the rows
-    of ``fresh()`` (uint8 [N], the player's ``fresh``), in every call; no host synchronisation"""
+    of ``fresh()`` (uint8 [N], the player's ``fresh``), in every call; no host synchronisation.  With ``leaves`` = L
+    positions per row the batch has N * L rows and a fresh row's root is its slot 0, batch row i * L"""
 
-    def __init__(self, inner, alpha=0.3, eps=0.25):
-        self.inner, self.alpha, self.eps, self.fresh = inner, alpha, eps, None
+    def __init__(self, inner, alpha=0.3, eps=0.25, leaves=1):
+        self.inner, self.alpha, self.eps, self.fresh, self.leaves = inner, alpha, eps, None, leaves
 
     def __call__(self, leaf_obs, leaf_mask):
         priors, values = self.inner(leaf_obs, leaf_mask)
@@ -92,6 +96,8 @@ class FreshRootNoise:
         noise = torch.distributions.Dirichlet(conc, validate_args=False).sample() * leaf_mask
         noise = noise / noise.sum(dim=1, keepdim=True).clamp(min=1e-12)
         eps = self.eps * self.fresh().to(torch.float32).unsqueeze(1)
+        if self.leaves > 1:  # [N] -> [N * L]: slot 0 of every row
+            eps = torch.cat([eps, eps.new_zeros(len(eps), self.leaves - 1)], dim=1).reshape(-1, 1)
         return (1 - eps) * priors.float() + eps * noise, values
 
 
@@ -134,7 +140,7 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
         raise ValueError("fast_iterations and full_prob go together")
     if fast_iterations is not None:
         return _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies,
-                            updates, batch, seed, noise, solver, reuse, leaves != 1 or search != "puct", log)
+                            updates, batch, seed, noise, solver, reuse, leaves, search != "puct", log)
     if noise == "wrapper":
         evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
@@ -168,23 +174,26 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
 
 
 def _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies, updates, batch,
-                 seed, noise, solver, reuse, unsupported, log):
+                 seed, noise, solver, reuse, leaves, unsupported, log):
     """``train`` through ``AsyncSearchSelfPlay``: a training round follows as many evaluator calls as ``plies`` plies of
     every row cost on average; the loss is ``train``'s (a fast ply's policy target is all zero: only its value counts)"""
     from selfplay.search_selfplay import AsyncSearchSelfPlay
 
     if unsupported:
-        raise ValueError("per-ply budgets do not combine with leaves or gumbel yet")
+        raise ValueError("per-ply budgets do not combine with gumbel yet")
+    if leaves != 1 and reuse:
+        raise ValueError("per-ply budgets with leaves do not combine with reuse yet")
     dev = next(net.parameters()).device
     C = m * n
     if noise == "wrapper":
-        evaluator = FreshRootNoise(evaluator)
+        evaluator = FreshRootNoise(evaluator, leaves=leaves)
     sp = AsyncSearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, fast_iterations=fast_iterations,
                              full_prob=full_prob, temp_plies=max(1, C // 3), capacity=2 * C, seed=seed, solver=solver,
-                             root_noise=(0.3, 0.25) if noise == "builtin" else None, keep_tree=reuse)
+                             root_noise=(0.3, 0.25) if noise == "builtin" else None, keep_tree=reuse, leaves=leaves)
     if noise == "wrapper":
         evaluator.fresh = lambda: sp.fresh
-    per_ply = full_prob * (iterations + 1) + (1 - full_prob) * (fast_iterations + 1)
+    # (evaluator calls per ply: ceil(B / L) + 1 for a budget of B)
+    per_ply = full_prob * (-(-iterations // leaves) + 1) + (1 - full_prob) * (-(-fast_iterations // leaves) + 1)
     calls = max(1, round((C if plies is None else plies) * per_ply))
     gen = torch.Generator(device=dev)
     gen.manual_seed(seed)

@@ -787,6 +787,50 @@ int mnk_search_selfplay_advance_keep(void* workspace, uint64_t* planes, uint32_t
                                      uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
                                      float noise_eps, int noise_fast, float* root_priors, int tree_iterations,
                                      int keep_nodes, int32_t* carried, void* stream);
+/* mnk_search_selfplay_advance_opts for rows that search with L = leaves slots per row and evaluator call (the lockstep
+ * player's mnk_puct_step_leaves / mnk_puct_step_solver inside the one launch).  Every argument but leaves and row_sims,
+ * and every rule not named here, is mnk_search_selfplay_advance_opts's.
+ *   workspace: that of mnk_puct_begin_leaves(.., iterations, leaves, ..), set up by it on the current roots.
+ *   batch layout: mnk_puct_step_leaves's -- slot j of row i is batch row i * L + j of leaf_obs [N*L][2][m][n], leaf_mask
+ *     [N*L][C], priors [N*L][C] and values [N*L].  root_priors stays [N][C] and fresh [N]: fresh[i] = 1 means "slot 0 of
+ *     row i is a root".
+ *   row_sims (u32 [N], in and out, required, caller-owned): the simulations row i's current ply has been offered.  Zero it
+ *     whenever mnk_puct_begin_leaves sets the workspace up.
+ *   1. backup: the row's pending slots are backed up in slot order by mnk_puct_step_leaves's rule (with solver != 0,
+ *      mnk_puct_step_solver's).  The noise and root_priors act on slot 0 when it is evaluation 0 (state 1, depth 0),
+ *      exactly as above, with the evaluator's row i * L.
+ *   2. budget: unchanged -- the Philox word of (seed, row id, p_i) decides between B = iterations and B = fast_iterations.
+ *   3. the ply ends iff row_sims[i] >= B or, with the solver, the root has a proof.
+ *      It ends by the rule above word for word: ring slot, the move from the (adjusted) counts, labels, stats, the reset,
+ *        p_i += 1, plies_max.  Then the row's tree is set up afresh on the position reached, as mnk_puct_begin_leaves
+ *        leaves it: slot 0 is the root, pending; slots 1 .. L-1 are void and show the root's view.  row_sims[i] = 0,
+ *        fresh[i] = 1.
+ *      It goes on with s = min(L, B - row_sims[i]): slots 0 .. s-1 select one after the other under virtual visits --
+ *        mnk_puct_step_leaves's selection, the slots that the walk makes void included -- and slots s .. L-1 are void.
+ *        row_sims[i] += s, fresh[i] = 0.  So a budget is met exactly, whatever B mod L is.
+ *      The counter, not n_root - 1: a slot that the walk makes void is a simulation the lockstep player loses as well, and
+ *        a row that counted visits would search longer than the lockstep player's.  With the counter a ply of budget B
+ *        takes exactly ceil(B / L) + 1 launches unless a proof ends it sooner.
+ *   4. the rows that report MNK_ERR_VISITS are those of mnk_search_selfplay_advance's step 4 (a selection that finds no
+ *      leaf: one whose slot 0 finds none); nothing of such a row changes, row_sims[i] stays, and all L batch rows of the
+ *      row show its root.
+ * So (a) with leaves = 1 the launch is mnk_search_selfplay_advance_opts, bit for bit, on every row that reports no error,
+ * and row_sims[i] = n_root - 1 whenever the launch reads it; (b) with full_threshold = 2^32 and rows that start together,
+ * iterations / L + 1 launches are one ply of the lockstep player with leaves = L (mnk_puct_begin_leaves, the steps,
+ * mnk_search_selfplay_step), with noise mnk_puct_root_noise at step = the ply, bit for bit.
+ * leaves in [1, MNK_PUCT_LEAVES_MAX]; iterations % leaves = 0 (the workspace's condition; fast_iterations is free in [1,
+ * iterations]); row_sims != NULL.  LDS and the kernel's shape are as above; the slots' paths stay in the workspace.  Every
+ * host check, those of mnk_search_selfplay_advance_opts included, runs before anything is enqueued; N = 0 returns MNK_OK
+ * after them. */
+int mnk_search_selfplay_advance_leaves(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                       int iterations, int fast_iterations, int leaves, uint64_t full_threshold,
+                                       const void* priors, int priors_dtype, const void* values, int values_dtype, float c,
+                                       int temp_plies, uint64_t seed, const uint64_t* seed_dev, int64_t env_id0,
+                                       uint64_t* row_plies, int64_t T, uint64_t* ring_planes, uint16_t* ring_visits,
+                                       int8_t* ring_z, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                       uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                       float noise_eps, int noise_fast, float* root_priors, uint32_t* row_sims,
+                                       void* stream);
 /* A minibatch of ring records: sample b is the flat id idx[b] = t*N + i (negative ids wrap, an id outside [0, T*N) sets
  * MNK_ERR_ACTION_RANGE as in mnk_gather_obs and gives zero planes, policy, value and weight) under symmetry s = sym[b]
  * (sym int8 [B] or NULL = the identity).  Output cell (r, c) reads source cell (r', c'): start from (r, c); if s & 4,

@@ -38,21 +38,6 @@ __device__ __forceinline__ int puct_row_planes(const MnkGeom& g, const void* obs
   return stones;
 }
 
-// slots 1 .. leaves - 1 of evaluation 0 are void: nothing pending, the root's view (pos) as batch rows i * leaves + j
-template <int NW, int CN>
-__device__ __forceinline__ void puct_row_void_slots(const MnkGeom& g, unsigned char* row, const MnkPuctLayout& L,
-                                                    const uint32_t* pos, int64_t i, int leaves, void* leaf_obs,
-                                                    int leaf_dtype, uint8_t* leaf_mask, int lane) {
-  for (int j = 1; j < leaves; ++j) {
-    if (lane == 0) {
-      uint32_t* ds = (uint32_t*)(row + L.xhdr) + 2 * (j - 1);
-      ds[0] = 0u;
-      ds[1] = 0u;
-    }
-    row_write_view<NW, CN>(g, pos, 0, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
-  }
-}
-
 // One wave per row: the row into bit planes (LDS, pos), the root node, the roots as the first leaves (slot 0 of `leaves`).
 template <int NW, int CN>
 __device__ __forceinline__ void puct_begin_row(const MnkGeom& g, const void* obs, int obs_dtype, int64_t i, int I, int leaves,

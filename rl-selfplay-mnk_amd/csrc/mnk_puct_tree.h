@@ -110,6 +110,21 @@ __device__ __forceinline__ void puct_row_fresh(unsigned char* row, const MnkPuct
   }
 }
 
+// slots 1 .. leaves - 1 of evaluation 0 are void: nothing pending, the root's view (pos) as batch rows i * leaves + j
+template <int NW, int CN>
+__device__ __forceinline__ void puct_row_void_slots(const MnkGeom& g, unsigned char* row, const MnkPuctLayout& L,
+                                                    const uint32_t* pos, int64_t i, int leaves, void* leaf_obs,
+                                                    int leaf_dtype, uint8_t* leaf_mask, int lane) {
+  for (int j = 1; j < leaves; ++j) {
+    if (lane == 0) {
+      uint32_t* ds = (uint32_t*)(row + L.xhdr) + 2 * (j - 1);
+      ds[0] = 0u;
+      ds[1] = 0u;
+    }
+    row_write_view<NW, CN>(g, pos, 0, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
+  }
+}
+
 // The backup of one pending evaluation (state bit 0 set): batch row b of priors / values, the leaf's planes in pos (LDS).
 // SOLVER: the leaf's term is its proof (3: a proven loss of its mover, +1 for its side to move), and a proven leaf's
 // backup ends with the proofs of its path, leaf side first: one scan of a node's child row per level (the selection's

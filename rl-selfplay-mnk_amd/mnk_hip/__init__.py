@@ -151,6 +151,11 @@ SIGNATURES = {
     "mnk_search_selfplay_advance_keep": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i, _u64, _vp,
                                          _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i,
                                          _vp, _i, _i, _vp, _vp],
+    # mnk_search_selfplay_advance_opts's arguments with leaves behind the fast iterations and row sims (u32 [N]) before the
+    # stream
+    "mnk_search_selfplay_advance_leaves": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i, _u64,
+                                           _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f,
+                                           _i, _vp, _vp, _vp],
     # ring planes, ring visits, ring z, T, N, m, n, idx, sym, B, obs, obs dtype, legal mask, policy, value, weight, err, stream
     "mnk_search_gather": [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],

@@ -36,7 +36,8 @@ row and ply, rows that play on as soon as their search is done.  It takes ``root
 its one launch (``mnk_search_selfplay_advance_opts``): the noise of a row's ply is a function of (seed, row id, the row's
 ply count), and a row whose root is proven plays at once instead of idling until the slowest row is done.  ``keep_tree=True`` is its
 ``reuse`` (``mnk_search_selfplay_advance_keep``): the launch that plays a row's ply carries the played move's subtree into
-the row's next search.
+the row's next search.  ``leaves=L`` is its ``leaves`` (``mnk_search_selfplay_advance_leaves``): L positions per row and
+evaluator call, a ply's budget counted in the simulations it has been offered, with ``root_noise`` and ``solver``.
 """
 from typing import Dict
 
@@ -207,14 +208,28 @@ class AsyncSearchSelfPlay:
     for after the evaluator's weights changed.  With the solver a carried root keeps the proof it had as a child and
     plays in the launch that renews it.
 
+    ``leaves=L`` is ``SearchSelfPlay``'s ``leaves``: every row shows the evaluator L positions per call (the rule:
+    include/mnk_hip.h, mnk_search_selfplay_advance_leaves), so a round is one evaluator call on ``num_envs * L`` rows --
+    slot j of row i is row ``i * L + j`` of ``leaf_obs`` / ``leaf_mask`` -- and one launch that backs a row's pending slots
+    up and selects up to L new leaves under virtual visits.  ``iterations`` must be a multiple of L; ``fast_iterations``
+    need not be: a ply of budget B is offered exactly B simulations in ``ceil(B / L) + 1`` rounds, the slots beyond the
+    budget staying void (they show the root and nothing is read for them).  ``row_sims`` (int32 ``[N]``) counts the
+    simulations every row's current ply has been offered -- the budget is held against it, not against the root's visits,
+    so that a slot the search itself leaves void counts as it does for the lockstep player.  ``fresh[i]`` then says that
+    slot 0 of row i -- batch row ``i * L`` -- is a root, and ``root_priors`` stays ``[N, C]``.  With every ply full the games
+    are those of ``SearchSelfPlay(leaves=L, ...)`` of the same seed, bit for bit, with ``root_noise`` too.  It takes
+    ``root_noise`` and ``solver``; with ``keep_tree`` it raises ``ValueError``.
+
     With neither option ``advance`` calls ``mnk_search_selfplay_advance``, as before; with ``root_noise`` or ``solver`` it
     calls ``mnk_search_selfplay_advance_opts``; with ``keep_tree`` it calls ``mnk_search_selfplay_advance_keep``, which
-    takes the other two.  No ``leaves`` or ``gumbel`` yet."""
+    takes the other two; with ``leaves > 1`` it calls ``mnk_search_selfplay_advance_leaves``, which takes ``root_noise``
+    and ``solver``.  No ``gumbel`` yet."""
 
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  fast_iterations: int = None, full_prob: float = 1.0, c: float = 1.25, temp_plies: int = None,
                  capacity: int = None, seed=None, leaf_dtype=torch.float32, device="cuda", root_noise=None,
-                 noise_on_fast: bool = False, solver: bool = False, keep_tree: bool = False, tree_nodes: int = None):
+                 noise_on_fast: bool = False, solver: bool = False, keep_tree: bool = False, tree_nodes: int = None,
+                 leaves: int = 1):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -228,11 +243,15 @@ class AsyncSearchSelfPlay:
         if capacity < C:
             raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
         self.keep_tree = bool(keep_tree)
-        # (the policy checks model / evaluator, iterations, c, leaf_dtype and tree_nodes -- its range, and that it comes
-        # with keep_tree; it lends its evaluator call, its key and its workspace and is never asked to act)
+        # (the policy checks model / evaluator, iterations, c, leaf_dtype, leaves -- its range, and that iterations is a
+        # multiple of it -- and tree_nodes -- its range, and that it comes with keep_tree; it lends its evaluator call, its
+        # key, its workspace and its leaf tensors, both sized for `leaves`, and is never asked to act)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
                                        temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=self.keep_tree,
-                                       tree_nodes=tree_nodes)
+                                       tree_nodes=tree_nodes, leaves=leaves)
+        self.leaves = self.policy.leaves
+        if self.leaves > 1 and self.keep_tree:
+            raise ValueError("keep_tree does not combine with leaves > 1 yet")
         self.iterations = self.policy.iterations
         self.tree_nodes = self.policy.tree_nodes  # (iterations + 1 without keep_tree)
         self.fast_iterations = self.iterations if fast_iterations is None else int(fast_iterations)
@@ -262,15 +281,24 @@ class AsyncSearchSelfPlay:
                             if self.root_noise is not None else None)
         # keep_tree: {nodes kept, the kept root's visit count} of every row's current search ({0, 0}: it began afresh)
         self.carried = torch.zeros((self.num_envs, 2), dtype=torch.int32, device=dev) if self.keep_tree else None
+        # leaves > 1: the simulations every row's current ply has been offered (the kernel's u32 words)
+        self.row_sims = torch.zeros(self.num_envs, dtype=torch.int32, device=dev) if self.leaves > 1 else None
         self._begin()
 
     def _begin(self) -> None:
-        """every row's search starts afresh on its current position (mnk_puct_begin): the roots are the next leaves"""
+        """every row's search starts afresh on its current position (mnk_puct_begin; with ``leaves > 1``,
+        mnk_puct_begin_leaves): the roots are the next leaves, in slot 0 of every row"""
         env = self.env
         env.observe_into(obs=self._roots, flip_side=(env._meta & 1).to(torch.int64))
-        mnk_hip.call("mnk_puct_begin", mnk_hip.ptr(self._roots), mnk_hip.OBS_F32, self.num_envs, self.m, self.n, self.k,
-                     self.tree_nodes - 1, mnk_hip.ptr(self.workspace), mnk_hip.ptr(self.leaf_obs), self.policy._leaf_code,
-                     mnk_hip.ptr(self.leaf_mask), mnk_hip.stream_ptr(env._dev))
+        if self.leaves > 1:
+            mnk_hip.call("mnk_puct_begin_leaves", mnk_hip.ptr(self._roots), mnk_hip.OBS_F32, self.num_envs, self.m, self.n,
+                         self.k, self.iterations, self.leaves, mnk_hip.ptr(self.workspace), mnk_hip.ptr(self.leaf_obs),
+                         self.policy._leaf_code, mnk_hip.ptr(self.leaf_mask), mnk_hip.stream_ptr(env._dev))
+            self.row_sims.zero_()
+        else:
+            mnk_hip.call("mnk_puct_begin", mnk_hip.ptr(self._roots), mnk_hip.OBS_F32, self.num_envs, self.m, self.n,
+                         self.k, self.tree_nodes - 1, mnk_hip.ptr(self.workspace), mnk_hip.ptr(self.leaf_obs),
+                         self.policy._leaf_code, mnk_hip.ptr(self.leaf_mask), mnk_hip.stream_ptr(env._dev))
         self.fresh.fill_(1)
         if self.carried is not None:
             self.carried.zero_()
@@ -286,15 +314,21 @@ class AsyncSearchSelfPlay:
         env, buf, N, C = self.env, self.buffer, self.num_envs, self.m * self.n
         stream = mnk_hip.stream_ptr(env._dev)
         for _ in range(int(rounds)):
-            priors, pcode, values, vcode = self.policy._evaluate(self.leaf_obs, self.leaf_mask, N, C)
+            priors, pcode, values, vcode = self.policy._evaluate(self.leaf_obs, self.leaf_mask, N * self.leaves, C)
             seed, seed_dev, _, _, env_id0, _ = self.sampler.block()
-            args = (mnk_hip.ptr(self.workspace), mnk_hip.ptr(env._planes), mnk_hip.ptr(env._meta), N, self.m, self.n,
-                    self.k, self.iterations, self.fast_iterations, self.full_threshold, mnk_hip.ptr(priors), pcode,
+            head = (mnk_hip.ptr(self.workspace), mnk_hip.ptr(env._planes), mnk_hip.ptr(env._meta), N, self.m, self.n,
+                    self.k, self.iterations, self.fast_iterations)
+            tail = (self.full_threshold, mnk_hip.ptr(priors), pcode,
                     mnk_hip.ptr(values), vcode, self.policy.c, self.temp_plies, seed, seed_dev, env_id0,
                     mnk_hip.ptr(self.row_plies), buf.capacity, mnk_hip.ptr(buf.planes), mnk_hip.ptr(buf.visits),
                     mnk_hip.ptr(buf.z), mnk_hip.ptr(self.leaf_obs), self.policy._leaf_code, mnk_hip.ptr(self.leaf_mask),
                     mnk_hip.ptr(self.fresh), mnk_hip.ptr(buf.plies), mnk_hip.ptr(self.stats), mnk_hip.ptr(env._err))
-            if self.keep_tree:
+            args = head + tail
+            if self.leaves > 1:
+                alpha, eps = self.root_noise or (0.0, 0.0)
+                mnk_hip.call("mnk_search_selfplay_advance_leaves", *head, self.leaves, *tail, int(self.solver), alpha, eps,
+                             int(self.noise_on_fast), mnk_hip.ptr(self.root_priors), mnk_hip.ptr(self.row_sims), stream)
+            elif self.keep_tree:
                 alpha, eps = self.root_noise or (0.0, 0.0)
                 mnk_hip.call("mnk_search_selfplay_advance_keep", *args, int(self.solver), alpha, eps,
                              int(self.noise_on_fast), mnk_hip.ptr(self.root_priors), self.tree_nodes - 1,
