@@ -18,8 +18,10 @@ the noise is drawn inside the player's one launch, on the roots of the full plie
 is proven plays at once) and with ``--reuse`` (``AsyncSearchSelfPlay(keep_tree=True)``: a fast ply searches on top of the
 subtree the searches before it left; the trees are dropped after each training round here too) and with ``--leaves L``
 (``AsyncSearchSelfPlay(leaves=L)``: the network sees envs * L positions per call and a ply of budget B takes ceil(B / L) +
-1 calls; the wrapper's noise then goes to slot 0 of the fresh rows, batch row i * L); not ``--leaves`` with ``--reuse``, and
-not with ``--search gumbel``.
+1 calls; the wrapper's noise then goes to slot 0 of the fresh rows, batch row i * L); not ``--leaves`` with ``--reuse``.
+They combine with ``--search gumbel`` too (``AsyncSearchSelfPlay(gumbel=m)``: the Gumbel draw is made inside the player's one
+launch, a fast ply plays a sample of the improved policy of its small search, and a full ply records that policy; no root
+noise, as in the lockstep run).
 
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 [--reuse] [--solver]
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --search gumbel --iterations 16
@@ -27,6 +29,7 @@ not with ``--search gumbel``.
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25 --noise builtin --solver
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 8 --full-prob 0.25 --reuse
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 6 --full-prob 0.25 --leaves 4 --noise builtin --solver
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --search gumbel --iterations 16 --fast-iterations 4 --full-prob 0.25
 """
 import argparse
 import os
@@ -140,7 +143,8 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
         raise ValueError("fast_iterations and full_prob go together")
     if fast_iterations is not None:
         return _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies,
-                            updates, batch, seed, noise, solver, reuse, leaves, search != "puct", log)
+                            updates, batch, seed, noise, solver, reuse, leaves,
+                            considered if search == "gumbel" else None, log)
     if noise == "wrapper":
         evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
@@ -174,13 +178,12 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
 
 
 def _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies, updates, batch,
-                 seed, noise, solver, reuse, leaves, unsupported, log):
+                 seed, noise, solver, reuse, leaves, gumbel, log):
     """``train`` through ``AsyncSearchSelfPlay``: a training round follows as many evaluator calls as ``plies`` plies of
-    every row cost on average; the loss is ``train``'s (a fast ply's policy target is all zero: only its value counts)"""
+    every row cost on average; the loss is ``train``'s (a fast ply's policy target is all zero: only its value counts).
+    ``gumbel``: None, or the moves a Gumbel root considers (``train`` has turned the noise off then)"""
     from selfplay.search_selfplay import AsyncSearchSelfPlay
 
-    if unsupported:
-        raise ValueError("per-ply budgets do not combine with gumbel yet")
     if leaves != 1 and reuse:
         raise ValueError("per-ply budgets with leaves do not combine with reuse yet")
     dev = next(net.parameters()).device
@@ -189,7 +192,8 @@ def _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations
         evaluator = FreshRootNoise(evaluator, leaves=leaves)
     sp = AsyncSearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, fast_iterations=fast_iterations,
                              full_prob=full_prob, temp_plies=max(1, C // 3), capacity=2 * C, seed=seed, solver=solver,
-                             root_noise=(0.3, 0.25) if noise == "builtin" else None, keep_tree=reuse, leaves=leaves)
+                             root_noise=(0.3, 0.25) if noise == "builtin" else None, keep_tree=reuse, leaves=leaves,
+                             gumbel=gumbel)
     if noise == "wrapper":
         evaluator.fresh = lambda: sp.fresh
     # (evaluator calls per ply: ceil(B / L) + 1 for a budget of B)

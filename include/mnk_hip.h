@@ -831,6 +831,57 @@ int mnk_search_selfplay_advance_leaves(void* workspace, uint64_t* planes, uint32
                                        uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
                                        float noise_eps, int noise_fast, float* root_priors, uint32_t* row_sims,
                                        void* stream);
+/* mnk_search_selfplay_advance for rows whose root is a GUMBEL ROOT (the lockstep player's mnk_puct_gumbel_root,
+ * mnk_puct_step_gumbel and mnk_search_selfplay_step_moves inside the one launch).  The arguments are those of
+ * mnk_search_selfplay_advance up to err without temp_plies -- the Gumbel draw is the exploration at every ply -- and every
+ * rule not named here is mnk_search_selfplay_advance's.  A round stays one evaluator call and one launch.
+ *   considered, c_visit, c_scale, gumbel_scale: those of mnk_puct_step_gumbel / mnk_puct_gumbel_root, with their ranges.
+ *   table_full (u16 [considered + 1][iterations]) and table_fast (u16 [considered + 1][fast_iterations]): what
+ *     mnk_puct_gumbel_schedule fills for the two budgets; they may be the same pointer when the budgets are equal.
+ *   gscore (f32 [N][C]) and vroot (f32 [N]): caller-owned, the rows' state between launches.
+ *   workspace: that of mnk_puct_begin with iterations, one leaf per row -- the workspace mnk_puct_begin_leaves(leaves = 1)
+ *     sets up.
+ * Row i of a launch, p_i its ply count:
+ *   1. backup: mnk_puct_step's rule from batch row i, bit for bit.  When the pending leaf is evaluation 0 of a fresh tree
+ *      (state 1, depth 0), the same launch writes gscore row i and vroot[i] by mnk_puct_gumbel_root's rule word for word
+ *      (f64 arithmetic with the full-precision logarithm, the clamp at 2^-126, the Philox layout over C4, the product
+ *      rounded, then the sum, then the one rounding to f32 -- fl32(gumbel_scale * g_a + l_a) -- and -inf on occupied
+ *      cells) with step =
+ *      p_i, row id = env_id0 + i, seed [or *seed_dev]; the free cells are those of the root's planes, the priors and the
+ *      value the evaluator's batch row i.  So the Gumbel draw of a ply is a function of (seed, row id, p_i) alone, as its
+ *      budget is.  The evaluator's tensors are never written; gscore row i and vroot[i] are written in no other launch.
+ *      Precondition (the host cannot see row_plies): p_i < 2^56 / C4 - 1, mnk_puct_gumbel_root's bound on step.
+ *   2. budget: unchanged -- the MNK_STREAM_BUDGET word of (seed, row id, p_i) decides between B = iterations with
+ *      table_full (row stride iterations) and B = fast_iterations with table_fast (row stride fast_iterations).
+ *   3. it = n_root - 1.
+ *      it < B: mnk_puct_step_gumbel's selection -- F = the root's free cells, v* = table_B[min(considered, F)][it], the
+ *        root's cell of maximal key among those with n_a = v* (all free cells if there is none), ties to the lowest cell,
+ *        and below the root mnk_puct_step's walk; fresh[i] = 0.
+ *      it >= B: the ply ends in this launch; fresh[i] = 1.  The move is mnk_puct_step_gumbel's: the free cell of maximal
+ *        key among those of the most visits, ties to the lowest cell.  Ring slot (p_i mod T, i) takes the planes before
+ *        the ply and z unknown.  On a FULL ply the visits are the improved policy of mnk_puct_step_gumbel (from vroot[i]
+ *        and the root's stored priors) quantised by mnk_search_selfplay_step_moves's rule, min(65535, rint(fl32(policy_a *
+ *        65535))) on free cells; on a fast ply they are all zero and no policy is computed.  No MNK_STREAM_SELFPLAY word
+ *        is used.  Then mnk_search_selfplay_advance's end of a ply: the ply, the outcome labels, stats, the reset,
+ *        p_i += 1, plies_max, and a fresh tree on the position reached, whose root is the next leaf.
+ *   4. the rows that report MNK_ERR_VISITS are mnk_search_selfplay_advance's: a root without a legal cell; a selection
+ *      that finds no leaf; a spent row whose move is not a free cell of planes (a workspace that is not this position's).
+ *      Nothing of such a row changes and it shows its root again.
+ * So with full_threshold = 2^32 and rows that start together, iterations + 1 launches are one ply of the lockstep Gumbel
+ * player -- mnk_puct_begin_leaves(leaves = 1), mnk_puct_gumbel_root at step = the ply, iterations + 1 mnk_puct_step_gumbel,
+ * mnk_search_selfplay_step_moves -- bit for bit, with two launches per ply fewer and the prep launch saved.
+ * Every host check -- those of mnk_search_selfplay_advance, the ranges of considered, c_visit, c_scale and gumbel_scale,
+ * non-NULL tables, gscore and vroot, C <= 1024 -- runs before anything is enqueued; N = 0 returns MNK_OK after them.  One
+ * wave per row; every id read from the workspace is clamped to the row. */
+int mnk_search_selfplay_advance_gumbel(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                       int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                       int priors_dtype, const void* values, int values_dtype, float c, uint64_t seed,
+                                       const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies, int64_t T,
+                                       uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs,
+                                       int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh, uint64_t* plies_max,
+                                       int64_t* stats, int32_t* err, int considered, float c_visit, float c_scale,
+                                       float gumbel_scale, const uint16_t* table_full, const uint16_t* table_fast,
+                                       float* gscore, float* vroot, void* stream);
 /* A minibatch of ring records: sample b is the flat id idx[b] = t*N + i (negative ids wrap, an id outside [0, T*N) sets
  * MNK_ERR_ACTION_RANGE as in mnk_gather_obs and gives zero planes, policy, value and weight) under symmetry s = sym[b]
  * (sym int8 [B] or NULL = the identity).  Output cell (r, c) reads source cell (r', c'): start from (r, c); if s & 4,

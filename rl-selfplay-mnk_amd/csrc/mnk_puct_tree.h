@@ -241,9 +241,11 @@ __device__ __forceinline__ int puct_root_keep(int C, const MnkPuctNode* node, co
   return keep;
 }
 
-// ------------------------------------------------------------------ the Gumbel root (k_puct_step_gumbel only)
+// ------------------------------------------------------------------ the Gumbel root
+// (k_puct_step_gumbel and k_search_selfplay_advance_gumbel)
 // What the root of row i reads besides the tree: its row of gscore (mnk_puct_gumbel_root), the table of considered visits
-// (mnk_puct_gumbel_schedule, [considered + 1][I]) and the constants of sigma.
+// (mnk_puct_gumbel_schedule, [considered + 1][I]; the I that puct_gumbel_pick and puct_walk are given is its row stride)
+// and the constants of sigma.
 struct MnkPuctGumbel {
   const float* gs;
   const uint16_t* table;

@@ -156,6 +156,12 @@ SIGNATURES = {
     "mnk_search_selfplay_advance_leaves": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i, _u64,
                                            _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f,
                                            _i, _vp, _vp, _vp],
+    # mnk_search_selfplay_advance's arguments up to err without temp_plies, then considered, c_visit, c_scale, gumbel scale,
+    # table for the full budget (u16 [considered + 1][iterations]), table for the fast one, gscore (f32 [N][C]), vroot (f32
+    # [N]), stream
+    "mnk_search_selfplay_advance_gumbel": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _u64, _vp,
+                                           _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _f,
+                                           _vp, _vp, _vp, _vp, _vp],
     # ring planes, ring visits, ring z, T, N, m, n, idx, sym, B, obs, obs dtype, legal mask, policy, value, weight, err, stream
     "mnk_search_gather": [_vp, _vp, _vp, _i64, _i64, _i, _i, _vp, _vp, _i64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "mnk_rollout_random": [_vp, _vp, _i64, _i, _i, _i, _i, _u64, _u64, _i64, _vp, _vp, _vp, _vp, _i, _vp],

@@ -38,6 +38,8 @@ ply count), and a row whose root is proven plays at once instead of idling until
 ``reuse`` (``mnk_search_selfplay_advance_keep``): the launch that plays a row's ply carries the played move's subtree into
 the row's next search.  ``leaves=L`` is its ``leaves`` (``mnk_search_selfplay_advance_leaves``): L positions per row and
 evaluator call, a ply's budget counted in the simulations it has been offered, with ``root_noise`` and ``solver``.
+``gumbel=m`` is its ``gumbel`` (``mnk_search_selfplay_advance_gumbel``): the Gumbel draw of a row's ply is made inside the
+launch that backs its root up, and a fast ply plays a sample of the improved policy of its small search.
 """
 from typing import Dict
 
@@ -220,16 +222,31 @@ class AsyncSearchSelfPlay:
     are those of ``SearchSelfPlay(leaves=L, ...)`` of the same seed, bit for bit, with ``root_noise`` too.  It takes
     ``root_noise`` and ``solver``; with ``keep_tree`` it raises ``ValueError``.
 
-    With neither option ``advance`` calls ``mnk_search_selfplay_advance``, as before; with ``root_noise`` or ``solver`` it
+    ``gumbel=m`` is ``SearchSelfPlay``'s ``gumbel``: every root is a Gumbel root (the rule: include/mnk_hip.h,
+    mnk_search_selfplay_advance_gumbel).  The launch that backs a fresh tree's root up draws the root's Gumbel variables
+    -- ``PUCTSearchPolicy(gumbel=m)``'s draw, keyed by (seed, row id, the row's ply count) -- into ``gscore`` (float32
+    ``[N, C]``) and keeps the root's value in ``vroot`` (float32 ``[N]``); the selections follow Sequential Halving with
+    the schedule of the ply's own budget (two tables, one for ``iterations`` and one for ``fast_iterations``, uploaded
+    once), and the launch that ends the ply plays the search's own move.  A full ply records the improved policy scaled
+    to 65 535, a fast ply zero visits as before -- but its move is still a sample of the improved policy of a
+    ``fast_iterations`` search, which a visit-count search of that size cannot give.  ``gumbel_c=(c_visit, c_scale)`` and
+    ``gumbel_scale`` are ``PUCTSearchPolicy``'s.  ``temp_plies`` is accepted and not read: the Gumbel draw is the
+    exploration at every ply, as in the lockstep player.  With every ply full the games are those of
+    ``SearchSelfPlay(gumbel=m)`` of the same seed, bit for bit.  With ``root_noise``, ``solver``, ``keep_tree`` or
+    ``leaves > 1`` it raises ``ValueError``, the lockstep player's rule.  ``state_dict`` needs nothing new for it: the
+    trees are not state, and the ``gscore`` that the search restarted by ``load_state_dict`` redraws is a function of
+    (seed, row id, ply count), so it is the one the interrupted search had.
+
+    With no option ``advance`` calls ``mnk_search_selfplay_advance``, as before; with ``root_noise`` or ``solver`` it
     calls ``mnk_search_selfplay_advance_opts``; with ``keep_tree`` it calls ``mnk_search_selfplay_advance_keep``, which
     takes the other two; with ``leaves > 1`` it calls ``mnk_search_selfplay_advance_leaves``, which takes ``root_noise``
-    and ``solver``.  No ``gumbel`` yet."""
+    and ``solver``; with ``gumbel`` it calls ``mnk_search_selfplay_advance_gumbel``."""
 
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  fast_iterations: int = None, full_prob: float = 1.0, c: float = 1.25, temp_plies: int = None,
                  capacity: int = None, seed=None, leaf_dtype=torch.float32, device="cuda", root_noise=None,
                  noise_on_fast: bool = False, solver: bool = False, keep_tree: bool = False, tree_nodes: int = None,
-                 leaves: int = 1):
+                 leaves: int = 1, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -266,11 +283,29 @@ class AsyncSearchSelfPlay:
         if self.noise_on_fast and self.root_noise is None:
             raise ValueError("noise_on_fast=True needs root_noise=(alpha, eps)")
         self.solver = bool(solver)
+        self.gumbel, self.gumbel_c, self.gumbel_scale = PUCTSearchPolicy._checked_gumbel(gumbel, gumbel_c, gumbel_scale)
+        if self.gumbel is not None:
+            for name, on in (("keep_tree=True", self.keep_tree), ("leaves > 1", self.leaves > 1),
+                             ("solver=True", self.solver), ("root_noise", self.root_noise is not None)):
+                if on:
+                    raise ValueError(f"gumbel does not combine with {name} yet")
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
         self.sampler = self.policy._sampler
         self.env.reset()
+        # gumbel: every row's root scores and root value (written by the launch that backs its root's evaluation up), and
+        # the schedules of considered visits of the two budgets, uploaded once
+        self.gscore = self.vroot = self._table_full = self._table_fast = None
+        if self.gumbel is not None:
+            self.gscore = torch.zeros((self.num_envs, C), dtype=torch.float32, device=dev)
+            self.vroot = torch.zeros(self.num_envs, dtype=torch.float32, device=dev)
+            table = mnk_hip.puct_gumbel_schedule(self.gumbel, self.iterations)
+            self._table_full = torch.from_numpy(table.view("int16")).to(dev)
+            self._table_fast = self._table_full
+            if self.fast_iterations != self.iterations:
+                table = mnk_hip.puct_gumbel_schedule(self.gumbel, self.fast_iterations)
+                self._table_fast = torch.from_numpy(table.view("int16")).to(dev)
         self.row_plies = torch.zeros(self.num_envs, dtype=torch.int64, device=dev)
         self.fresh = torch.zeros(self.num_envs, dtype=torch.uint8, device=dev)
         self.stats = torch.zeros((mnk_hip.STATS_REPLICAS, mnk_hip.STATS_STRIDE), dtype=torch.int64, device=dev)
@@ -324,7 +359,11 @@ class AsyncSearchSelfPlay:
                     mnk_hip.ptr(buf.z), mnk_hip.ptr(self.leaf_obs), self.policy._leaf_code, mnk_hip.ptr(self.leaf_mask),
                     mnk_hip.ptr(self.fresh), mnk_hip.ptr(buf.plies), mnk_hip.ptr(self.stats), mnk_hip.ptr(env._err))
             args = head + tail
-            if self.leaves > 1:
+            if self.gumbel is not None:  # (no temp_plies: argument 15 of the plain entry point)
+                mnk_hip.call("mnk_search_selfplay_advance_gumbel", *args[:15], *args[16:], self.gumbel, *self.gumbel_c,
+                             self.gumbel_scale, mnk_hip.ptr(self._table_full), mnk_hip.ptr(self._table_fast),
+                             mnk_hip.ptr(self.gscore), mnk_hip.ptr(self.vroot), stream)
+            elif self.leaves > 1:
                 alpha, eps = self.root_noise or (0.0, 0.0)
                 mnk_hip.call("mnk_search_selfplay_advance_leaves", *head, self.leaves, *tail, int(self.solver), alpha, eps,
                              int(self.noise_on_fast), mnk_hip.ptr(self.root_priors), mnk_hip.ptr(self.row_sims), stream)
