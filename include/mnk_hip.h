@@ -541,6 +541,35 @@ int mnk_puct_step_solver(void* workspace, int64_t N, int m, int n, int k, int it
                          uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                          int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                          int32_t* visits, float* root_value, int8_t* proof, void* stream);
+/* mnk_puct_step_leaves (solver = 0) or mnk_puct_step_solver (solver = 1) with FIRST-PLAY URGENCY (optional: a search
+ * that never calls it is the search above).  Above, a free cell without a visit scores with q = 0: with values in [-1, 1],
+ * "an untried move is a draw", so a node whose visited moves all look lost tries every other cell once before it returns
+ * to one, and a node whose first move looks won never tries a second.  Here such a cell is valued at the node's own mean
+ * value, less a reduction that grows with the prior mass already visited (KataGo's and Leela's rule).  The workspace is
+ * that of mnk_puct_begin_leaves / mnk_puct_rebase_leaves, leaves in [1, MNK_PUCT_LEAVES_MAX]; every step of an act is this
+ * entry point.  fpu_root is the reduction at the root (node 0), fpu the one below it: f32, finite, >= 0.
+ *   At an evaluated node v, with n'_a, w'_a the child's counts through cell a under the round's virtual visits as above:
+ *     q_v  = fdiv(-w_v, (float)n_v), from the stored n_v >= 1 and w_v, WITHOUT virtual visits: the node's mean value for
+ *            its own side to move (root_value's formula);
+ *     t_a  = (uint64_t)(min(max(P_v[a], 0), 1) * 2^32), truncated, for every free cell a of v with n'_a > 0 (every such
+ *            cell, the children proven LOSS included), and T = the sum of the t_a: integers, so the order of the sum
+ *            cannot matter (a prior of 1 or more is 2^32; T < 2^43);
+ *     mass = fl32(sqrt((double)T * 2^-32)), the f64 square root correctly rounded, then rounded to f32;
+ *     r    = fpu_root at v = node 0, fpu elsewhere;
+ *     a free cell with n'_a = 0 scores with  q = fmax(fsub(q_v, fmul(r, mass)), -1);
+ *     a free cell with n'_a > 0 keeps        q = fdiv(w'_a, (float)n'_a).
+ *   Every operation correctly rounded, no contraction.  Everything else is unchanged: s, the tie rule, the solver's
+ *   classes of candidates, where a walk ends, the backup, the move, visits, root_value, the proofs.  fpu = fpu_root = 0 is
+ *   NOT the search above: an untried move then scores with q_v, not with 0.
+ * proof may be NULL, and is not written, when solver = 0.  solver outside {0, 1}, leaves outside [1,
+ * MNK_PUCT_LEAVES_MAX], a NaN, infinite or negative fpu or fpu_root are MNK_EINVAL; every host check runs before anything
+ * is enqueued; N = 0 returns MNK_OK after them. */
+int mnk_puct_step_fpu(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                      int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                      uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                      int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                      int32_t* visits, float* root_value, int8_t* proof, int solver, float fpu, float fpu_root,
+                      void* stream);
 /* The search above with a GUMBEL ROOT ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022;
  * optional: a search that never calls these is the search above).  One Gumbel variable per root move, the budget spent on
  * the `considered` best moves by Sequential Halving, the survivor played -- an exact sample from the improved policy --
@@ -787,6 +816,30 @@ int mnk_search_selfplay_advance_keep(void* workspace, uint64_t* planes, uint32_t
                                      uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
                                      float noise_eps, int noise_fast, float* root_priors, int tree_iterations,
                                      int keep_nodes, int32_t* carried, void* stream);
+/* mnk_search_selfplay_advance_opts and mnk_search_selfplay_advance_keep with FIRST-PLAY URGENCY in the selection (the
+ * rule: mnk_puct_step_fpu at leaves = 1, with or without the solver): their arguments, then fpu and fpu_root before the
+ * stream, and nothing else differs -- the backup, the budget, the end of a ply, the noise, the carry.  With full_threshold
+ * = 2^32 and rows that start together the launches are the lockstep player's with mnk_puct_step_fpu in the place of its
+ * step, bit for bit, with the exceptions their siblings state for the solver.  fpu, fpu_root: finite, >= 0 (else
+ * MNK_EINVAL); every host check runs before anything is enqueued; N = 0 returns MNK_OK after them. */
+int mnk_search_selfplay_advance_opts_fpu(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                         int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                         int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                         uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
+                                         int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
+                                         void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                         uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                         float noise_eps, int noise_fast, float* root_priors, float fpu, float fpu_root,
+                                         void* stream);
+int mnk_search_selfplay_advance_keep_fpu(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                         int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                         int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                         uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
+                                         int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
+                                         void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                         uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                         float noise_eps, int noise_fast, float* root_priors, int tree_iterations,
+                                         int keep_nodes, int32_t* carried, float fpu, float fpu_root, void* stream);
 /* mnk_search_selfplay_advance_opts for rows that search with L = leaves slots per row and evaluator call (the lockstep
  * player's mnk_puct_step_leaves / mnk_puct_step_solver inside the one launch).  Every argument but leaves and row_sims,
  * and every rule not named here, is mnk_search_selfplay_advance_opts's.

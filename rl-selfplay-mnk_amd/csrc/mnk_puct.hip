@@ -617,6 +617,106 @@ k_puct_step_solver(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, c
   if (lane == 0) hdr[0] = (uint32_t)nodes;
 }
 
+// ------------------------------------------------------------------ a round with first-play urgency
+// k_puct_step_leaves (SOLVER: k_puct_step_solver) with the first-play urgency of puct_walk compiled in: a free cell
+// without a visit scores from its parent's own mean value, less a reduction that grows with the prior mass already
+// visited, in the place of q = 0.  The backups, the move and the slots are those kernels'; proof is read with SOLVER
+// only.  The rule: include/mnk_hip.h, mnk_puct_step_fpu.
+template <int NW, int CN, int CK, bool SOLVER>
+__global__ void __launch_bounds__(256)
+k_puct_step_fpu(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, const void* priors, int priors_dtype,
+                const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
+                const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
+                void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits, float* root_value,
+                int8_t* proof, float fpu, float fpu_root) {
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
+  if (i >= N) return;
+  const int C = g.C, NWg = g.NW;
+  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, leaves);
+  unsigned char* row = ws + i * L.row;
+  uint32_t* hdr = (uint32_t*)row;
+  const uint32_t* root = (const uint32_t*)(row + L.root);
+  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
+  float* prior = (float*)(row + L.prior);
+  uint16_t* child = (uint16_t*)(row + L.child);
+  uint32_t* pos = lds_pos[wave];
+  // slot j's {depth, state}, leaf planes and path (slot 0: the header's, `leaf`, `path`)
+  auto slot_ds = [&](int j) { return j ? (uint32_t*)(row + L.xhdr) + 2 * (j - 1) : hdr + 1; };
+  auto slot_leaf = [&](int j) { return (uint32_t*)(row + (j ? L.xleaf + 8 * (int64_t)NWg * (j - 1) : L.leaf)); };
+  auto slot_path = [&](int j) { return (uint16_t*)(row + (j ? L.xpath + L.pstride * (j - 1) : L.path)); };
+  // (clamped: a workspace that mnk_puct_begin_leaves did not set up cannot send a store outside the row)
+  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
+  const bool live = hdr[3] != 0u;
+
+  // ---- the backups of the pending evaluations, in slot order
+  for (int j = 0; j < leaves; ++j) {
+    const uint32_t* ds = slot_ds(j);
+    const int depth = (int)min(ds[0], (uint32_t)I);
+    const uint32_t state = ds[1];
+    if (!(state & 1u)) continue;
+    const uint32_t* leafp = slot_leaf(j);
+    for (int q = lane; q < 2 * NW; q += 64) {
+      const int pl = q >= NW, w = q - (pl ? NW : 0);
+      pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
+    }
+    row_wave_sync();
+    puct_backup<NW, CN, SOLVER>(g, pos, slot_path(j), node, prior, child, nodes, depth, state, priors, priors_dtype, values,
+                                values_dtype, i * leaves + j, lane);
+  }
+
+  if (last) {
+    puct_move<SOLVER>(C, node, child, nodes, live, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, i,
+                      actions, visits, root_value, lane, proof);
+    return;
+  }
+
+  // ---- the selections
+  const int nodes0 = nodes;
+  const uint16_t* epath = slot_path(min(lane, leaves - 1));  // lane l < leaves: slot l's path
+  int edepth = 0;                                            // and, once it has selected, its leaf's depth
+  uint32_t active = 0u;                                      // the slots of this round that have a leaf
+  bool open = live;                                          // no slot was void yet
+  if constexpr (SOLVER)
+    if (MNK_PUCT_PROOF(node[0].info)) open = false;  // a proven root: nothing left to search
+  for (int j = 0; j < leaves; ++j) {
+    int d = 0;
+    uint32_t nstate = 0u;
+    uint16_t* path = slot_path(j);
+    MnkEnv<NW> e;
+    if (open && nodes <= I) {
+      puct_env_root<NW>(e, root, NWg);
+      nstate = puct_walk<NW, CN, CK, true, SOLVER, false, true>(g, e, I, c, node, prior, child, path, nodes, d, lane, nodes0,
+                                                                active, epath, edepth, nullptr, fpu, fpu_root);
+    }
+    if (nstate) {
+      active |= 1u << j;
+      if (lane == j) edepth = d;
+    } else {
+      d = 0;
+      open = false;
+    }
+    if (lane == 0) {
+#pragma unroll
+      for (int w = 0; w < NW; ++w) {
+        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
+        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
+      }
+      path[0] = 0;
+      uint32_t* ds = slot_ds(j);
+      ds[0] = (uint32_t)d;
+      ds[1] = nstate;
+    }
+    row_wave_sync();
+    uint32_t* leafp = slot_leaf(j);
+    for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
+    row_write_view<NW, CN>(g, pos, d & 1, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
+    row_wave_sync();  // (the next slot's walk reads this one's node, child entry and path; its write-out reuses pos)
+  }
+  if (lane == 0) hdr[0] = (uint32_t)nodes;
+}
+
 // ------------------------------------------------------------------ a step whose root is a Gumbel root
 // k_puct_step (one leaf per row and evaluation, the same workspace) with the root's part of puct_walk replaced by
 // puct_gumbel_pick and puct_move by puct_move_gumbel; below the root the walk and the backup are k_puct_step's.  The
@@ -768,7 +868,8 @@ static int puct_step(void* workspace, int64_t N, int m, int n, int k, int iterat
                      int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
                      uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                      int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
-                     int32_t* visits, float* root_value, void* stream, bool solver = false, int8_t* proof = nullptr) {
+                     int32_t* visits, float* root_value, void* stream, bool solver = false, int8_t* proof = nullptr,
+                     bool with_fpu = false, float fpu = 0.0f, float fpu_root = 0.0f) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
@@ -779,9 +880,22 @@ static int puct_step(void* workspace, int64_t N, int m, int n, int k, int iterat
       (temperature != 0 && temperature != 1) || !puct_leaves_ok(iterations, leaves))
     return MNK_EINVAL;
   if (last ? !actions : (!leaf_obs || !leaf_mask || !mnk_obs_dtype_ok(leaf_dtype))) return MNK_EINVAL;
+  if (with_fpu && (!(fpu >= 0.0f && fpu <= 3.0e38f) || !(fpu_root >= 0.0f && fpu_root <= 3.0e38f))) return MNK_EINVAL;
   if (N == 0) return MNK_OK;
   const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
   hipStream_t s = (hipStream_t)stream;
+#define MNK_PUCT_STEP_FPU(SOLVER)                                                                                        \
+  MNK_DISPATCH(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_puct_step_fpu<NW, CN, CK, SOLVER>), grid, block, 0, s, g,         \
+                                     (unsigned char*)workspace, N, iterations, leaves, priors, priors_dtype, values,     \
+                                     values_dtype, c, last, temperature, seed, seed_dev, step, step_dev, env_id0,        \
+                                     deterministic, leaf_obs, leaf_dtype, leaf_mask, actions, visits, root_value, proof, \
+                                     fpu, fpu_root))
+  if (with_fpu) {
+    if (solver) MNK_PUCT_STEP_FPU(true);
+    else MNK_PUCT_STEP_FPU(false);
+    return mnk_launch_status("puct_step_fpu");
+  }
+#undef MNK_PUCT_STEP_FPU
   if (solver)
     MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step_solver), grid, block, 0, s, g, (unsigned char*)workspace, N,
                                        iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
@@ -860,6 +974,18 @@ int mnk_puct_step_solver(void* workspace, int64_t N, int m, int n, int k, int it
   return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
                    temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
                    actions, visits, root_value, stream, true, proof);
+}
+
+int mnk_puct_step_fpu(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                      int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                      uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                      int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                      int32_t* visits, float* root_value, int8_t* proof, int solver, float fpu, float fpu_root,
+                      void* stream) {
+  if (!leaves || (solver != 0 && solver != 1)) return MNK_EINVAL;
+  return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
+                   temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
+                   actions, visits, root_value, stream, solver != 0, solver ? proof : nullptr, true, fpu, fpu_root);
 }
 
 int mnk_puct_step_gumbel(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,

@@ -317,6 +317,24 @@ __device__ __forceinline__ int puct_gumbel_pick(int C, int I, const MnkPuctNode*
   return __builtin_amdgcn_readfirstlane(ba != 0x7fffffff ? ba : aa);
 }
 
+// ------------------------------------------------------------------ first-play urgency
+// A visited cell's share of the visited prior mass: the prior clipped to [0, 1] as a 32-bit fixed-point number (truncated;
+// 2^32 for a prior of 1 or more).  Integers, so that the order of the sum over the lanes cannot matter.
+__device__ __forceinline__ uint64_t puct_fpu_term(float p) {
+  const float pc = fminf(fmaxf(p, 0.0f), 1.0f);
+  return pc >= 1.0f ? 1ull << 32 : (uint64_t)(uint32_t)__fmul_rn(pc, 0x1p32f);  // (pc < 1: the product is exact, < 2^32)
+}
+// The q of node k's free cells without a visit from the lanes' partial sums T of puct_fpu_term (reduced here; the result
+// is the same in every lane): mass = fl32(sqrt(T * 2^-32)), the f64 square root correctly rounded (T < 2^43: the
+// conversion and the scaling are exact), q_v = -w / n from the stored record, q = max(q_v - r * mass, -1).
+__device__ __forceinline__ float puct_fpu_q(uint64_t T, const MnkPuctNode& k, float r) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) T += (uint64_t)__shfl_xor((unsigned long long)T, off, 64);
+  const float mass = (float)__dsqrt_rn(__dmul_rn((double)T, 0x1p-32));
+  const float qv = __fdiv_rn(-k.w, (float)k.n);
+  return fmaxf(__fsub_rn(qv, __fmul_rn(r, mass)), -1.0f);
+}
+
 // One walk from the root (e = the root's position on entry, the leaf's on return; wave-uniform): the new pending state
 // (0: no leaf), the leaf's depth in d, its path in path[1 .. d].  A new leaf becomes node `nodes`.
 // VL: the walk of a slot under the virtual visits of the round's earlier slots.  vl(x) is counted from their stored paths
@@ -329,12 +347,16 @@ __device__ __forceinline__ int puct_gumbel_pick(int C, int I, const MnkPuctNode*
 // in a child with a proof as it ends in a terminal one; the new pending state carries the proof in the term's bits.
 // GUMBEL: at the root the cell is puct_gumbel_pick's (gm: the row's Gumbel inputs); from the chosen child on, the walk
 // below.
-template <int NW, int CN, int CK, bool VL, bool SOLVER = false, bool GUMBEL = false>
+// FPU: first-play urgency (the rule: include/mnk_hip.h, mnk_puct_step_fpu).  A free cell without a visit scores with
+// q = max(q_v - r * mass, -1) in the place of 0, r = fpu_root at the root and fpu below it: puct_fpu_q, one more pass over
+// the node's child row and priors before the scoring loop, in its access shape.
+template <int NW, int CN, int CK, bool VL, bool SOLVER = false, bool GUMBEL = false, bool FPU = false>
 __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, int I, float c, MnkPuctNode* node,
                                               const float* prior, uint16_t* child, uint16_t* path, int& nodes, int& d,
                                               int lane, int nodes0 = 0, uint32_t share = 0u,
                                               const uint16_t* epath = nullptr, int edepth = 0,
-                                              const MnkPuctGumbel* gm = nullptr) {
+                                              const MnkPuctGumbel* gm = nullptr, float fpu = 0.0f,
+                                              float fpu_root = 0.0f) {
   const int C = g.C;
   int v = 0;
   for (;;) {
@@ -363,6 +385,22 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
         picked = true;
       }
     }
+    [[maybe_unused]] float qu = 0.0f;  // FPU: the q of a free cell without a visit, the same in every lane
+    if constexpr (FPU) {
+      uint64_t T = 0ull;
+      for (int a = lane; a < C; a += 64) {
+        const uint32_t ch = cl[a];
+        if (ch == MNK_PUCT_NONE || ch == 0u) continue;
+        const int kk = min((int)ch, nodes - 1);
+        uint32_t na = node[kk].n;
+        if (VL && share) {
+#pragma unroll
+          for (int l = 0; l < MNK_PUCT_LEAVES_MAX; ++l) na += nx[l] == (uint32_t)kk;
+        }
+        if (na) T += puct_fpu_term(pr[a]);
+      }
+      qu = puct_fpu_q(T, node[v], v == 0 ? fpu_root : fpu);
+    }
     if (!picked)  // (the loop keeps its indentation: below this line the scoring is the text it was)
     for (int a = lane; a < C; a += 64) {
       const uint32_t ch = cl[a];
@@ -384,7 +422,7 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
           wa = __fadd_rn(wa, -(float)vl);
         }
       }
-      const float q = na ? __fdiv_rn(wa, (float)na) : 0.0f;
+      const float q = na ? __fdiv_rn(wa, (float)na) : (FPU ? qu : 0.0f);
       const float s = __fadd_rn(q, __fdiv_rn(__fmul_rn(__fmul_rn(c, pr[a]), sq), (float)(1u + na)));
       if constexpr (SOLVER) {
         if (ba == 0x7fffffff || cls > bc || (cls == bc && s > best)) {

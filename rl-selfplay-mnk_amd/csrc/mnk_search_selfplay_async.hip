@@ -216,15 +216,19 @@ k_search_selfplay_advance(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32
 // shape: one wave per row, no workgroup barrier, every id clamped to the row.  SOLVER is a template flag (it changes
 // puct_walk's inner loop); the noise is a wave-uniform run-time branch that only a wave whose pending leaf is the root of
 // a fresh tree takes, once per ply.  nz.alpha = 0: no noise, and then the launch has no dynamic LDS.
-template <int NW, int CN, int CK, bool SOLVER>
-__global__ void __launch_bounds__(256)
-k_search_selfplay_advance_opts(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32_t* meta, int64_t N, int I,
+// The launch's row is a device function, search_selfplay_advance_opts_row, so that the kernel with first-play urgency
+// (FPU: puct_walk's, the rule: include/mnk_hip.h, mnk_puct_step_fpu) is the same text; k_search_selfplay_advance_opts
+// below is its FPU = false form behind the parameter list it always had.
+template <int NW, int CN, int CK, bool SOLVER, bool FPU>
+__device__ __forceinline__ void
+search_selfplay_advance_opts_row(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32_t* meta, int64_t N, int I,
                                int I_fast, uint64_t full_threshold, const void* priors, int priors_dtype,
                                const void* values, int values_dtype, float c, int temp_plies, uint64_t seed,
                                const uint64_t* seed_dev, int64_t env_id0, unsigned long long* row_plies, int64_t T,
                                uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs, int leaf_dtype,
                                uint8_t* leaf_mask, uint8_t* fresh, unsigned long long* plies_max, unsigned long long* stats,
-                               int32_t* err, MnkPuctNoise nz, float noise_eps, int noise_fast, float* root_priors) {
+                               int32_t* err, MnkPuctNoise nz, float noise_eps, int noise_fast, float* root_priors, float fpu,
+                               float fpu_root) {
   __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
   extern __shared__ double lds_gamma[];  // with noise: [MNK_PUCT_ROWS][C], a root's log-gammas between the two passes
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -407,7 +411,8 @@ k_search_selfplay_advance_opts(MnkGeom g, unsigned char* ws, uint64_t* planes, u
   uint32_t nstate = 0u;  // nothing pending: a full tree shows its root again (it cannot happen: nodes <= n_root <= I)
   if (nodes <= I) {
     puct_env_root<NW>(e, root, NWg);
-    nstate = puct_walk<NW, CN, CK, false, SOLVER>(g, e, I, c, node, prior, child, path, nodes, d, lane);
+    nstate = puct_walk<NW, CN, CK, false, SOLVER, false, FPU>(g, e, I, c, node, prior, child, path, nodes, d, lane, 0, 0u,
+                                                              nullptr, 0, nullptr, fpu, fpu_root);
     if (nstate == 0u) d = 0;
     if (lane == 0) {
 #pragma unroll
@@ -436,6 +441,36 @@ k_search_selfplay_advance_opts(MnkGeom g, unsigned char* ws, uint64_t* planes, u
   row_write_view<NW, CN>(g, pos, d & 1, i, leaf_obs, leaf_dtype, leaf_mask, lane);
 }
 
+template <int NW, int CN, int CK, bool SOLVER>
+__global__ void __launch_bounds__(256)
+k_search_selfplay_advance_opts(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32_t* meta, int64_t N, int I,
+                               int I_fast, uint64_t full_threshold, const void* priors, int priors_dtype,
+                               const void* values, int values_dtype, float c, int temp_plies, uint64_t seed,
+                               const uint64_t* seed_dev, int64_t env_id0, unsigned long long* row_plies, int64_t T,
+                               uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs, int leaf_dtype,
+                               uint8_t* leaf_mask, uint8_t* fresh, unsigned long long* plies_max, unsigned long long* stats,
+                               int32_t* err, MnkPuctNoise nz, float noise_eps, int noise_fast, float* root_priors) {
+  search_selfplay_advance_opts_row<NW, CN, CK, SOLVER, false>(
+      g, ws, planes, meta, N, I, I_fast, full_threshold, priors, priors_dtype, values,
+      values_dtype, c, temp_plies, seed, seed_dev, env_id0, row_plies, T, ring_planes, ring_visits, ring_z, leaf_obs,
+      leaf_dtype, leaf_mask, fresh, plies_max, stats, err, nz, noise_eps, noise_fast, root_priors, 0.0f, 0.0f);
+}
+template <int NW, int CN, int CK, bool SOLVER>
+__global__ void __launch_bounds__(256)
+k_search_selfplay_advance_opts_fpu(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32_t* meta, int64_t N, int I,
+                                   int I_fast, uint64_t full_threshold, const void* priors, int priors_dtype,
+                                   const void* values, int values_dtype, float c, int temp_plies, uint64_t seed,
+                                   const uint64_t* seed_dev, int64_t env_id0, unsigned long long* row_plies, int64_t T,
+                                   uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs, int leaf_dtype,
+                                   uint8_t* leaf_mask, uint8_t* fresh, unsigned long long* plies_max, unsigned long long* stats,
+                                   int32_t* err, MnkPuctNoise nz, float noise_eps, int noise_fast, float* root_priors,
+                                   float fpu, float fpu_root) {
+  search_selfplay_advance_opts_row<NW, CN, CK, SOLVER, true>(
+      g, ws, planes, meta, N, I, I_fast, full_threshold, priors, priors_dtype, values,
+      values_dtype, c, temp_plies, seed, seed_dev, env_id0, row_plies, T, ring_planes, ring_visits, ring_z, leaf_obs,
+      leaf_dtype, leaf_mask, fresh, plies_max, stats, err, nz, noise_eps, noise_fast, root_priors, fpu, fpu_root);
+}
+
 // k_search_selfplay_advance_opts for rows that keep the played move's subtree (the rule: include/mnk_hip.h,
 // mnk_search_selfplay_advance_keep).  The same shape: one wave per row, no workgroup barrier, every id clamped to the row
 // -- by TI = tree_iterations, the workspace's layout parameter; I stays the full budget.  The end of a ply calls
@@ -445,16 +480,17 @@ k_search_selfplay_advance_opts(MnkGeom g, unsigned char* ws, uint64_t* planes, u
 #ifndef MNK_KEEP_CARRY_B
 #define MNK_KEEP_CARRY_B 8  // nodes in flight in the carry's copy loop (an experiment's knob: DESIGN section 5, row 34)
 #endif
-template <int NW, int CN, int CK, bool SOLVER>
-__global__ void __launch_bounds__(256)
-k_search_selfplay_advance_keep(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32_t* meta, int64_t N, int I,
+// (a device function for the same reason as search_selfplay_advance_opts_row)
+template <int NW, int CN, int CK, bool SOLVER, bool FPU>
+__device__ __forceinline__ void
+search_selfplay_advance_keep_row(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32_t* meta, int64_t N, int I,
                                int I_fast, uint64_t full_threshold, const void* priors, int priors_dtype,
                                const void* values, int values_dtype, float c, int temp_plies, uint64_t seed,
                                const uint64_t* seed_dev, int64_t env_id0, unsigned long long* row_plies, int64_t T,
                                uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs, int leaf_dtype,
                                uint8_t* leaf_mask, uint8_t* fresh, unsigned long long* plies_max, unsigned long long* stats,
                                int32_t* err, MnkPuctNoise nz, float noise_eps, int noise_fast, float* root_priors, int TI,
-                               int keep_nodes, int32_t* carried) {
+                               int keep_nodes, int32_t* carried, float fpu, float fpu_root) {
   __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
   extern __shared__ double lds_gamma[];  // with noise: [MNK_PUCT_ROWS][C], a root's log-gammas between the two passes;
                                          // behind them (or first) the carry's maps
@@ -682,7 +718,8 @@ k_search_selfplay_advance_keep(MnkGeom g, unsigned char* ws, uint64_t* planes, u
   uint32_t nstate = 0u;  // nothing pending: a full tree shows its root again (it cannot happen: nodes <= keep_nodes + it)
   if (nodes <= TI) {
     puct_env_root<NW>(e, root, NWg);
-    nstate = puct_walk<NW, CN, CK, false, SOLVER>(g, e, TI, c, node, prior, child, path, nodes, d, lane);
+    nstate = puct_walk<NW, CN, CK, false, SOLVER, false, FPU>(g, e, TI, c, node, prior, child, path, nodes, d, lane, 0, 0u,
+                                                              nullptr, 0, nullptr, fpu, fpu_root);
     if (nstate == 0u) d = 0;
     if (lane == 0) {
 #pragma unroll
@@ -709,6 +746,39 @@ k_search_selfplay_advance_keep(MnkGeom g, unsigned char* ws, uint64_t* planes, u
   row_wave_sync();
   for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
   row_write_view<NW, CN>(g, pos, d & 1, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+}
+
+template <int NW, int CN, int CK, bool SOLVER>
+__global__ void __launch_bounds__(256)
+k_search_selfplay_advance_keep(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32_t* meta, int64_t N, int I,
+                               int I_fast, uint64_t full_threshold, const void* priors, int priors_dtype,
+                               const void* values, int values_dtype, float c, int temp_plies, uint64_t seed,
+                               const uint64_t* seed_dev, int64_t env_id0, unsigned long long* row_plies, int64_t T,
+                               uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs, int leaf_dtype,
+                               uint8_t* leaf_mask, uint8_t* fresh, unsigned long long* plies_max, unsigned long long* stats,
+                               int32_t* err, MnkPuctNoise nz, float noise_eps, int noise_fast, float* root_priors, int TI,
+                               int keep_nodes, int32_t* carried) {
+  search_selfplay_advance_keep_row<NW, CN, CK, SOLVER, false>(
+      g, ws, planes, meta, N, I, I_fast, full_threshold, priors, priors_dtype, values,
+      values_dtype, c, temp_plies, seed, seed_dev, env_id0, row_plies, T, ring_planes, ring_visits, ring_z, leaf_obs,
+      leaf_dtype, leaf_mask, fresh, plies_max, stats, err, nz, noise_eps, noise_fast, root_priors, TI, keep_nodes, carried,
+      0.0f, 0.0f);
+}
+template <int NW, int CN, int CK, bool SOLVER>
+__global__ void __launch_bounds__(256)
+k_search_selfplay_advance_keep_fpu(MnkGeom g, unsigned char* ws, uint64_t* planes, uint32_t* meta, int64_t N, int I,
+                                   int I_fast, uint64_t full_threshold, const void* priors, int priors_dtype,
+                                   const void* values, int values_dtype, float c, int temp_plies, uint64_t seed,
+                                   const uint64_t* seed_dev, int64_t env_id0, unsigned long long* row_plies, int64_t T,
+                                   uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs, int leaf_dtype,
+                                   uint8_t* leaf_mask, uint8_t* fresh, unsigned long long* plies_max, unsigned long long* stats,
+                                   int32_t* err, MnkPuctNoise nz, float noise_eps, int noise_fast, float* root_priors, int TI,
+                                   int keep_nodes, int32_t* carried, float fpu, float fpu_root) {
+  search_selfplay_advance_keep_row<NW, CN, CK, SOLVER, true>(
+      g, ws, planes, meta, N, I, I_fast, full_threshold, priors, priors_dtype, values,
+      values_dtype, c, temp_plies, seed, seed_dev, env_id0, row_plies, T, ring_planes, ring_visits, ring_z, leaf_obs,
+      leaf_dtype, leaf_mask, fresh, plies_max, stats, err, nz, noise_eps, noise_fast, root_priors, TI, keep_nodes, carried,
+      fpu, fpu_root);
 }
 
 extern "C" {
@@ -742,14 +812,16 @@ int mnk_search_selfplay_advance(void* workspace, uint64_t* planes, uint32_t* met
   return mnk_launch_status("search_selfplay_advance");
 }
 
-int mnk_search_selfplay_advance_opts(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+// (what mnk_search_selfplay_advance_opts and its _fpu form share: every host check, then the launch)
+static int advance_opts(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
                                      int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
                                      int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
                                      uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
                                      int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
                                      void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
                                      uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
-                                     float noise_eps, int noise_fast, float* root_priors, void* stream) {
+                                     float noise_eps, int noise_fast, float* root_priors, bool with_fpu, float fpu,
+                                     float fpu_root, void* stream) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
@@ -765,10 +837,25 @@ int mnk_search_selfplay_advance_opts(void* workspace, uint64_t* planes, uint32_t
       !(noise_eps >= 0.0f && noise_eps <= 1.0f) || (noise_fast != 0 && noise_fast != 1) ||
       g.C > MNK_PUCT_NOISE_CELLS_MAX)
     return MNK_EINVAL;
+  if (with_fpu && (!(fpu >= 0.0f && fpu <= 3.0e38f) || !(fpu_root >= 0.0f && fpu_root <= 3.0e38f))) return MNK_EINVAL;
   if (N == 0) return MNK_OK;
   const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
   const MnkPuctNoise nz = noise_alpha > 0.0f ? mnk_puct_noise_params(noise_alpha) : MnkPuctNoise{0.0, 0.0, 0.0};
   const size_t lds = noise_alpha > 0.0f ? (size_t)MNK_PUCT_ROWS * g.C * sizeof(double) : 0;
+#define MNK_ADVANCE_OPTS_FPU(SOLVER)                                                                                      \
+  MNK_DISPATCH(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search_selfplay_advance_opts_fpu<NW, CN, CK, SOLVER>), grid,      \
+                                     block, lds, (hipStream_t)stream, g, (unsigned char*)workspace, planes, meta, N,      \
+                                     iterations, fast_iterations, full_threshold, priors, priors_dtype, values,           \
+                                     values_dtype, c, temp_plies, seed, seed_dev, env_id0, (unsigned long long*)row_plies, \
+                                     T, ring_planes, ring_visits, ring_z, leaf_obs, leaf_dtype, leaf_mask, fresh,         \
+                                     (unsigned long long*)plies_max, (unsigned long long*)stats, err, nz, noise_eps,      \
+                                     noise_fast, root_priors, fpu, fpu_root))
+  if (with_fpu) {
+    if (solver) MNK_ADVANCE_OPTS_FPU(true);
+    else MNK_ADVANCE_OPTS_FPU(false);
+    return mnk_launch_status("search_selfplay_advance_opts_fpu");
+  }
+#undef MNK_ADVANCE_OPTS_FPU
 #define MNK_ADVANCE_OPTS(SOLVER)                                                                                          \
   MNK_DISPATCH(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search_selfplay_advance_opts<NW, CN, CK, SOLVER>), grid, block,   \
                                      lds, (hipStream_t)stream, g, (unsigned char*)workspace, planes, meta, N, iterations, \
@@ -781,6 +868,33 @@ int mnk_search_selfplay_advance_opts(void* workspace, uint64_t* planes, uint32_t
   else MNK_ADVANCE_OPTS(false);
 #undef MNK_ADVANCE_OPTS
   return mnk_launch_status("search_selfplay_advance_opts");
+}
+int mnk_search_selfplay_advance_opts(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                     int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                     int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                     uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
+                                     int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
+                                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                     uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                     float noise_eps, int noise_fast, float* root_priors, void* stream) {
+  return advance_opts(workspace, planes, meta, N, m, n, k, iterations, fast_iterations, full_threshold, priors, priors_dtype,
+                      values, values_dtype, c, temp_plies, seed, seed_dev, env_id0, row_plies, T, ring_planes, ring_visits,
+                      ring_z, leaf_obs, leaf_dtype, leaf_mask, fresh, plies_max, stats, err, solver, noise_alpha, noise_eps,
+                      noise_fast, root_priors, false, 0.0f, 0.0f, stream);
+}
+int mnk_search_selfplay_advance_opts_fpu(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                     int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                     int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                     uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
+                                     int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
+                                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                     uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                     float noise_eps, int noise_fast, float* root_priors, float fpu, float fpu_root,
+                                     void* stream) {
+  return advance_opts(workspace, planes, meta, N, m, n, k, iterations, fast_iterations, full_threshold, priors, priors_dtype,
+                      values, values_dtype, c, temp_plies, seed, seed_dev, env_id0, row_plies, T, ring_planes, ring_visits,
+                      ring_z, leaf_obs, leaf_dtype, leaf_mask, fresh, plies_max, stats, err, solver, noise_alpha, noise_eps,
+                      noise_fast, root_priors, true, fpu, fpu_root, stream);
 }
 
 // the LDS one workgroup of a plain launch may hold on the current device, read once (64 KiB where no device answers: the
@@ -798,7 +912,8 @@ static size_t advance_keep_lds_limit() {
   return limit;
 }
 
-int mnk_search_selfplay_advance_keep(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+// (what mnk_search_selfplay_advance_keep and its _fpu form share)
+static int advance_keep(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
                                      int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
                                      int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
                                      uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
@@ -806,7 +921,8 @@ int mnk_search_selfplay_advance_keep(void* workspace, uint64_t* planes, uint32_t
                                      void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
                                      uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
                                      float noise_eps, int noise_fast, float* root_priors, int tree_iterations,
-                                     int keep_nodes, int32_t* carried, void* stream) {
+                                     int keep_nodes, int32_t* carried, bool with_fpu, float fpu, float fpu_root,
+                                     void* stream) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
@@ -832,9 +948,24 @@ int mnk_search_selfplay_advance_keep(void* workspace, uint64_t* planes, uint32_t
   size_t lds_static = 0;
   MNK_DISPATCH(g, lds_static = sizeof(uint32_t) * MNK_PUCT_ROWS * 2 * NW);
   if (lds_static + lds > advance_keep_lds_limit()) return MNK_EINVAL;
+  if (with_fpu && (!(fpu >= 0.0f && fpu <= 3.0e38f) || !(fpu_root >= 0.0f && fpu_root <= 3.0e38f))) return MNK_EINVAL;
   if (N == 0) return MNK_OK;
   const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
   const MnkPuctNoise nz = noise_alpha > 0.0f ? mnk_puct_noise_params(noise_alpha) : MnkPuctNoise{0.0, 0.0, 0.0};
+#define MNK_ADVANCE_KEEP_FPU(SOLVER)                                                                                      \
+  MNK_DISPATCH(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search_selfplay_advance_keep_fpu<NW, CN, CK, SOLVER>), grid,      \
+                                     block, lds, (hipStream_t)stream, g, (unsigned char*)workspace, planes, meta, N,      \
+                                     iterations, fast_iterations, full_threshold, priors, priors_dtype, values,           \
+                                     values_dtype, c, temp_plies, seed, seed_dev, env_id0, (unsigned long long*)row_plies, \
+                                     T, ring_planes, ring_visits, ring_z, leaf_obs, leaf_dtype, leaf_mask, fresh,         \
+                                     (unsigned long long*)plies_max, (unsigned long long*)stats, err, nz, noise_eps,      \
+                                     noise_fast, root_priors, tree_iterations, keep_nodes, carried, fpu, fpu_root))
+  if (with_fpu) {
+    if (solver) MNK_ADVANCE_KEEP_FPU(true);
+    else MNK_ADVANCE_KEEP_FPU(false);
+    return mnk_launch_status("search_selfplay_advance_keep_fpu");
+  }
+#undef MNK_ADVANCE_KEEP_FPU
 #define MNK_ADVANCE_KEEP(SOLVER)                                                                                          \
   MNK_DISPATCH(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_search_selfplay_advance_keep<NW, CN, CK, SOLVER>), grid, block,   \
                                      lds, (hipStream_t)stream, g, (unsigned char*)workspace, planes, meta, N, iterations, \
@@ -847,6 +978,34 @@ int mnk_search_selfplay_advance_keep(void* workspace, uint64_t* planes, uint32_t
   else MNK_ADVANCE_KEEP(false);
 #undef MNK_ADVANCE_KEEP
   return mnk_launch_status("search_selfplay_advance_keep");
+}
+int mnk_search_selfplay_advance_keep(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                     int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                     int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                     uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
+                                     int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
+                                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                     uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                     float noise_eps, int noise_fast, float* root_priors, int tree_iterations,
+                                     int keep_nodes, int32_t* carried, void* stream) {
+  return advance_keep(workspace, planes, meta, N, m, n, k, iterations, fast_iterations, full_threshold, priors, priors_dtype,
+                      values, values_dtype, c, temp_plies, seed, seed_dev, env_id0, row_plies, T, ring_planes, ring_visits,
+                      ring_z, leaf_obs, leaf_dtype, leaf_mask, fresh, plies_max, stats, err, solver, noise_alpha, noise_eps,
+                      noise_fast, root_priors, tree_iterations, keep_nodes, carried, false, 0.0f, 0.0f, stream);
+}
+int mnk_search_selfplay_advance_keep_fpu(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n, int k,
+                                     int iterations, int fast_iterations, uint64_t full_threshold, const void* priors,
+                                     int priors_dtype, const void* values, int values_dtype, float c, int temp_plies,
+                                     uint64_t seed, const uint64_t* seed_dev, int64_t env_id0, uint64_t* row_plies,
+                                     int64_t T, uint64_t* ring_planes, uint16_t* ring_visits, int8_t* ring_z,
+                                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, uint8_t* fresh,
+                                     uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
+                                     float noise_eps, int noise_fast, float* root_priors, int tree_iterations,
+                                     int keep_nodes, int32_t* carried, float fpu, float fpu_root, void* stream) {
+  return advance_keep(workspace, planes, meta, N, m, n, k, iterations, fast_iterations, full_threshold, priors, priors_dtype,
+                      values, values_dtype, c, temp_plies, seed, seed_dev, env_id0, row_plies, T, ring_planes, ring_visits,
+                      ring_z, leaf_obs, leaf_dtype, leaf_mask, fresh, plies_max, stats, err, solver, noise_alpha, noise_eps,
+                      noise_fast, root_priors, tree_iterations, keep_nodes, carried, true, fpu, fpu_root, stream);
 }
 
 }  // extern "C"

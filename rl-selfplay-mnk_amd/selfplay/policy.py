@@ -337,12 +337,22 @@ class PUCTSearchPolicy(Policy):
     (0, which ``act(deterministic=True)`` passes: no randomness at all).  Below the root the search is the one above.  One
     more launch per ``act`` (the draw, after the roots' evaluation) and three buffers of the policy's own.  It does not
     combine with ``reuse``, ``leaves > 1``, ``solver``, ``root_noise`` or ``temperature=1`` yet (``ValueError``).
-    ``None`` (the default): the search above, launch for launch, and nothing is allocated."""
+    ``None`` (the default): the search above, launch for launch, and nothing is allocated.
+
+    ``fpu=r`` or ``fpu=(r, r_root)`` turns on first-play urgency (the rule: include/mnk_hip.h, mnk_puct_step_fpu).  The
+    score above values a move without a visit at ``q = 0``, "an untried move is a draw": where every visited move looks
+    lost the search then tries each remaining cell once before it returns to any, and where the first move looks won it
+    never tries a second.  With ``fpu`` an untried move is valued at its parent's own mean value less ``r * sqrt(prior
+    mass of the parent's visited moves)`` (``r_root`` at the root, ``r`` below it; not below -1) -- KataGo's and Leela's
+    reduction; 0.2 is their usual value, and ``fpu=0`` still differs from ``None`` (the parent's value, not 0).  Every
+    step is then ``mnk_puct_step_fpu``, at any ``leaves``, with or without ``reuse``, ``solver`` and ``root_noise``; the
+    evaluator sees the same batch shapes.  It does not combine with ``gumbel`` yet (``ValueError``).  ``None`` (the
+    default): the search above, launch for launch, and nothing is allocated."""
 
     def __init__(self, k: int, model=None, evaluator=None, iterations: int = 256, c: float = 1.25, temperature: int = 0,
                  leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None, leaves: int = 1,
                  root_noise=None, solver: bool = False, gumbel: int = None, gumbel_c=(50.0, 0.5),
-                 gumbel_scale: float = 1.0):
+                 gumbel_scale: float = 1.0, fpu=None):
         if (model is None) == (evaluator is None):
             raise ValueError("PUCTSearchPolicy needs exactly one of model and evaluator")
         self.k = int(k)
@@ -388,6 +398,9 @@ class PUCTSearchPolicy(Policy):
                              ("root_noise", self.root_noise is not None), ("temperature=1", temperature == 1)):
                 if on:
                     raise ValueError(f"gumbel does not combine with {name} yet")
+        self.fpu = self._checked_fpu(fpu)
+        if self.fpu is not None and self.gumbel is not None:
+            raise ValueError("fpu does not combine with gumbel yet")
         self._bufs = None  # (key, workspace, leaf_obs, leaf_mask, noised priors or None)
         self._gumbel_bufs = None  # gumbel: (key, table, gscore, vroot)
 
@@ -405,6 +418,22 @@ class PUCTSearchPolicy(Policy):
         if not 0.0 <= eps <= 1.0:
             raise ValueError(f"root_noise: eps must lie in [0, 1], got {eps}")
         return alpha, eps
+
+    @staticmethod
+    def _checked_fpu(fpu):
+        """None, or (fpu, fpu_root) as floats, each finite and >= 0 (as a float32 too); a number r stands for (r, r)"""
+        if fpu is None:
+            return None
+        try:
+            pair = tuple(float(x) for x in fpu) if hasattr(fpu, "__iter__") else (float(fpu),) * 2
+            if len(pair) != 2 or isinstance(fpu, (bool, str)):
+                raise ValueError
+        except (TypeError, ValueError):
+            raise ValueError(f"fpu must be None, a number or (fpu, fpu_root), got {fpu!r}") from None
+        for x in pair:
+            if not (math.isfinite(x) and 0.0 <= x <= 3.0e38):
+                raise ValueError(f"fpu: the reductions must be finite and >= 0, got {fpu!r}")
+        return pair
 
     @staticmethod
     def _checked_gumbel(gumbel, gumbel_c, gumbel_scale):
@@ -507,8 +536,11 @@ class PUCTSearchPolicy(Policy):
             cap = self.tree_nodes - 1  # the workspace's layout parameter: node capacity - 1 (= I without reuse)
             # leaves = 1 stays on the entry points without the argument (the same results either way: include/mnk_hip.h)
             # (the solver's step takes `leaves` always, and the workspace the *_leaves entry points set up)
-            sfx, lv = ("_leaves", (self.leaves,)) if self.leaves > 1 or self.solver else ("", ())
+            # (so does the step with first-play urgency, which takes the solver as an argument)
+            sfx, lv = ("_leaves", (self.leaves,)) if self.leaves > 1 or self.solver or self.fpu is not None else ("", ())
             step, out = ("mnk_puct_step_solver", (mnk_hip.ptr(proof),)) if self.solver else ("mnk_puct_step" + sfx, ())
+            if self.fpu is not None:
+                step, out = "mnk_puct_step_fpu", (mnk_hip.ptr(proof), int(self.solver), *self.fpu)
             if self.reuse:
                 mnk_hip.call("mnk_puct_rebase" + sfx, mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k,
                              cap, self.tree_nodes - I, *lv, mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code,

@@ -31,6 +31,10 @@ mnk_puct_step_gumbel) and plays through ``mnk_search_selfplay_step_moves``: the 
 the improved policy, drawn at the ring's ply counter like the noise -- and the ring's u16 visits are that policy scaled to
 65 535, which ``mnk_search_gather`` turns back into the target.  ``temp_plies`` is then not read.
 
+``fpu=r`` or ``fpu=(r, r_root)`` searches with first-play urgency (``PUCTSearchPolicy(fpu=...)``, the rule:
+include/mnk_hip.h, mnk_puct_step_fpu): a move without a visit is valued at its parent's mean value less a reduction, not
+at 0, so a root that looks lost still concentrates its visits -- and its policy target -- on few moves.
+
 ``AsyncSearchSelfPlay`` (below) is the same loop without the lockstep: one launch per evaluator call, a search budget per
 row and ply, rows that play on as soon as their search is done.  It takes ``root_noise`` and ``solver`` too, built into
 its one launch (``mnk_search_selfplay_advance_opts``): the noise of a row's ply is a function of (seed, row id, the row's
@@ -55,7 +59,8 @@ class SearchSelfPlay:
     def __init__(self, m: int, n: int, k: int, num_envs: int, model=None, evaluator=None, iterations: int = 64,
                  c: float = 1.25, temp_plies: int = None, capacity: int = None, seed=None, leaf_dtype=torch.float32,
                  device="cuda", reuse: bool = False, tree_nodes: int = None, leaves: int = 1, root_noise=None,
-                 solver: bool = False, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0):
+                 solver: bool = False, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0,
+                 fpu=None):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -68,12 +73,12 @@ class SearchSelfPlay:
         capacity = 2 * C if capacity is None else int(capacity)
         if capacity < C:
             raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
-        # (the policy checks model / evaluator, iterations, c, leaves, root_noise and leaf_dtype before anything touches the
+        # (the policy checks model / evaluator, iterations, c, leaves, root_noise, fpu and leaf_dtype before anything touches the
         # GPU)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
                                        temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=reuse, tree_nodes=tree_nodes,
                                        leaves=leaves, root_noise=root_noise, solver=solver, gumbel=gumbel,
-                                       gumbel_c=gumbel_c, gumbel_scale=gumbel_scale)
+                                       gumbel_c=gumbel_c, gumbel_scale=gumbel_scale, fpu=fpu)
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
@@ -237,6 +242,12 @@ class AsyncSearchSelfPlay:
     trees are not state, and the ``gscore`` that the search restarted by ``load_state_dict`` redraws is a function of
     (seed, row id, ply count), so it is the one the interrupted search had.
 
+    ``fpu=r`` or ``fpu=(r, r_root)`` is ``SearchSelfPlay``'s ``fpu``: first-play urgency in every selection (the rule:
+    include/mnk_hip.h, mnk_puct_step_fpu), with ``root_noise``, ``solver`` and ``keep_tree``.  ``advance`` then calls
+    ``mnk_search_selfplay_advance_opts_fpu``, under ``keep_tree`` ``mnk_search_selfplay_advance_keep_fpu``; with every ply
+    full the games are those of ``SearchSelfPlay(fpu=..., same options)`` of the same seed, bit for bit (the solver
+    excepted, as above).  With ``leaves > 1`` or ``gumbel`` it raises ``ValueError``.
+
     With no option ``advance`` calls ``mnk_search_selfplay_advance``, as before; with ``root_noise`` or ``solver`` it
     calls ``mnk_search_selfplay_advance_opts``; with ``keep_tree`` it calls ``mnk_search_selfplay_advance_keep``, which
     takes the other two; with ``leaves > 1`` it calls ``mnk_search_selfplay_advance_leaves``, which takes ``root_noise``
@@ -246,7 +257,7 @@ class AsyncSearchSelfPlay:
                  fast_iterations: int = None, full_prob: float = 1.0, c: float = 1.25, temp_plies: int = None,
                  capacity: int = None, seed=None, leaf_dtype=torch.float32, device="cuda", root_noise=None,
                  noise_on_fast: bool = False, solver: bool = False, keep_tree: bool = False, tree_nodes: int = None,
-                 leaves: int = 1, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0):
+                 leaves: int = 1, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0, fpu=None):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -289,6 +300,12 @@ class AsyncSearchSelfPlay:
                              ("solver=True", self.solver), ("root_noise", self.root_noise is not None)):
                 if on:
                     raise ValueError(f"gumbel does not combine with {name} yet")
+        self.fpu = PUCTSearchPolicy._checked_fpu(fpu)
+        if self.fpu is not None:
+            if self.gumbel is not None:
+                raise ValueError("fpu does not combine with gumbel yet")
+            if self.leaves > 1:
+                raise ValueError("fpu does not combine with leaves > 1 in the per-row loop yet")
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
@@ -367,6 +384,14 @@ class AsyncSearchSelfPlay:
                 alpha, eps = self.root_noise or (0.0, 0.0)
                 mnk_hip.call("mnk_search_selfplay_advance_leaves", *head, self.leaves, *tail, int(self.solver), alpha, eps,
                              int(self.noise_on_fast), mnk_hip.ptr(self.root_priors), mnk_hip.ptr(self.row_sims), stream)
+            elif self.fpu is not None:
+                alpha, eps = self.root_noise or (0.0, 0.0)
+                opts = (*args, int(self.solver), alpha, eps, int(self.noise_on_fast), mnk_hip.ptr(self.root_priors))
+                if self.keep_tree:
+                    mnk_hip.call("mnk_search_selfplay_advance_keep_fpu", *opts, self.tree_nodes - 1,
+                                 self.tree_nodes - self.iterations, mnk_hip.ptr(self.carried), *self.fpu, stream)
+                else:
+                    mnk_hip.call("mnk_search_selfplay_advance_opts_fpu", *opts, *self.fpu, stream)
             elif self.keep_tree:
                 alpha, eps = self.root_noise or (0.0, 0.0)
                 mnk_hip.call("mnk_search_selfplay_advance_keep", *args, int(self.solver), alpha, eps,
