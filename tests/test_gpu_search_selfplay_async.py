@@ -238,30 +238,66 @@ def test_a_restored_state_continues_as_the_rule_does(hip):
 
 
 # ----------------------------------------------------------------------------- 5. refusals
-def test_the_host_refuses_bad_budgets_before_anything_is_enqueued(hip):
+# entry point: (the player's options, the argument index of `leaves` or None, has temp_plies, {its own arguments after
+# `err`, by offset: (what the player passes there -- checked, so that a moved argument fails here --, one bad value)})
+KEEP_NODES = lambda sp: sp.tree_nodes - sp.iterations  # noqa: E731
+ENTRY_POINTS = {
+    "mnk_search_selfplay_advance": ({}, None, True, {}),
+    "mnk_search_selfplay_advance_opts": ({"solver": True}, None, True, {0: (1, 2)}),                      # solver
+    "mnk_search_selfplay_advance_opts_fpu": ({"solver": True, "fpu": 0.25}, None, True, {0: (1, 2), 5: (0.25, -1.0)}),  # fpu
+    "mnk_search_selfplay_advance_keep": ({"keep_tree": True}, None, True, {6: (KEEP_NODES, 0)}),          # keep_nodes
+    "mnk_search_selfplay_advance_keep_fpu": ({"keep_tree": True, "fpu": 0.25}, None, True,
+                                             {6: (KEEP_NODES, 0), 8: (0.25, -1.0)}),
+    "mnk_search_selfplay_advance_leaves": ({"leaves": 2}, 9, True, {0: (0, 2)}),                          # solver; leaves below
+    "mnk_search_selfplay_advance_gumbel": ({"gumbel": 4}, None, False, {0: (4, 0)}),                      # considered
+}
+
+
+@pytest.mark.parametrize("name", list(ENTRY_POINTS))
+def test_the_host_refuses_bad_budgets_before_anything_is_enqueued(hip, name):
     lib = hip.lib
-    sp = new_async(hip, (3, 3, 3), 5, 1, capacity=9)
-    sp.advance(3)
+    options, at_leaves, has_temp, own = ENTRY_POINTS[name]
+    sp = new_async(hip, (3, 3, 3), 5, 1, capacity=9, **options)
+    # the argument list of the player's own call of the entry point
+    seen, inner = [], lib.call
+    lib.call = lambda fn, *a: (seen.append((fn, a)), inner(fn, *a))[1]
+    try:
+        sp.advance(3)
+    finally:
+        lib.call = inner
+    assert {fn for fn, _ in seen if fn.startswith("mnk_search_selfplay_advance")} == {name}
+    good = list([a for fn, a in seen if fn == name][-1])
     torch.cuda.synchronize()
     before = [t.clone() for t in (sp.workspace, sp.row_plies, sp.leaf_obs, sp.buffer.z, sp.env._meta)]
     priors, values = exact_torch(9)(sp.leaf_obs, sp.leaf_mask)
     priors, values = priors.contiguous(), values.contiguous()
+    # where the arguments stand: iterations, fast_iterations, [leaves,] full_threshold, priors, .., values, ..,
+    # [temp_plies,] .., T, .., err, then the entry point's own
+    shift = 0 if at_leaves is None else 1
+    FULL_AT, FAST_AT, THRESHOLD_AT, PRIORS_AT, VALUES_AT = 7, 8, 9 + shift, 10 + shift, 12 + shift
+    T_AT = 19 + shift + (1 if has_temp else 0)
+    OWN_AT = T_AT + 11
+    good[PRIORS_AT], good[VALUES_AT] = lib.ptr(priors), lib.ptr(values)
+    assert good[FULL_AT] == FULL and good[FAST_AT] == FAST and good[THRESHOLD_AT] == THRESHOLD and good[T_AT] == 9
 
-    def adv(T=9, full=FULL, fast=FAST, threshold=THRESHOLD):
-        buf = sp.buffer
-        fn = lib.load().mnk_search_selfplay_advance
-        return fn(lib.ptr(sp.workspace), lib.ptr(sp.env._planes), lib.ptr(sp.env._meta), 5, 3, 3, 3, full, fast, threshold,
-                  lib.ptr(priors), 0, lib.ptr(values), 0, 1.25, 2, 1, None, 0, lib.ptr(sp.row_plies), T, lib.ptr(buf.planes),
-                  lib.ptr(buf.visits), lib.ptr(buf.z), lib.ptr(sp.leaf_obs), 0, lib.ptr(sp.leaf_mask), lib.ptr(sp.fresh),
-                  lib.ptr(buf.plies), lib.ptr(sp.stats), lib.ptr(sp.env._err), lib.stream_ptr(DEV))
+    def adv(changed=()):
+        args = list(good)
+        for at, value in dict(changed).items():
+            args[at] = value
+        return getattr(lib.load(), name)(*args)
 
     EINVAL = -1
-    assert adv(T=8) == EINVAL and adv(fast=FULL + 1) == EINVAL and adv(fast=0) == EINVAL
-    assert adv(threshold=2 ** 32 + 1) == EINVAL
+    assert adv({T_AT: 8}) == EINVAL and adv({FAST_AT: FULL + 1}) == EINVAL and adv({FAST_AT: 0}) == EINVAL
+    assert adv({THRESHOLD_AT: 2 ** 32 + 1}) == EINVAL
+    for offset, (passed, bad) in own.items():
+        assert good[OWN_AT + offset] == (passed(sp) if callable(passed) else passed), (name, offset)
+        assert adv({OWN_AT + offset: bad}) == EINVAL, (name, offset)
+    if at_leaves is not None:
+        assert good[at_leaves] == 2 and adv({at_leaves: 4}) == EINVAL  # (4 does not divide 6 iterations)
     torch.cuda.synchronize()
     for was, now in zip(before, (sp.workspace, sp.row_plies, sp.leaf_obs, sp.buffer.z, sp.env._meta)):
         assert torch.equal(was, now)
-    assert adv() == 0 and adv(threshold=2 ** 32) == 0 and adv(threshold=0, fast=1) == 0
+    assert adv() == 0 and adv({THRESHOLD_AT: 2 ** 32}) == 0 and adv({THRESHOLD_AT: 0, FAST_AT: 1}) == 0
 
 
 def test_a_root_without_a_legal_cell_is_reported_and_left_alone(hip):
@@ -283,4 +319,35 @@ def test_a_root_without_a_legal_cell_is_reported_and_left_alone(hip):
     assert sp.env._planes[:, 0, 2].tolist() == [bits(black), bits(white)]
     assert (sp.buffer.z[:, 2] == lib.Z_UNKNOWN).all() and not sp.buffer.visits[:, 2].any()
     assert sp.leaf_mask[2].sum().item() == 0 and sp.leaf_obs[2].sum().item() == 9  # its root, shown again
+    sp.env._err.zero_()
+
+
+@pytest.mark.parametrize("options", [{"root_noise": (0.3, 0.25), "solver": True}, {"keep_tree": True}, {"leaves": 2}],
+                         ids=["opts", "keep", "leaves"])
+def test_every_form_reports_a_root_without_a_legal_cell_and_leaves_it_alone(hip, options):
+    """the same row in the kernels with the options, with kept trees and with two leaves per row: the error row is one
+    piece of code, and every form must go through it"""
+    lib = hip.lib
+    N, L = 5, options.get("leaves", 1)
+    sp = new_async(hip, (3, 3, 3), N, 4, capacity=9, **options)
+    s = sp.state_dict()
+    # row 2 holds a full board without a run (x o x / x o o / o x x), handed in by state
+    black, white = [0, 2, 3, 7, 8], [1, 4, 5, 6]
+    bits = lambda cells: sum(1 << (a + a // 3) for a in cells)  # noqa: E731
+    s["env"]["planes"][0, 0, 2], s["env"]["planes"][1, 0, 2] = bits(black), bits(white)
+    s["env"]["meta"][2] = (9 << 1) | 1
+    sp.load_state_dict(s)
+    if L > 1:
+        sp.row_sims[2] = 5  # (a count that no ply of this run leaves behind)
+    sp.advance(25)
+    torch.cuda.synchronize()
+    assert sp.env._err.tolist() == [lib.ERR_VISITS, 2]
+    assert sp.row_plies[2].item() == 0 and sp.fresh[2].item() == 0 and (sp.row_plies > 0).sum().item() == N - 1
+    assert sp.env._meta[2].item() == (9 << 1) | 1
+    assert sp.env._planes[:, 0, 2].tolist() == [bits(black), bits(white)]
+    assert (sp.buffer.z[:, 2] == lib.Z_UNKNOWN).all() and not sp.buffer.visits[:, 2].any()
+    for b in range(2 * L, 2 * L + L):  # its root, shown again in every batch row of the row
+        assert sp.leaf_mask[b].sum().item() == 0 and sp.leaf_obs[b].sum().item() == 9
+    if L > 1:
+        assert sp.row_sims[2].item() == 5
     sp.env._err.zero_()

@@ -215,13 +215,13 @@ def kernels(parent, work, out_path):
         by_name = {v: k for k, v in dm.items()}
         names.update(dm)
         for mangled, plain in dm.items():
-            if "_fpu<" not in plain:
-                continue
             args = re.search(r"<(.*)>", plain).group(1).split(", ")
             if plain.startswith("k_puct_step_fpu"):
                 sib = ("k_puct_step_solver" if args[3] == "true" else "k_puct_step_leaves") + "<" + ", ".join(args[:3]) + ">"
+            elif re.match(r"k_search_selfplay_advance_(opts|keep)<", plain) and args[4] == "true":
+                sib = plain.split("<")[0] + "<" + ", ".join(args[:4]) + ", false>"  # (FPU: the kernels' last template flag)
             else:
-                sib = plain.replace("_fpu<", "<")
+                continue
             r, s = res[mangled], res[by_name[sib]]
             lines.append(f"| `{plain}` | {r['VGPRs']} | `{sib.split('<')[0]}` | {s['VGPRs']} | {len(asm[mangled])} | "
                          f"{len(asm[by_name[sib]])} | {r['LDS Size']} | {r['ScratchSize']} | "
