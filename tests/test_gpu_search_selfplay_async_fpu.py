@@ -3,9 +3,13 @@
 launch for launch with the numpy rule (tests/puct_fpu_rule.py: ``AsyncKeepFpuRule``, which is ``AsyncOptsFpuRule`` without
 ``keep_tree``), with and without ``keep_tree``, the solver and root noise, on 3x3x3 from the empty board, on 9x9x5 from late
 positions in the style of tests/golden/search_selfplay_async_starts.npz (a drawn board less a few stones: games end, fill
-and are drawn inside the run) and on that fixture's own 7x9x5 rows, the sibling board of the 9x9x5 variant; with every ply
-full it must leave, bit for bit, what the lockstep ``SearchSelfPlay(fpu=..., same options)`` leaves -- with the solver the
-games are the lockstep solver's in no more launches, the exception the existing equalities state.
+and are drawn inside the run) and on that fixture's own 7x9x5 rows, the sibling board of the 9x9x5 variant; and both
+entry points on every other kind of board they are compiled for -- 12x13x5, 16x15x5 and 19x19x5 (the variants <6,13,5>,
+<8,15,5> and <12,19,5>) and 12x12x5 (the generic form of five words) from the fixture's rows, 7x7x4 (the generic form of
+two) from the empty board; the cases are tests/search_selfplay_async_fpu_cases.py's, where tests/test_puct_fpu_cpu.py shows
+with the rule alone that each uses the options it turns on.  With every ply full it must leave, bit for bit, what the
+lockstep ``SearchSelfPlay(fpu=..., same options)`` leaves (3x3x3, 9x9x5 and, for a few plies, 16x15x5 and 12x12x5) -- with
+the solver the games are the lockstep solver's in no more launches, the exception the existing equalities state.
 
 Everything is bit-exact except the noised priors of a root against numpy's, at the ``rtol=1e-6`` of
 tests/test_gpu_puct_noise.py (``Beside`` of tests/test_gpu_search_selfplay_async_opts.py makes it); the rule then takes the
@@ -14,65 +18,23 @@ import numpy as np
 import pytest
 import torch
 
-from oracle.packing import pack_boards
 from player_cases import DEV, hip  # noqa: F401 (hip: the fixture)
-from puct_fpu_rule import AsyncKeepFpuRule
-from puct_solver_cases import drawn_board
-from test_gpu_search_selfplay_async import (ENV_ID0, FAST, FULL, THRESHOLD, assert_same_state, exact_torch, new_async,
-                                            start_state)
+from search_selfplay_async_fpu_cases import CASES, FPU, N, NOISE, new_rule
+from test_gpu_search_selfplay_async import ENV_ID0, THRESHOLD, assert_same_state, exact_torch, new_async
 from test_gpu_search_selfplay_async_keep import KeepBeside
 from test_gpu_search_selfplay_async_opts import Beside, same_players
 
 pytestmark = pytest.mark.gpu
-NOISE, FPU, N = (0.3, 0.25), (0.25, 0.5), 5  # (five rows: a partial workgroup)
-
-
-def late_start(m, n, k, rows, seed=1):
-    """(planes, meta) of ``rows`` env states: the drawn board less 3 .. 8 stones taken off at random, the side to move by
-    the parity of the stones, as the rows of the fixture two stones short of a drawn board.  (The seed: with 0 a noised
-    root has one free cell, of prior 1, on which the mix with a Dirichlet draw over one cell is the prior itself, and
-    ``Beside`` asks every noised root to differ from its plain priors; checked with the rule on the CPU.)"""
-    full, rng = drawn_board(m, n, k), np.random.default_rng(seed)
-    boards = []
-    for i in range(rows):
-        keep = np.ones(m * n, bool)
-        keep[rng.choice(m * n, size=3 + i % 6, replace=False)] = False
-        boards.append(full & keep.reshape(m, n))
-    boards = np.stack(boards)
-    moves = boards.reshape(rows, -1).sum(axis=1)
-    return pack_boards(boards, m, n), ((moves << 1) | (moves & 1)).astype(np.uint32)
-
-
-def state_of(board, start):
-    if start == "late":
-        return late_start(*board, N)
-    return start_state(board, start)
-
-
-# board, start, temp_plies, rounds, seed, root_noise, solver, keep_tree, tree_nodes
-CASES = [
-    ((3, 3, 3), None, 2, 130, 6, NOISE, True, False, None),
-    ((3, 3, 3), None, 2, 130, 6, None, True, True, 13),
-    ((3, 3, 3), None, 2, 130, 6, None, False, True, 8),
-    ((9, 9, 5), "late", 4, 150, 6, NOISE, False, False, None),
-    ((9, 9, 5), "late", 4, 150, 6, NOISE, True, True, 13),
-    ((9, 9, 5), "late", 4, 150, 6, None, True, False, None),
-    ((7, 9, 5), "golden", 4, 150, 6, None, False, True, 13),
-]
 
 
 @pytest.mark.parametrize("board,start,temp,rounds,seed,noise,solver,keep,tree_nodes", CASES)
 def test_mixed_budgets_equal_the_rule_launch_for_launch(hip, board, start, temp, rounds, seed, noise, solver, keep,
                                                         tree_nodes):
     m, n, k = board
-    rule = AsyncKeepFpuRule(m, n, k, N, m * n, FULL, FAST, THRESHOLD, 1.25, temp, seed, ENV_ID0, root_noise=noise,
-                            solver=solver, keep_tree=keep, tree_nodes=tree_nodes, fpu=FPU)
-    state = state_of(board, start)
-    if state is not None:
-        rule.load(*state)
-        rule.begin()
-    sp = new_async(hip, board, N, seed, temp_plies=temp, capacity=m * n, root_noise=noise, solver=solver, keep_tree=keep,
-                   tree_nodes=tree_nodes, fpu=FPU)
+    rule, state = new_rule(board, start, temp, seed, noise, solver, keep, tree_nodes)
+    assert rule.N % 4  # a partial workgroup
+    sp = new_async(hip, board, rule.N, seed, temp_plies=temp, capacity=m * n, root_noise=noise, solver=solver,
+                   keep_tree=keep, tree_nodes=tree_nodes, fpu=FPU)
     sp.sampler.env_id0 = ENV_ID0
     if state is not None:
         s = sp.state_dict()
@@ -92,7 +54,9 @@ def test_mixed_budgets_equal_the_rule_launch_for_launch(hip, board, start, temp,
 # ----------------------------------------------------------------------------- every ply full: the lockstep player
 @pytest.mark.parametrize("noise", [None, NOISE])
 @pytest.mark.parametrize("keep,tree_nodes", [(False, None), (True, 13), (True, 8)])
-@pytest.mark.parametrize("board,plies,capacity", [((3, 3, 3), 2 * 9 + 5, None), ((9, 9, 5), 24, 81)])
+@pytest.mark.parametrize("board,plies,capacity", [((3, 3, 3), 2 * 9 + 5, None), ((9, 9, 5), 24, 81),
+                                                  # a multi-word variant and the generic form of five words, a few plies
+                                                  ((16, 15, 5), 6, None), ((12, 12, 5), 6, None)])
 def test_with_every_ply_full_it_is_the_lockstep_player(hip, board, plies, capacity, keep, tree_nodes, noise):
     from selfplay.search_selfplay import SearchSelfPlay
 
@@ -111,7 +75,11 @@ def test_with_every_ply_full_it_is_the_lockstep_player(hip, board, plies, capaci
     assert sp.fresh.tolist() == [1] * N and sp.row_plies.tolist() == [plies] * N
     assert sp.buffer.plies.item() == plies and sp.env._err.tolist() == [0, 0]
     assert lock.buffer.visits.any()
-    if board == (9, 9, 5):
+    if board in ((16, 15, 5), (12, 12, 5)):
+        # (six plies of six iterations from the empty board: no game ends, and no unvisited cell's urgency decides a
+        # selection -- the player without fpu records the same; the mixed cases above hold the urgency on these boards)
+        assert lock.pop_game_stats() == sp.pop_game_stats()
+    elif board == (9, 9, 5):
         assert lock.pop_game_stats() == sp.pop_game_stats()
         plain = new_async(hip, board, N, 13, **kw)
         plain.advance(plies * (I + 1))

@@ -9,7 +9,13 @@ a legal cell; the example's loop.
 Ring visits on full plies are compared within ONE count: the policy is the f32 of f64 values that agree with numpy's to a
 few ulps, rtol 1e-6 * 65 535 is 0.07 of a count, so a difference can arise only next to a rounding boundary of rint (the
 bar of tests/test_gpu_puct_gumbel.py).  On fast plies they are exactly zero.  The seeds and shapes are those of
-tests/test_search_selfplay_async_gumbel_cpu.py, which shows on the CPU that they reach every branch."""
+tests/test_search_selfplay_async_gumbel_cpu.py, which shows on the CPU that they reach every branch.
+
+The boards: with mixed budgets 3x3x3, 4x6x3 and 9x9x5 from the empty board, 12x13x5, 16x15x5 and 19x19x5 (the variants
+<6,13,5>, <8,15,5> and <12,19,5>) and 12x12x5 (the generic form of five words) from the stored late positions of
+tests/golden/search_selfplay_async_starts.npz, and 7x7x4 (the generic form of two words) from the empty board for more
+than a lap of its ring; uint8 and bfloat16 leaves, bfloat16 priors and values and the device key word are spread over
+them.  With every ply full 3x3x3, 9x9x5, 7x9x5 and, for a few plies, the same four large boards."""
 import importlib.util
 import math
 import os
@@ -24,7 +30,8 @@ from search_selfplay_async_gumbel_rule import AsyncGumbelRule
 from search_selfplay_async_rule import exact_np
 from test_gpu_search_selfplay_async import exact_torch, load_start, new_async  # noqa: F401
 from test_gpu_search_selfplay_async_opts import same_players
-from test_search_selfplay_async_gumbel_cpu import CONSIDERED, ENV_ID0, FAST, FULL, MIXED_CASES, THRESHOLD
+from test_search_selfplay_async_gumbel_cpu import (CONSIDERED, ENV_ID0, FAST, FULL, MIXED_HOW, MIXED_RUNS, THRESHOLD,
+                                                   new_rule)
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -38,7 +45,14 @@ def ring(sp):
 # ----------------------------------------------------------------------------- 1. every ply full: the lockstep player
 @pytest.mark.parametrize("board,N,I,cons,plies,capacity", [((3, 3, 3), 6, 8, 4, 2 * 9 + 5, None),
                                                            ((9, 9, 5), 5, 16, 8, 81 + 5, 81),
-                                                           ((7, 9, 5), 5, 8, 8, 20, None)])
+                                                           ((7, 9, 5), 5, 8, 8, 20, None),
+                                                           # the multi-word variants and the generic form of five words,
+                                                           # from the empty board: no game ends in so few plies (the
+                                                           # mixed cases below carry the game ends)
+                                                           ((12, 13, 5), 5, 4, 4, 6, None),
+                                                           ((16, 15, 5), 5, 4, 4, 6, None),
+                                                           ((19, 19, 5), 3, 4, 4, 6, None),
+                                                           ((12, 12, 5), 3, 4, 4, 6, None)])
 def test_with_every_ply_full_it_is_the_lockstep_gumbel_player(hip, board, N, I, cons, plies, capacity):
     from selfplay.search_selfplay import SearchSelfPlay
 
@@ -62,11 +76,6 @@ def test_with_every_ply_full_it_is_the_lockstep_gumbel_player(hip, board, N, I, 
 
 
 # ----------------------------------------------------------------------------- 2 / 3. mixed budgets against the rule
-def new_rule(board, N, seed, T=None, env_id0=ENV_ID0):
-    m, n, k = board
-    return AsyncGumbelRule(m, n, k, N, T or m * n, FULL, FAST, THRESHOLD, 1.25, seed, CONSIDERED, env_id0=env_id0)
-
-
 def follow(sp, rule, rounds, obs, mask, what=""):
     """``rounds`` launches of the player beside the rule, which searches with the kernel's gscore: leaves, masks and
     fresh are compared exactly in every round, gscore of the rows that backed a root up with the rule's own (rtol 1e-6 on
@@ -129,16 +138,21 @@ def assert_same_state(sp, rule, what=""):
     assert sp.buffer.plies.item() == rule.plies_max, what + " plies_max"
 
 
-@pytest.mark.parametrize("board,N,rounds,seed", MIXED_CASES)
+@pytest.mark.parametrize("board,N,rounds,seed", MIXED_RUNS)
 def test_mixed_budgets_equal_the_rule_round_by_round(hip, board, N, rounds, seed):
     m, n, k = board
     assert N % 4  # a partial workgroup
-    out_dtype = torch.bfloat16 if board == (9, 9, 5) else torch.float32
-    rule = new_rule(board, N, seed)
-    sp = new_async(hip, board, N, seed, full=FULL, fast=FAST, full_prob=0.5, out_dtype=out_dtype, capacity=m * n,
-                   gumbel=CONSIDERED)
+    start, leaf_dtype, out_dtype, key_word = MIXED_HOW[board, N, rounds, seed]
+    leaf_dtype, out_dtype = getattr(torch, leaf_dtype), getattr(torch, out_dtype)
+    rule = new_rule(board, N, seed, start)
+    sp = new_async(hip, board, N, seed + 100 if key_word else seed, full=FULL, fast=FAST, full_prob=0.5,
+                   leaf_dtype=leaf_dtype, out_dtype=out_dtype, capacity=m * n, gumbel=CONSIDERED)
     sp.sampler.env_id0 = ENV_ID0
+    if key_word:  # the device word replaces the host's key
+        sp.sampler.seed_dev = torch.tensor([seed], dtype=torch.int64, device=DEV)
+    load_start(sp, board, start)
     assert sp.full_threshold == THRESHOLD and sp.gscore.shape == (N, m * n) and sp.vroot.shape == (N,)
+    assert sp.leaf_obs.dtype == leaf_dtype
     obs, mask = rule.view()
     full_seen, fast_seen, worst, _, _ = follow(sp, rule, rounds, obs, mask)
     print(f"{board}: {full_seen} full and {fast_seen} fast records, largest difference of a count {worst}")

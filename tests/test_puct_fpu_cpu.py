@@ -2,12 +2,16 @@
 and ``mnk_search_selfplay_advance_keep_fpu`` (header, binding, host checks that reject before anything is enqueued), the
 argument checks of ``PUCTSearchPolicy(fpu=...)``, ``SearchSelfPlay`` and ``AsyncSearchSelfPlay`` before the GPU is touched,
 and the numpy restatement (tests/puct_fpu_rule.py) on its own: that it is ``SolverPuct`` with ``fpu=None``, what the rule
-is for, that ``fpu=0`` is not ``fpu=None``, and the clamp at -1."""
+is for, that ``fpu=0`` is not ``fpu=None``, and the clamp at -1; and the cases of
+tests/test_gpu_search_selfplay_async_fpu.py (tests/search_selfplay_async_fpu_cases.py) under the rule alone: each shows what
+it is there for."""
 import re
 
 import numpy as np
 import pytest
 
+import search_selfplay_async_fpu_cases as async_cases
+from oracle.packing import record_words
 from player_cases import HEADER, check_header_and_binding, lib  # noqa: F401 (lib: the fixture)
 from puct_fpu_rule import FpuPuct, as_pair, mass_of, untried_q
 from puct_rule import _Tree
@@ -205,3 +209,35 @@ def test_the_mass_and_the_clamp():
     assert untried_q(tree, 0, seen, as_pair((0.0, 64.0))) == np.float32(-1.0)  # clamped
     assert untried_q(tree, 0, seen, as_pair(3.0e38)) == np.float32(-1.0)
     assert untried_q(tree, 0, np.array([], np.float32), as_pair(3.0e38)) == np.float32(-0.5)  # nothing visited: no reduction
+
+
+# ----------------------------------------------------------------------------- the cases of the per-row GPU tests
+# (the rule gives, per case: games, fast / full records, row plies, plies ended by proof, carried plies that kept more
+# than one node, noised roots -- printed below)
+@pytest.mark.parametrize("case", range(len(async_cases.CASES)))
+def test_every_per_row_case_uses_every_option_it_turns_on(case):
+    rule = async_cases.mixed_run(case)
+    by_proof, kept_many, noised = async_cases.conditions(rule)
+    print(f"{async_cases.CASES[case][0]}: games {rule.stats[0]}, fast / full records {rule.fast_records} / "
+          f"{rule.full_records}, row plies {rule.row_plies.tolist()}, by proof {by_proof}, kept more than one node "
+          f"{kept_many}, noised / plain roots {rule.noised_roots} / {rule.plain_roots}")
+    async_cases.assert_every_option_was_used(case, rule)
+
+
+def test_both_per_row_entry_points_run_on_every_kind_of_board():
+    """(words per plane, n, k) of the built-in rows a case runs in, (words, 0, 0) for a generic form: with ``keep_tree``
+    the entry point is ``mnk_search_selfplay_advance_keep_fpu``, without it ``..._opts_fpu``"""
+    builtin = {(1, 3, 3), (3, 9, 5), (6, 13, 5), (8, 15, 5), (12, 19, 5)}  # (MNK_BUILTIN_BOARDS of csrc/mnk_emit.h)
+
+    def kind(board):
+        m, n, k = board
+        row = (record_words(m, n), n, k)
+        return row if row in builtin else (row[0], 0, 0)
+
+    for keep in (False, True):
+        kinds = {kind(c[0]) for c in async_cases.CASES if c[7] == keep}
+        assert kinds == builtin | {(5, 0, 0), (2, 0, 0)}, (keep, kinds)
+    # the solver, the noise and a tree cut to keep_nodes each run on a multi-word built-in and on a generic form
+    for option in (5, 6):
+        kinds = {kind(c[0]) for c in async_cases.CASES if c[option]}
+        assert any(w > 3 and n for w, n, _ in kinds) and any(w > 1 and not n for w, n, _ in kinds), option

@@ -9,15 +9,33 @@ import re
 import numpy as np
 import pytest
 
+from oracle.packing import record_words
 from player_cases import HEADER, check_header_and_binding, lib  # noqa: F401 (lib: the fixture)
 from puct_gumbel_rule import GumbelSelfPlayRule, gumbel_puct, schedule
 from search_selfplay_async_gumbel_rule import AsyncGumbelRule
+from search_selfplay_async_keep_cases import start_state
 from search_selfplay_async_rule import exact_np
 
 # what the GPU tests share with this file: the mixed budgets (a fast budget below `considered`: the fast table's rows are
-# a truncated first round of Sequential Halving), the row id of row 0, and the cases (board, rows, rounds, seed)
+# a truncated first round of Sequential Halving), the row id of row 0, and the cases: board, rows, rounds, seed, start
+# ("golden": a stored env state near the end of games, tests/golden/search_selfplay_async_starts.npz), and what only the
+# device reads -- leaf dtype, dtype of priors and values, device key word.  The first three are indexed below; the others
+# put the entry point on every kind of board it is compiled for: 12x13x5, 16x15x5 (C = 240: the plane fills its last word)
+# and 19x19x5 (C = 361: no multiple of four, so the draw's row stride is not C, and six trips of a per-cell loop) are
+# siblings of or the built-in variants <6,13,5>, <8,15,5> and <12,19,5>, 12x12x5 is the generic form of five words and
+# 7x7x4 that of two, from the empty board for more than a lap of its ring.  The rule gives (games, full / fast records,
+# row plies) in test_every_case_records_fast_and_full_plies_and_leaves_the_rows_out_of_step's output.
 FULL, FAST, CONSIDERED, THRESHOLD, ENV_ID0 = 8, 3, 4, 2 ** 31, 3
-MIXED_CASES = [((3, 3, 3), 7, 130, 6), ((4, 6, 3), 5, 200, 6), ((9, 9, 5), 5, 150, 6)]
+MIXED_CASES = [
+    ((3, 3, 3), 7, 130, 6, None, "float32", "float32", False),
+    ((4, 6, 3), 5, 200, 6, None, "float32", "float32", False),
+    ((9, 9, 5), 5, 150, 6, None, "float32", "bfloat16", False),
+    ((12, 13, 5), 5, 150, 6, "golden", "bfloat16", "float32", False),
+    ((16, 15, 5), 5, 150, 6, "golden", "float32", "bfloat16", False),
+    ((19, 19, 5), 3, 150, 6, "golden", "uint8", "float32", False),
+    ((12, 12, 5), 3, 150, 6, "golden", "float32", "float32", True),
+    ((7, 7, 4), 5, 500, 6, None, "uint8", "bfloat16", True),
+]
 
 
 # ----------------------------------------------------------------------------- a. the entry point
@@ -114,10 +132,24 @@ def test_with_every_ply_full_the_rule_is_the_lockstep_gumbel_rule(board, N, P):
 
 
 # ----------------------------------------------------------------------------- e. the GPU tests' seeds and shapes
-@functools.lru_cache(maxsize=None)
-def mixed_run(board, N, rounds, seed):
+MIXED_RUNS = [case[:4] for case in MIXED_CASES]               # what the tests are parametrized by,
+MIXED_HOW = {case[:4]: case[4:] for case in MIXED_CASES}       # and the rest of a case by it
+assert len(MIXED_HOW) == len(MIXED_CASES)
+
+
+def new_rule(board, N, seed, start=None, T=None, env_id0=ENV_ID0):
     m, n, k = board
-    rule = AsyncGumbelRule(m, n, k, N, m * n, FULL, FAST, THRESHOLD, 1.25, seed, CONSIDERED, env_id0=ENV_ID0)
+    rule = AsyncGumbelRule(m, n, k, N, T or m * n, FULL, FAST, THRESHOLD, 1.25, seed, CONSIDERED, env_id0=env_id0)
+    state = start_state(board, start)
+    if state is not None:
+        rule.load(*state)
+        rule.begin()
+    return rule
+
+
+@functools.lru_cache(maxsize=None)
+def mixed_run(board, N, rounds, seed, start=None, *read_on_the_device):
+    rule = new_rule(board, N, seed, start)
     ev = exact_np(rule.C)
     obs, mask = rule.view()
     for _ in range(rounds):
@@ -133,10 +165,15 @@ def test_the_fast_table_is_a_truncated_first_round_of_sequential_halving():
     assert fast[2].tolist() == [0, 0, 1] and fast[1].tolist() == [0, 1, 2]
 
 
-@pytest.mark.parametrize("board,N,rounds,seed", MIXED_CASES)
+@pytest.mark.parametrize("board,N,rounds,seed", MIXED_RUNS)
 def test_every_case_records_fast_and_full_plies_and_leaves_the_rows_out_of_step(board, N, rounds, seed):
-    rule = mixed_run(board, N, rounds, seed)
+    start = MIXED_HOW[board, N, rounds, seed][0]
+    rule = mixed_run(board, N, rounds, seed, *MIXED_HOW[board, N, rounds, seed])
+    print(f"{board}: games {rule.stats[0]}, full / fast records {rule.full_records} / {rule.fast_records}, row plies "
+          f"{rule.row_plies.tolist()}")
     assert not rule.errors and N % 4
+    if (board, start) != ((9, 9, 5), None):  # (150 launches from the empty 9x9 board end no game: every other case does)
+        assert rule.stats[0] > 0
     assert rule.full_records > 0 and rule.fast_records > 0
     assert len(set(rule.row_plies.tolist())) > 1
     assert any(e["full"] for e in rule.log) and any(not e["full"] for e in rule.log)
@@ -158,3 +195,18 @@ def test_the_cases_together_reach_every_branch():
     assert mid.row_plies.min() > mid.C and mid.stats[0] > 0  # and on a generic board
     large = mixed_run(*MIXED_CASES[2])
     assert large.row_plies.min() > 8  # several plies of every row on the flagship board
+
+
+def test_the_new_boards_are_one_of_every_kind_and_every_dtype_is_read():
+    """the boards of MIXED_CASES[3:] by the form that runs them (the built-in rows of MNK_DISPATCH are <1,3,3>, <3,9,5>,
+    <6,13,5>, <8,15,5> and <12,19,5>: 32-bit words per plane, columns, k; any other board takes the generic form of its
+    word count), and what the device reads and writes spread over them"""
+    new = MIXED_CASES[3:]
+    assert [(record_words(b[0], b[1]), b[1], b[2]) for b, *_ in new[:3]] == [(6, 13, 5), (8, 15, 5), (12, 19, 5)]
+    assert [record_words(b[0], b[1]) for b, *_ in new[3:]] == [5, 2]
+    assert 16 * (15 + 1) % 32 == 0 and 19 * 19 % 4  # rows of n + 1 bits fill the last word; a row stride that is not C
+    assert ((19, 19, 5), "uint8") in {(c[0], c[5]) for c in new}  # 361-byte leaf rows at odd offsets
+    assert "bfloat16" in {c[5] for c in new} and "bfloat16" in {c[6] for c in new} and True in {c[7] for c in new}
+    assert all(c[4] == "golden" for c in new[:4]) and new[4][4] is None
+    small = mixed_run(*new[4])
+    assert small.row_plies.min() > small.C  # from the empty board: more than a lap of the ring (T = C)
