@@ -5,10 +5,25 @@
 // carries the subtree of the position that was reached into the next search.  The *_leaves entry points run the same
 // search with L leaves per row and evaluation (a round = L backups, then L selections under virtual visits), so the
 // evaluator sees I / L + 1 batches of N * L rows.  mnk_puct_step_solver is mnk_puct_step_leaves with exact proofs of wins,
-// draws and losses in the backup (a 2-bit proof per node, propagated up the leaf's path).  The rule: include/mnk_hip.h.
+// draws and losses in the backup (a 2-bit proof per node, propagated up the leaf's path), mnk_puct_step_fpu either of them
+// with first-play urgency, mnk_puct_step_gumbel mnk_puct_step with a Gumbel root.  The rule: include/mnk_hip.h.
+//
+// What is here: one begin kernel and one rebase kernel (an entry point without `leaves` launches them with 1: the layout of
+// one leaf is the layout without the argument); the moves; ONE body of a step, puct_step_row, which the six step kernels
+// instantiate -- k_puct_step and k_puct_step_gumbel with one leaf and the walk without virtual visits,
+// k_puct_step_leaves<SOLVER, FPU> as the round -- around the pieces of mnk_puct_tree.h; and the host side: one argument
+// block, one check of it, one launch shape.
 #include "mnk_host.h"
 #include "mnk_wave_rows.h"
 #include "mnk_puct_tree.h"
+
+// what every kernel here begins with: one wave per row, MNK_PUCT_ROWS rows per workgroup; row i, the wave's stage `pos`
+#define MNK_PUCT_WAVE_ROW(N)                                       \
+  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];              \
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;      \
+  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;    \
+  if (i >= (N)) return;                                            \
+  uint32_t* pos = lds_pos[wave];
 
 // ------------------------------------------------------------------ evaluation 0: the roots
 // row i of obs into guard-column bit planes in LDS (pos[2 * NW], the wave's own); returns its stone count
@@ -53,24 +68,10 @@ __device__ __forceinline__ void puct_begin_row(const MnkGeom& g, const void* obs
 
 template <int NW, int CN, int CK>
 __global__ void __launch_bounds__(256)
-k_puct_begin(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, unsigned char* ws, void* leaf_obs,
-             int leaf_dtype, uint8_t* leaf_mask) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  puct_begin_row<NW, CN>(g, obs, obs_dtype, i, I, 1, ws, leaf_obs, leaf_dtype, leaf_mask, lds_pos[wave], lane);
-}
-
-template <int NW, int CN, int CK>
-__global__ void __launch_bounds__(256)
 k_puct_begin_leaves(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int leaves, unsigned char* ws,
                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  puct_begin_row<NW, CN>(g, obs, obs_dtype, i, I, leaves, ws, leaf_obs, leaf_dtype, leaf_mask, lds_pos[wave], lane);
+  MNK_PUCT_WAVE_ROW(N)
+  puct_begin_row<NW, CN>(g, obs, obs_dtype, i, I, leaves, ws, leaf_obs, leaf_dtype, leaf_mask, pos, lane);
 }
 
 // ------------------------------------------------------------------ evaluation 0 of a search that keeps its tree
@@ -90,7 +91,7 @@ __device__ __forceinline__ void puct_rebase_row(const MnkGeom& g, const void* ob
   const uint32_t* root = (const uint32_t*)(row + L.root);
   MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
   uint16_t* child = (uint16_t*)(row + L.child);
-  // (clamped, as in k_puct_step: whatever the workspace holds, no id leaves the row)
+  // (clamped, as in puct_header: whatever the workspace holds, no id leaves the row)
   const int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
   const bool live = hdr[3] != 0u;
 
@@ -143,7 +144,7 @@ __device__ __forceinline__ void puct_rebase_row(const MnkGeom& g, const void* ob
     }
   }
 
-  if (plies < 0) {  // exactly what k_puct_begin writes
+  if (plies < 0) {  // exactly what k_puct_begin_leaves writes
     puct_row_fresh<NW>(row, L, pos, NWg, stones < C, lane);
     if (carried && lane == 0) {
       carried[2 * i] = 0;
@@ -159,73 +160,82 @@ __device__ __forceinline__ void puct_rebase_row(const MnkGeom& g, const void* ob
   puct_row_void_slots<NW, CN>(g, row, L, pos, i, leaves, leaf_obs, leaf_dtype, leaf_mask, lane);
 }
 
-#define MNK_PUCT_REBASE_LDS                                                                                      \
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];                                                            \
-  __shared__ uint32_t lds_new[MNK_PUCT_ROWS][2 * NW]; /* the stones the row has and the stored root has not */ \
-  __shared__ uint16_t lds_map[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];                                            \
-  __shared__ uint16_t lds_inv[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];
-
-template <int NW, int CN, int CK>
-__global__ void __launch_bounds__(256)
-k_puct_rebase(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int keep, unsigned char* ws, void* leaf_obs,
-              int leaf_dtype, uint8_t* leaf_mask, int32_t* carried) {
-  MNK_PUCT_REBASE_LDS
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  puct_rebase_row<NW, CN>(g, obs, obs_dtype, i, I, keep, 1, ws, leaf_obs, leaf_dtype, leaf_mask, carried, lds_pos[wave],
-                          lds_new[wave], lds_map[wave], lds_inv[wave], lane);
-}
-
 template <int NW, int CN, int CK>
 __global__ void __launch_bounds__(256)
 k_puct_rebase_leaves(MnkGeom g, const void* obs, int obs_dtype, int64_t N, int I, int keep, int leaves, unsigned char* ws,
                      void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried) {
-  MNK_PUCT_REBASE_LDS
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  puct_rebase_row<NW, CN>(g, obs, obs_dtype, i, I, keep, leaves, ws, leaf_obs, leaf_dtype, leaf_mask, carried,
-                          lds_pos[wave], lds_new[wave], lds_map[wave], lds_inv[wave], lane);
+  MNK_PUCT_WAVE_ROW(N)
+  __shared__ uint32_t lds_new[MNK_PUCT_ROWS][2 * NW];  // the stones the row has and the stored root has not
+  __shared__ uint16_t lds_map[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];
+  __shared__ uint16_t lds_inv[MNK_PUCT_ROWS][MNK_PUCT_ITERS_MAX + 2];
+  puct_rebase_row<NW, CN>(g, obs, obs_dtype, i, I, keep, leaves, ws, leaf_obs, leaf_dtype, leaf_mask, carried, pos,
+                          lds_new[wave], lds_map[wave], lds_inv[wave], lane);
 }
 
-// ------------------------------------------------------------------ one backup, then one selection (or the move)
+// ------------------------------------------------------------------ a step: the argument block
+// What every step kernel takes, as its first parameter; a kernel's own parameters follow it.  leaves: 1 from an entry
+// point without the argument.  temperature: 0 from mnk_puct_step_gumbel, which has none.
+struct MnkPuctStepArgs {
+  MnkGeom g;
+  unsigned char* ws;
+  int64_t N;
+  int I, leaves;
+  const void* priors;
+  int priors_dtype;
+  const void* values;
+  int values_dtype;
+  float c;
+  int last, temperature;
+  uint64_t seed;
+  const uint64_t* seed_dev;
+  uint64_t step;
+  const uint64_t* step_dev;
+  int64_t env_id0;
+  int deterministic;
+  void* leaf_obs;
+  int leaf_dtype;
+  uint8_t* leaf_mask;
+  int64_t* actions;
+  int32_t* visits;
+  float* root_value;
+};
+
+// ------------------------------------------------------------------ the move
+// the draw of row i's move (0: deterministic)
+__device__ __forceinline__ uint32_t puct_move_draw(const MnkPuctStepArgs& a, int64_t i) {
+  const uint64_t step = a.step_dev ? a.step + *a.step_dev : a.step, seed = a.seed_dev ? *a.seed_dev : a.seed;
+  return a.deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(a.env_id0 + i), step, MNK_STREAM_SAMPLE);
+}
 
 // The move, the visits, the root value of row i, after its last backup.
 // SOLVER: the counts are the adjusted ones (`keep`: 0 = every child's n, 1 = the WIN children's, 2 = all but the LOSS
 // children's), a proven root's value is exact, and `proof` takes the root's proof for its side to move.
-template <bool SOLVER = false>
-__device__ __forceinline__ void puct_move(int C, const MnkPuctNode* node, const uint16_t* child, int nodes, bool live,
-                                          int temperature, uint64_t seed, const uint64_t* seed_dev, uint64_t step,
-                                          const uint64_t* step_dev, int64_t env_id0, int deterministic, int64_t i,
-                                          int64_t* actions, int32_t* visits, float* root_value, int lane,
-                                          int8_t* proof = nullptr) {
-  if (step_dev) step += *step_dev;
-  if (seed_dev) seed = *seed_dev;
-  const uint32_t x = deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(env_id0 + i), step, MNK_STREAM_SAMPLE);
+template <bool SOLVER>
+__device__ __forceinline__ void puct_move(const MnkPuctStepArgs& a, const MnkPuctNode* node, const uint16_t* child,
+                                          int nodes, bool live, int64_t i, int lane, int8_t* proof) {
+  const int C = a.g.C;
+  const bool sample = a.temperature == 1 && !a.deterministic;
+  const uint32_t x = puct_move_draw(a, i);
+  int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells
+  uint32_t maxn = 0u, tot = 0u;
   if constexpr (SOLVER) {
-    auto count = [&](int a, int keep) { return puct_kept_count(puct_root_kid(C, node, child, nodes, live, a), keep); };
-    uint32_t maxn = 0u, tot = 0u;
+    auto count = [&](int q, int keep) { return puct_kept_count(puct_root_kid(C, node, child, nodes, live, q), keep); };
     const int keep = puct_root_keep(C, node, child, nodes, live, lane, maxn, tot);
-    if (visits)
-      for (int a = lane; a < C; a += 64) visits[i * C + a] = (int32_t)count(a, keep);
-    int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells
-    if (maxn)
-      mnk_pick_by_visits(C, x, temperature == 1 && !deterministic, maxn, tot, lane, [&](int a) { return count(a, keep); },
-                         move);
+    if (a.visits)
+      for (int q = lane; q < C; q += 64) a.visits[i * C + q] = (int32_t)count(q, keep);
+    if (maxn) mnk_pick_by_visits(C, x, sample, maxn, tot, lane, [&](int q) { return count(q, keep); }, move);
     if (lane == 0) {
       const uint32_t pf = MNK_PUCT_PROOF(node[0].info);  // from the view of the side that is NOT to move
-      actions[i] = move;
-      if (root_value) root_value[i] = pf ? (float)((int)pf - 2) : __fdiv_rn(-node[0].w, (float)node[0].n);
+      a.actions[i] = move;
+      if (a.root_value) a.root_value[i] = pf ? (float)((int)pf - 2) : __fdiv_rn(-node[0].w, (float)node[0].n);
       if (proof) proof[i] = pf ? (int8_t)((int)pf - 2) : (int8_t)MNK_PROOF_UNKNOWN;
     }
     return;
   }
-  uint32_t maxn = 0u, tot = 0u;
-  for (int a = lane; a < C; a += 64) {
-    const uint32_t ch = live ? child[a] : MNK_PUCT_NONE;
+  for (int q = lane; q < C; q += 64) {
+    const uint32_t ch = live ? child[q] : MNK_PUCT_NONE;
     const uint32_t na = (ch != 0u && ch != MNK_PUCT_NONE) ? node[min((int)ch, nodes - 1)].n : 0u;
-    if (visits) visits[i * C + a] = (int32_t)na;
+    if (a.visits) a.visits[i * C + q] = (int32_t)na;
     maxn = max(maxn, na);
     tot += na;
   }
@@ -234,582 +244,166 @@ __device__ __forceinline__ void puct_move(int C, const MnkPuctNode* node, const 
     maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
     tot += (uint32_t)__shfl_xor((int)tot, off, 64);
   }
-  int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells
   if (maxn)
-    mnk_pick_by_visits(C, x, temperature == 1 && !deterministic, maxn, tot, lane, [&](int a) {
-      const uint32_t ch = a < C ? child[a] : 0u;
+    mnk_pick_by_visits(C, x, sample, maxn, tot, lane, [&](int q) {
+      const uint32_t ch = q < C ? child[q] : 0u;
       return (ch != 0u && ch != MNK_PUCT_NONE) ? node[min((int)ch, nodes - 1)].n : 0u;
     }, move);
   if (lane == 0) {
-    actions[i] = move;
-    if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
+    a.actions[i] = move;
+    if (a.root_value) a.root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
   }
 }
 
-// a sum over the wave, the same value in every lane
-__device__ __forceinline__ double puct_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-
-// The move, the visits, the root value and the improved policy of row i, after its last backup (the rule:
-// include/mnk_hip.h, mnk_puct_step_gumbel).  The policy is f64: five passes over the root's cells (the sum of the clamped
-// priors; the visited cells' sums for v_mix; the maximum of y; the sum of exp(y - max); the store), every pass
-// recomputing a cell's terms from the tree -- the same operations on the same inputs give the same y each time -- and
-// reduced over the wave.  pr = the root's stored priors (node 0's row).
-__device__ __forceinline__ void puct_move_gumbel(int C, int I, const MnkPuctNode* node, const float* pr, const uint16_t* cl,
-                                                 int nodes, bool live, const MnkPuctGumbel& gm, float vroot, uint64_t seed,
-                                                 const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev,
-                                                 int64_t env_id0, int deterministic, int64_t i, int64_t* actions,
-                                                 int32_t* visits, float* root_value, float* policy, int lane) {
-  if (!live) {  // no legal cell: the draw over all C cells of mnk_puct_step, no visits, no policy
-    if (step_dev) step += *step_dev;
-    if (seed_dev) seed = *seed_dev;
-    const uint32_t x = deterministic ? 0u : mnk_rand_u32(seed, (uint64_t)(env_id0 + i), step, MNK_STREAM_SAMPLE);
-    for (int a = lane; a < C; a += 64) {
-      if (visits) visits[i * C + a] = 0;
-      if (policy) policy[i * C + a] = 0.0f;
-    }
-    if (lane == 0) {
-      actions[i] = (int)__umulhi(x, (uint32_t)C);
-      if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
-    }
-    return;
-  }
+// The move, the visits, the root value and the improved policy (puct_gumbel_policy, mnk_puct_tree.h) of row i, after its
+// last backup (the rule: include/mnk_hip.h, mnk_puct_step_gumbel).  pr = the root's stored priors (node 0's row), cl its
+// child row.
+__device__ __forceinline__ void puct_move_gumbel(const MnkPuctStepArgs& a, const MnkPuctNode* node, const float* pr,
+                                                 const uint16_t* cl, int nodes, bool live, const MnkPuctGumbel& gm,
+                                                 const float* vroot, float* policy, int64_t i, int lane) {
+  const int C = a.g.C;
   uint32_t maxn = 0u;
-  const int move = puct_gumbel_pick<true>(C, I, node, cl, nodes, gm, lane, &maxn);
+  // no legal cell: the draw over all C cells of mnk_puct_step, no visits, no policy
+  const int move = live ? puct_gumbel_pick<true>(C, a.I, node, cl, nodes, gm, lane, &maxn)
+                        : (int)__umulhi(puct_move_draw(a, i), (uint32_t)C);
   if (lane == 0) {
-    actions[i] = move == 0x7fffffff ? 0 : move;
-    if (root_value) root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
+    a.actions[i] = move == 0x7fffffff ? 0 : move;
+    if (a.root_value) a.root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
   }
-  if (!visits && !policy) return;
-  // a free cell's clamped prior, visit count and q (0 where it has no visit)
-  auto cell = [&](int a, double& p, uint32_t& na, double& q) {
-    const uint32_t ch = cl[a];
-    if (ch == MNK_PUCT_NONE) return false;
-    const float pa = pr[a];
-    p = (double)(pa > 0x1p-126f ? pa : 0x1p-126f);
-    na = 0u;
-    q = 0.0;
-    if (ch) {
-      const MnkPuctNode k = node[min((int)ch, nodes - 1)];
-      na = k.n;
-      if (na) q = (double)__fdiv_rn(k.w, (float)na);
+  if (a.visits)
+    for (int q = lane; q < C; q += 64) {
+      const uint32_t ch = live ? cl[q] : MNK_PUCT_NONE;
+      a.visits[i * C + q] = (ch != 0u && ch != MNK_PUCT_NONE) ? (int32_t)node[min((int)ch, nodes - 1)].n : 0;
     }
-    return true;
-  };
-  double p, q, sp = 0.0;
-  uint32_t na, ns = 0u;
-  for (int a = lane; a < C; a += 64) {
-    const bool fr = cell(a, p, na, q);
-    if (visits) visits[i * C + a] = fr ? (int32_t)na : 0;
-    if (fr) {
-      sp += p;
-      ns += na;
-    }
-  }
   if (!policy) return;
-  sp = puct_wave_sum(sp);
-#pragma unroll
-  for (int off = 32; off; off >>= 1) ns += (uint32_t)__shfl_xor((int)ns, off, 64);
-  double sv = 0.0, sq = 0.0;
-  for (int a = lane; a < C; a += 64)
-    if (cell(a, p, na, q) && na) {
-      sv += p / sp;
-      sq += p / sp * q;
-    }
-  sv = puct_wave_sum(sv);
-  sq = puct_wave_sum(sq);
-  const double vmix = sv > 0.0 ? ((double)vroot + (double)ns * sq / sv) / (1.0 + (double)ns) : (double)vroot;
-  const double K = ((double)gm.c_visit + (double)maxn) * (double)gm.c_scale;
-  auto y_of = [&](int a, double& y) {
-    if (!cell(a, p, na, q)) return false;
-    y = log(p) + K * (na ? q : vmix);
-    return true;
-  };
-  double y, my = -INFINITY;
-  for (int a = lane; a < C; a += 64)
-    if (y_of(a, y)) my = fmax(my, y);
-#pragma unroll
-  for (int off = 32; off; off >>= 1) my = fmax(my, __shfl_xor(my, off, 64));
-  double se = 0.0;
-  for (int a = lane; a < C; a += 64)
-    if (y_of(a, y)) se += exp(y - my);
-  se = puct_wave_sum(se);
-  for (int a = lane; a < C; a += 64) policy[i * C + a] = y_of(a, y) ? (float)(exp(y - my) / se) : 0.0f;
+  if (live)
+    puct_gumbel_policy(C, node, pr, cl, nodes, gm, vroot[i], maxn, lane, [&](int q, float p) { policy[i * C + q] = p; });
+  else
+    for (int q = lane; q < C; q += 64) policy[i * C + q] = 0.0f;
 }
 
-// One wave per row, MNK_PUCT_ROWS rows per workgroup.  Selection is wave-uniform: the position in registers, the scores
-// of a node's C cells spread over the lanes and reduced to the maximum, ties to the lowest cell.
-template <int NW, int CN, int CK>
-__global__ void __launch_bounds__(256)
-k_puct_step(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, int priors_dtype, const void* values,
-            int values_dtype, float c, int last, int temperature, uint64_t seed, const uint64_t* seed_dev, uint64_t step,
-            const uint64_t* step_dev, int64_t env_id0, int deterministic, void* leaf_obs, int leaf_dtype,
-            uint8_t* leaf_mask, int64_t* actions, int32_t* visits, float* root_value) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  const int C = g.C, NWg = g.NW;
-  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I);
-  unsigned char* row = ws + i * L.row;
-  uint32_t* hdr = (uint32_t*)row;
-  const uint32_t* root = (const uint32_t*)(row + L.root);
-  uint32_t* leafp = (uint32_t*)(row + L.leaf);
-  uint16_t* path = (uint16_t*)(row + L.path);
-  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
-  float* prior = (float*)(row + L.prior);
-  uint16_t* child = (uint16_t*)(row + L.child);
-  uint32_t* pos = lds_pos[wave];
-  // (clamped: a workspace that mnk_puct_begin did not set up cannot send a store outside the row)
-  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
-  const int depth = (int)min(hdr[1], (uint32_t)I);
-  const uint32_t state = hdr[2];
-  const bool live = hdr[3] != 0u;
-  for (int q = lane; q < 2 * NW; q += 64) {
-    const int pl = q >= NW, w = q - (pl ? NW : 0);
-    pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
-  }
-  row_wave_sync();
-
-  // ---- backup of the pending evaluation
-  if (state & 1u)
-    puct_backup<NW, CN>(g, pos, path, node, prior, child, nodes, depth, state, priors, priors_dtype, values, values_dtype,
-                        i, lane);
-
-  if (last) {
-    puct_move(C, node, child, nodes, live, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, i, actions,
-              visits, root_value, lane);
-    return;
-  }
-
-  // ---- selection
-  int d = 0;
-  uint32_t nstate = 0u;  // nothing pending: a row without a legal cell (or a full tree) shows its root again
-  if (live && nodes <= I) {
-    MnkEnv<NW> e;
-    puct_env_root<NW>(e, root, NWg);
-    nstate = puct_walk<NW, CN, CK, false>(g, e, I, c, node, prior, child, path, nodes, d, lane);
-    if (nstate == 0u) d = 0;
-    if (lane == 0) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
-        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
-      }
-    }
-  } else if (lane == 0) {
-    for (int q = 0; q < 2 * NW; ++q) {
-      const int pl = q >= NW, w = q - (pl ? NW : 0);
-      pos[q] = w < NWg ? root[pl * NWg + w] : 0u;
-    }
-  }
-  if (lane == 0) {
-    path[0] = 0;
-    hdr[0] = (uint32_t)nodes;
-    hdr[1] = (uint32_t)d;
-    hdr[2] = nstate;
-  }
-  row_wave_sync();
-  for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
-  row_write_view<NW, CN>(g, pos, d & 1, i, leaf_obs, leaf_dtype, leaf_mask, lane);
-}
-
-// ------------------------------------------------------------------ a round: `leaves` backups, then `leaves` selections
-// One wave per row as above.  Slot j of row i is batch row i * leaves + j.  The backups run in slot order with a wave
-// sync between them (paths share nodes), each lane-parallel over its path.  Then the slots select one after the other,
-// each under the virtual visits of the slots before it (puct_walk<VL>), and every slot's leaf is written out as soon as
-// it is known: planes through the wave's LDS stage, the one part of a slot that every lane reads.  The paths stay in the
-// workspace (at the maxima 4 rows x 16 slots x 2 050 u16 exceed the CU's LDS); a walk reads one entry per earlier slot and
-// node.  A slot without a leaf is void (state 0, the root's view), and so is every slot after it: nothing has changed
-// that its walk could see.
-template <int NW, int CN, int CK>
-__global__ void __launch_bounds__(256)
-k_puct_step_leaves(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, const void* priors, int priors_dtype,
-                   const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
-                   const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
-                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
-                   float* root_value) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  const int C = g.C, NWg = g.NW;
-  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, leaves);
-  unsigned char* row = ws + i * L.row;
-  uint32_t* hdr = (uint32_t*)row;
-  const uint32_t* root = (const uint32_t*)(row + L.root);
-  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
-  float* prior = (float*)(row + L.prior);
-  uint16_t* child = (uint16_t*)(row + L.child);
-  uint32_t* pos = lds_pos[wave];
-  // slot j's {depth, state}, leaf planes and path (slot 0: the header's, `leaf`, `path`)
-  auto slot_ds = [&](int j) { return j ? (uint32_t*)(row + L.xhdr) + 2 * (j - 1) : hdr + 1; };
-  auto slot_leaf = [&](int j) { return (uint32_t*)(row + (j ? L.xleaf + 8 * (int64_t)NWg * (j - 1) : L.leaf)); };
-  auto slot_path = [&](int j) { return (uint16_t*)(row + (j ? L.xpath + L.pstride * (j - 1) : L.path)); };
-  // (clamped: a workspace that mnk_puct_begin_leaves did not set up cannot send a store outside the row)
-  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
-  const bool live = hdr[3] != 0u;
+// ------------------------------------------------------------------ a step of row i
+// One wave per row.  `leaves` backups, then the move (a.last) or `leaves` selections; slot j of row i is batch row
+// i * leaves + j.  The backups run in slot order with a wave sync between them (paths share nodes), each lane-parallel
+// over its path.  Selection is wave-uniform: the position in registers, the scores of a node's C cells spread over the
+// lanes and reduced to the maximum, ties to the lowest cell.  The slots select one after the other, each (VL) under the
+// virtual visits of the slots before it, and every slot's leaf is written out as soon as it is known: planes through the
+// wave's LDS stage, the one part of a slot that every lane reads.  The paths stay in the workspace (at the maxima 4 rows x
+// 16 slots x 2 050 u16 exceed the CU's LDS); a walk reads one entry per earlier slot and node.  A slot without a leaf -- a
+// row without a legal cell, a full tree, a walk that ends in a node of this round -- is void (state 0, the root's view),
+// and so is every slot after it: nothing has changed that its walk could see.
+// The flags are puct_walk's, puct_backup's and the move's:
+//   VL      the round.  Without it `leaves` is the constant 1 and the walk is the one without virtual visits.
+//   SOLVER  the backups prove what they can along their paths, and a root that is proven selects nothing (its slots are
+//           void, as those of a full tree).  The rule: mnk_puct_step_solver.
+//   FPU     a free cell without a visit scores from its parent's own mean value (fpu below the root, fpu_root at it).  The
+//           rule: mnk_puct_step_fpu.
+//   GUMBEL  the root's part of the walk is puct_gumbel_pick (gm: the row's Gumbel inputs).  The rule: mnk_puct_step_gumbel.
+// move(r, nodes, live): the kernel's move on a.last.
+template <int NW, int CN, int CK, bool VL, bool SOLVER, bool FPU, bool GUMBEL, class Move>
+__device__ __forceinline__ void puct_step_row(const MnkPuctStepArgs& a, int leaves, int64_t i, uint32_t* pos, int lane,
+                                              Move move, float fpu = 0.0f, float fpu_root = 0.0f,
+                                              const MnkPuctGumbel* gm = nullptr) {
+  const int C = a.g.C, NWg = a.g.NW, I = a.I;
+  const MnkPuctRow r = puct_row(a.ws, i, NWg, C, I, leaves);
+  const MnkPuctHeader h = puct_header(r.hdr, I);  // (nodes and live; depth and state are a slot's)
+  int nodes = h.nodes;
 
   // ---- the backups of the pending evaluations, in slot order
   for (int j = 0; j < leaves; ++j) {
-    const uint32_t* ds = slot_ds(j);
+    const uint32_t* ds = puct_slot_ds(r, j);
     const int depth = (int)min(ds[0], (uint32_t)I);
     const uint32_t state = ds[1];
     if (!(state & 1u)) continue;
-    const uint32_t* leafp = slot_leaf(j);
-    for (int q = lane; q < 2 * NW; q += 64) {
-      const int pl = q >= NW, w = q - (pl ? NW : 0);
-      pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
-    }
+    puct_stage_planes<NW>(pos, puct_slot_leaf(r, j, NWg), NWg, lane);
     row_wave_sync();
-    puct_backup<NW, CN>(g, pos, slot_path(j), node, prior, child, nodes, depth, state, priors, priors_dtype, values,
-                        values_dtype, i * leaves + j, lane);
+    puct_backup<NW, CN, SOLVER>(a.g, pos, puct_slot_path(r, j), r.node, r.prior, r.child, nodes, depth, state, a.priors,
+                                a.priors_dtype, a.values, a.values_dtype, i * leaves + j, lane);
   }
 
-  if (last) {
-    puct_move(C, node, child, nodes, live, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, i, actions,
-              visits, root_value, lane);
+  if (a.last) {
+    move(r, nodes, h.live);
     return;
   }
 
   // ---- the selections
   const int nodes0 = nodes;
-  const uint16_t* epath = slot_path(min(lane, leaves - 1));  // lane l < leaves: slot l's path
-  int edepth = 0;                                            // and, once it has selected, its leaf's depth
-  uint32_t active = 0u;                                      // the slots of this round that have a leaf
-  bool open = live;                                          // no slot was void yet
-  for (int j = 0; j < leaves; ++j) {
-    int d = 0;
-    uint32_t nstate = 0u;
-    uint16_t* path = slot_path(j);
-    MnkEnv<NW> e;
-    if (open && nodes <= I) {
-      puct_env_root<NW>(e, root, NWg);
-      nstate = puct_walk<NW, CN, CK, true>(g, e, I, c, node, prior, child, path, nodes, d, lane, nodes0, active, epath,
-                                           edepth);
-    }
-    if (nstate) {
-      active |= 1u << j;
-      if (lane == j) edepth = d;
-    } else {
-      d = 0;
-      open = false;
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
-        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
-      }
-      path[0] = 0;
-      uint32_t* ds = slot_ds(j);
-      ds[0] = (uint32_t)d;
-      ds[1] = nstate;
-    }
-    row_wave_sync();
-    uint32_t* leafp = slot_leaf(j);
-    for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
-    row_write_view<NW, CN>(g, pos, d & 1, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
-    row_wave_sync();  // (the next slot's walk reads this one's node, child entry and path; its write-out reuses pos)
-  }
-  if (lane == 0) hdr[0] = (uint32_t)nodes;
-}
-
-// ------------------------------------------------------------------ a round that proves wins, draws and losses
-// k_puct_step_leaves (for any number of leaves, 1 included) with the solver's parts of puct_backup, puct_walk and
-// puct_move compiled in: the backups prove what they can along their paths, a root that is proven selects nothing (its
-// slots are void, as those of a full tree), and the move is made from the adjusted counts.  The rule: include/mnk_hip.h,
-// mnk_puct_step_solver.
-template <int NW, int CN, int CK>
-__global__ void __launch_bounds__(256)
-k_puct_step_solver(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, const void* priors, int priors_dtype,
-                   const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
-                   const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
-                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
-                   float* root_value, int8_t* proof) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  const int C = g.C, NWg = g.NW;
-  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, leaves);
-  unsigned char* row = ws + i * L.row;
-  uint32_t* hdr = (uint32_t*)row;
-  const uint32_t* root = (const uint32_t*)(row + L.root);
-  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
-  float* prior = (float*)(row + L.prior);
-  uint16_t* child = (uint16_t*)(row + L.child);
-  uint32_t* pos = lds_pos[wave];
-  // slot j's {depth, state}, leaf planes and path (slot 0: the header's, `leaf`, `path`)
-  auto slot_ds = [&](int j) { return j ? (uint32_t*)(row + L.xhdr) + 2 * (j - 1) : hdr + 1; };
-  auto slot_leaf = [&](int j) { return (uint32_t*)(row + (j ? L.xleaf + 8 * (int64_t)NWg * (j - 1) : L.leaf)); };
-  auto slot_path = [&](int j) { return (uint16_t*)(row + (j ? L.xpath + L.pstride * (j - 1) : L.path)); };
-  // (clamped: a workspace that mnk_puct_begin_leaves did not set up cannot send a store outside the row)
-  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
-  const bool live = hdr[3] != 0u;
-
-  // ---- the backups of the pending evaluations, in slot order
-  for (int j = 0; j < leaves; ++j) {
-    const uint32_t* ds = slot_ds(j);
-    const int depth = (int)min(ds[0], (uint32_t)I);
-    const uint32_t state = ds[1];
-    if (!(state & 1u)) continue;
-    const uint32_t* leafp = slot_leaf(j);
-    for (int q = lane; q < 2 * NW; q += 64) {
-      const int pl = q >= NW, w = q - (pl ? NW : 0);
-      pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
-    }
-    row_wave_sync();
-    puct_backup<NW, CN, true>(g, pos, slot_path(j), node, prior, child, nodes, depth, state, priors, priors_dtype, values,
-                              values_dtype, i * leaves + j, lane);
-  }
-
-  if (last) {
-    puct_move<true>(C, node, child, nodes, live, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, i,
-                    actions, visits, root_value, lane, proof);
-    return;
-  }
-
-  // ---- the selections
-  const int nodes0 = nodes;
-  const uint16_t* epath = slot_path(min(lane, leaves - 1));  // lane l < leaves: slot l's path
-  int edepth = 0;                                            // and, once it has selected, its leaf's depth
-  uint32_t active = 0u;                                      // the slots of this round that have a leaf
-  bool open = live;                                          // no slot was void yet
-  if (MNK_PUCT_PROOF(node[0].info)) open = false;            // a proven root: nothing left to search
-  for (int j = 0; j < leaves; ++j) {
-    int d = 0;
-    uint32_t nstate = 0u;
-    uint16_t* path = slot_path(j);
-    MnkEnv<NW> e;
-    if (open && nodes <= I) {
-      puct_env_root<NW>(e, root, NWg);
-      nstate = puct_walk<NW, CN, CK, true, true>(g, e, I, c, node, prior, child, path, nodes, d, lane, nodes0, active,
-                                                 epath, edepth);
-    }
-    if (nstate) {
-      active |= 1u << j;
-      if (lane == j) edepth = d;
-    } else {
-      d = 0;
-      open = false;
-    }
-    if (lane == 0) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
-        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
-      }
-      path[0] = 0;
-      uint32_t* ds = slot_ds(j);
-      ds[0] = (uint32_t)d;
-      ds[1] = nstate;
-    }
-    row_wave_sync();
-    uint32_t* leafp = slot_leaf(j);
-    for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
-    row_write_view<NW, CN>(g, pos, d & 1, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
-    row_wave_sync();  // (the next slot's walk reads this one's node, child entry and path; its write-out reuses pos)
-  }
-  if (lane == 0) hdr[0] = (uint32_t)nodes;
-}
-
-// ------------------------------------------------------------------ a round with first-play urgency
-// k_puct_step_leaves (SOLVER: k_puct_step_solver) with the first-play urgency of puct_walk compiled in: a free cell
-// without a visit scores from its parent's own mean value, less a reduction that grows with the prior mass already
-// visited, in the place of q = 0.  The backups, the move and the slots are those kernels'; proof is read with SOLVER
-// only.  The rule: include/mnk_hip.h, mnk_puct_step_fpu.
-template <int NW, int CN, int CK, bool SOLVER>
-__global__ void __launch_bounds__(256)
-k_puct_step_fpu(MnkGeom g, unsigned char* ws, int64_t N, int I, int leaves, const void* priors, int priors_dtype,
-                const void* values, int values_dtype, float c, int last, int temperature, uint64_t seed,
-                const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
-                void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits, float* root_value,
-                int8_t* proof, float fpu, float fpu_root) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  const int C = g.C, NWg = g.NW;
-  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, leaves);
-  unsigned char* row = ws + i * L.row;
-  uint32_t* hdr = (uint32_t*)row;
-  const uint32_t* root = (const uint32_t*)(row + L.root);
-  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
-  float* prior = (float*)(row + L.prior);
-  uint16_t* child = (uint16_t*)(row + L.child);
-  uint32_t* pos = lds_pos[wave];
-  // slot j's {depth, state}, leaf planes and path (slot 0: the header's, `leaf`, `path`)
-  auto slot_ds = [&](int j) { return j ? (uint32_t*)(row + L.xhdr) + 2 * (j - 1) : hdr + 1; };
-  auto slot_leaf = [&](int j) { return (uint32_t*)(row + (j ? L.xleaf + 8 * (int64_t)NWg * (j - 1) : L.leaf)); };
-  auto slot_path = [&](int j) { return (uint16_t*)(row + (j ? L.xpath + L.pstride * (j - 1) : L.path)); };
-  // (clamped: a workspace that mnk_puct_begin_leaves did not set up cannot send a store outside the row)
-  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
-  const bool live = hdr[3] != 0u;
-
-  // ---- the backups of the pending evaluations, in slot order
-  for (int j = 0; j < leaves; ++j) {
-    const uint32_t* ds = slot_ds(j);
-    const int depth = (int)min(ds[0], (uint32_t)I);
-    const uint32_t state = ds[1];
-    if (!(state & 1u)) continue;
-    const uint32_t* leafp = slot_leaf(j);
-    for (int q = lane; q < 2 * NW; q += 64) {
-      const int pl = q >= NW, w = q - (pl ? NW : 0);
-      pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
-    }
-    row_wave_sync();
-    puct_backup<NW, CN, SOLVER>(g, pos, slot_path(j), node, prior, child, nodes, depth, state, priors, priors_dtype, values,
-                                values_dtype, i * leaves + j, lane);
-  }
-
-  if (last) {
-    puct_move<SOLVER>(C, node, child, nodes, live, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, i,
-                      actions, visits, root_value, lane, proof);
-    return;
-  }
-
-  // ---- the selections
-  const int nodes0 = nodes;
-  const uint16_t* epath = slot_path(min(lane, leaves - 1));  // lane l < leaves: slot l's path
-  int edepth = 0;                                            // and, once it has selected, its leaf's depth
-  uint32_t active = 0u;                                      // the slots of this round that have a leaf
-  bool open = live;                                          // no slot was void yet
+  const uint16_t* epath = puct_slot_path(r, min(lane, leaves - 1));  // lane l < leaves: slot l's path
+  int edepth = 0;                                                    // and, once it has selected, its leaf's depth
+  uint32_t active = 0u;                                              // the slots of this round that have a leaf
+  bool open = h.live;                                                // no slot was void yet
   if constexpr (SOLVER)
-    if (MNK_PUCT_PROOF(node[0].info)) open = false;  // a proven root: nothing left to search
+    if (MNK_PUCT_PROOF(r.node[0].info)) open = false;  // a proven root: nothing left to search
   for (int j = 0; j < leaves; ++j) {
     int d = 0;
     uint32_t nstate = 0u;
-    uint16_t* path = slot_path(j);
+    uint16_t* path = puct_slot_path(r, j);
     MnkEnv<NW> e;
     if (open && nodes <= I) {
-      puct_env_root<NW>(e, root, NWg);
-      nstate = puct_walk<NW, CN, CK, true, SOLVER, false, true>(g, e, I, c, node, prior, child, path, nodes, d, lane, nodes0,
-                                                                active, epath, edepth, nullptr, fpu, fpu_root);
+      puct_env_root<NW>(e, r.root, NWg);
+      nstate = puct_walk<NW, CN, CK, VL, SOLVER, GUMBEL, FPU>(a.g, e, I, a.c, r.node, r.prior, r.child, path, nodes, d,
+                                                              lane, nodes0, active, epath, edepth, gm, fpu, fpu_root);
     }
     if (nstate) {
       active |= 1u << j;
       if (lane == j) edepth = d;
+      puct_stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
     } else {
       d = 0;
       open = false;
+      puct_stage_planes<NW>(pos, r.root, NWg, lane);  // (a void slot shows the root)
     }
-    if (lane == 0) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
-        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
-      }
-      path[0] = 0;
-      uint32_t* ds = slot_ds(j);
-      ds[0] = (uint32_t)d;
-      ds[1] = nstate;
-    }
-    row_wave_sync();
-    uint32_t* leafp = slot_leaf(j);
-    for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
-    row_write_view<NW, CN>(g, pos, d & 1, i * leaves + j, leaf_obs, leaf_dtype, leaf_mask, lane);
-    row_wave_sync();  // (the next slot's walk reads this one's node, child entry and path; its write-out reuses pos)
+    puct_store_selection<NW, CN>(a.g, pos, nstate, d, path, puct_slot_ds(r, j), puct_slot_leaf(r, j, NWg), i * leaves + j,
+                                 a.leaf_obs, a.leaf_dtype, a.leaf_mask, lane);
+    // (the next slot's walk reads this one's node, child entry and path; its write-out reuses pos)
+    if constexpr (VL) row_wave_sync();
   }
-  if (lane == 0) hdr[0] = (uint32_t)nodes;
+  if (lane == 0) r.hdr[0] = (uint32_t)nodes;
 }
 
-// ------------------------------------------------------------------ a step whose root is a Gumbel root
-// k_puct_step (one leaf per row and evaluation, the same workspace) with the root's part of puct_walk replaced by
-// puct_gumbel_pick and puct_move by puct_move_gumbel; below the root the walk and the backup are k_puct_step's.  The
-// rule: include/mnk_hip.h, mnk_puct_step_gumbel.
+// one leaf per row and evaluation
+template <int NW, int CN, int CK>
+__global__ void __launch_bounds__(256) k_puct_step(MnkPuctStepArgs a) {
+  MNK_PUCT_WAVE_ROW(a.N)
+  puct_step_row<NW, CN, CK, false, false, false, false>(a, 1, i, pos, lane, [&](const MnkPuctRow& r, int nodes, bool live) {
+    puct_move<false>(a, r.node, r.child, nodes, live, i, lane, nullptr);
+  });
+}
+
+// the round; proof is read with SOLVER only, fpu and fpu_root with FPU
+template <int NW, int CN, int CK, bool SOLVER, bool FPU>
+__global__ void __launch_bounds__(256) k_puct_step_leaves(MnkPuctStepArgs a, int8_t* proof, float fpu, float fpu_root) {
+  MNK_PUCT_WAVE_ROW(a.N)
+  auto move = [&](const MnkPuctRow& r, int nodes, bool live) {
+    puct_move<SOLVER>(a, r.node, r.child, nodes, live, i, lane, proof);
+  };
+  puct_step_row<NW, CN, CK, true, SOLVER, FPU, false>(a, a.leaves, i, pos, lane, move, fpu, fpu_root);
+}
+
+// one leaf, the root a Gumbel root (the same workspace as k_puct_step's)
 template <int NW, int CN, int CK>
 __global__ void __launch_bounds__(256)
-k_puct_step_gumbel(MnkGeom g, unsigned char* ws, int64_t N, int I, const void* priors, int priors_dtype, const void* values,
-                   int values_dtype, float c, int last, int considered, float c_visit, float c_scale,
-                   const uint16_t* table, const float* gscore, const float* vroot, uint64_t seed, const uint64_t* seed_dev,
-                   uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic, void* leaf_obs,
-                   int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits, float* root_value,
-                   float* policy) {
-  __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-  const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
-  if (i >= N) return;
-  const int C = g.C, NWg = g.NW;
-  const MnkPuctLayout L = mnk_puct_layout(NWg, C, I, 1);
-  unsigned char* row = ws + i * L.row;
-  uint32_t* hdr = (uint32_t*)row;
-  const uint32_t* root = (const uint32_t*)(row + L.root);
-  uint32_t* leafp = (uint32_t*)(row + L.leaf);
-  uint16_t* path = (uint16_t*)(row + L.path);
-  MnkPuctNode* node = (MnkPuctNode*)(row + L.node);
-  float* prior = (float*)(row + L.prior);
-  uint16_t* child = (uint16_t*)(row + L.child);
-  uint32_t* pos = lds_pos[wave];
-  // (clamped: a workspace that mnk_puct_begin_leaves did not set up cannot send a store outside the row)
-  int nodes = (int)min(hdr[0], (uint32_t)(I + 1));
-  const int depth = (int)min(hdr[1], (uint32_t)I);
-  const uint32_t state = hdr[2];
-  const bool live = hdr[3] != 0u;
-  for (int q = lane; q < 2 * NW; q += 64) {
-    const int pl = q >= NW, w = q - (pl ? NW : 0);
-    pos[q] = w < NWg ? leafp[pl * NWg + w] : 0u;
-  }
-  row_wave_sync();
-  MnkPuctGumbel gm;
-  gm.gs = gscore + i * C;
-  gm.table = table;
-  gm.considered = considered;
-  gm.c_visit = c_visit;
-  gm.c_scale = c_scale;
-
-  // ---- backup of the pending evaluation
-  if (state & 1u)
-    puct_backup<NW, CN>(g, pos, path, node, prior, child, nodes, depth, state, priors, priors_dtype, values, values_dtype,
-                        i, lane);
-
-  if (last) {
-    puct_move_gumbel(C, I, node, prior, child, nodes, live, gm, policy ? vroot[i] : 0.0f, seed, seed_dev, step, step_dev,
-                     env_id0, deterministic, i, actions, visits, root_value, policy, lane);
-    return;
-  }
-
-  // ---- selection
-  int d = 0;
-  uint32_t nstate = 0u;  // nothing pending: a row without a legal cell (or a full tree) shows its root again
-  if (live && nodes <= I) {
-    MnkEnv<NW> e;
-    puct_env_root<NW>(e, root, NWg);
-    nstate = puct_walk<NW, CN, CK, false, false, true>(g, e, I, c, node, prior, child, path, nodes, d, lane, 0, 0u, nullptr,
-                                                       0, &gm);
-    if (nstate == 0u) d = 0;
-    if (lane == 0) {
-#pragma unroll
-      for (int w = 0; w < NW; ++w) {
-        pos[w] = nstate ? e.p[0][w] : (w < NWg ? root[w] : 0u);
-        pos[NW + w] = nstate ? e.p[1][w] : (w < NWg ? root[NWg + w] : 0u);
-      }
-    }
-  } else if (lane == 0) {
-    for (int q = 0; q < 2 * NW; ++q) {
-      const int pl = q >= NW, w = q - (pl ? NW : 0);
-      pos[q] = w < NWg ? root[pl * NWg + w] : 0u;
-    }
-  }
-  if (lane == 0) {
-    path[0] = 0;
-    hdr[0] = (uint32_t)nodes;
-    hdr[1] = (uint32_t)d;
-    hdr[2] = nstate;
-  }
-  row_wave_sync();
-  for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
-  row_write_view<NW, CN>(g, pos, d & 1, i, leaf_obs, leaf_dtype, leaf_mask, lane);
+k_puct_step_gumbel(MnkPuctStepArgs a, int considered, float c_visit, float c_scale, const uint16_t* table,
+                   const float* gscore, const float* vroot, float* policy) {
+  MNK_PUCT_WAVE_ROW(a.N)
+  const MnkPuctGumbel gm{gscore + i * a.g.C, table, considered, c_visit, c_scale};
+  puct_step_row<NW, CN, CK, false, false, false, true>(a, 1, i, pos, lane, [&](const MnkPuctRow& r, int nodes, bool live) {
+    puct_move_gumbel(a, r.node, r.prior, r.child, nodes, live, gm, vroot, policy, i, lane);
+  }, 0.0f, 0.0f, &gm);
 }
 
 // ------------------------------------------------------------------ the entry points
-// what the four pairs of entry points share: the host checks (before anything is enqueued) and the launch.  leaves = 0
-// stands for the entry point without the argument: today's kernels, one leaf.
+// what the pairs of entry points share: the host checks (before anything is enqueued) and the launch.  leaves = 0 stands
+// for the entry point without the argument: one leaf.
 static bool puct_leaves_ok(int iterations, int leaves) {
   return leaves == 0 || (leaves >= 1 && leaves <= MNK_PUCT_LEAVES_MAX && iterations % leaves == 0);
+}
+
+// the one launch shape (N > 0): one wave per row, MNK_PUCT_ROWS rows per workgroup
+template <typename... P, typename... A>
+static void puct_launch(void (*kernel)(P...), int64_t N, void* stream, const A&... args) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), dim3(64 * MNK_PUCT_ROWS), 0,
+                     (hipStream_t)stream, args...);
 }
 
 static int64_t puct_workspace_bytes(int64_t N, int m, int n, int iterations, int leaves) {
@@ -820,23 +414,27 @@ static int64_t puct_workspace_bytes(int64_t N, int m, int n, int iterations, int
   return N * mnk_puct_layout(g.NW, g.C, iterations, leaves ? leaves : 1).row;
 }
 
+// what mnk_puct_begin* and mnk_puct_rebase* refuse alike: the board's code, else MNK_EINVAL
+static int puct_roots_check(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, int leaves,
+                            void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, MnkGeom* g) {
+  const int rc = mnk_check_geom(m, n, k, g);
+  if (rc != MNK_OK) return rc;
+  if (!obs || !workspace || !leaf_obs || !leaf_mask || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS ||
+      !mnk_obs_dtype_ok(obs_dtype) || !mnk_obs_dtype_ok(leaf_dtype) || iterations < 1 || iterations > MNK_PUCT_ITERS_MAX ||
+      !puct_leaves_ok(iterations, leaves))
+    return MNK_EINVAL;
+  return MNK_OK;
+}
+
 static int puct_begin(const void* obs, int obs_dtype, int64_t N, int m, int n, int k, int iterations, int leaves,
                       void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, void* stream) {
   MnkGeom g;
-  const int rc = mnk_check_geom(m, n, k, &g);
+  const int rc =
+      puct_roots_check(obs, obs_dtype, N, m, n, k, iterations, leaves, workspace, leaf_obs, leaf_dtype, leaf_mask, &g);
   if (rc != MNK_OK) return rc;
-  if (!obs || !workspace || !leaf_obs || !leaf_mask || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS || !mnk_obs_dtype_ok(obs_dtype) ||
-      !mnk_obs_dtype_ok(leaf_dtype) || iterations < 1 || iterations > MNK_PUCT_ITERS_MAX || !puct_leaves_ok(iterations, leaves))
-    return MNK_EINVAL;
   if (N == 0) return MNK_OK;
-  const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
-  hipStream_t s = (hipStream_t)stream;
-  if (leaves)
-    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_begin_leaves), grid, block, 0, s, g, obs, obs_dtype, N, iterations,
-                                       leaves, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask));
-  else
-    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_begin), grid, block, 0, s, g, obs, obs_dtype, N, iterations,
-                                       (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask));
+  MNK_DISPATCH(g, puct_launch(MNK_K(k_puct_begin_leaves), N, stream, g, obs, obs_dtype, N, iterations, leaves ? leaves : 1,
+                              (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask));
   return mnk_launch_status(leaves ? "puct_begin_leaves" : "puct_begin");
 }
 
@@ -844,32 +442,29 @@ static int puct_rebase(const void* obs, int obs_dtype, int64_t N, int m, int n, 
                        int leaves, void* workspace, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int32_t* carried,
                        void* stream) {
   MnkGeom g;
-  const int rc = mnk_check_geom(m, n, k, &g);
+  const int rc = puct_roots_check(obs, obs_dtype, N, m, n, k, tree_iterations, leaves, workspace, leaf_obs, leaf_dtype,
+                                  leaf_mask, &g);
   if (rc != MNK_OK) return rc;
   // (at least one round's room: keep_nodes <= tree_iterations + 1 - J, J >= leaves)
-  if (!obs || !workspace || !leaf_obs || !leaf_mask || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS || !mnk_obs_dtype_ok(obs_dtype) ||
-      !mnk_obs_dtype_ok(leaf_dtype) || tree_iterations < 1 || tree_iterations > MNK_PUCT_ITERS_MAX ||
-      !puct_leaves_ok(tree_iterations, leaves) || keep_nodes < 1 || keep_nodes > tree_iterations + 1 - (leaves ? leaves : 1))
-    return MNK_EINVAL;
+  if (keep_nodes < 1 || keep_nodes > tree_iterations + 1 - (leaves ? leaves : 1)) return MNK_EINVAL;
   if (N == 0) return MNK_OK;
-  const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
-  hipStream_t s = (hipStream_t)stream;
-  if (leaves)
-    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_rebase_leaves), grid, block, 0, s, g, obs, obs_dtype, N, tree_iterations,
-                                       keep_nodes, leaves, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask,
-                                       carried));
-  else
-    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_rebase), grid, block, 0, s, g, obs, obs_dtype, N, tree_iterations,
-                                       keep_nodes, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask, carried));
+  MNK_DISPATCH(g, puct_launch(MNK_K(k_puct_rebase_leaves), N, stream, g, obs, obs_dtype, N, tree_iterations, keep_nodes,
+                              leaves ? leaves : 1, (unsigned char*)workspace, leaf_obs, leaf_dtype, leaf_mask, carried));
   return mnk_launch_status(leaves ? "puct_rebase_leaves" : "puct_rebase");
 }
 
-static int puct_step(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
-                     int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
-                     uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
-                     int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
-                     int32_t* visits, float* root_value, void* stream, bool solver = false, int8_t* proof = nullptr,
-                     bool with_fpu = false, float fpu = 0.0f, float fpu_root = 0.0f) {
+// the common arguments of a step's C entry point, under the names the public header gives them in every one, for
+// puct_step_check; LEAVES / TEMPERATURE: the entry point's, or 0 where it has none
+#define MNK_PUCT_STEP_COMMON(LEAVES, TEMPERATURE)                                                                          \
+  workspace, N, m, n, k, iterations, LEAVES, priors, priors_dtype, values, values_dtype, c, last, TEMPERATURE, seed,       \
+      seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions, visits, root_value
+
+// What every step entry point refuses: the board's code, else MNK_EINVAL.  MNK_OK: `a` is filled.
+static int puct_step_check(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                           int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                           uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev,
+                           int64_t env_id0, int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask,
+                           int64_t* actions, int32_t* visits, float* root_value, MnkPuctStepArgs* a) {
   MnkGeom g;
   const int rc = mnk_check_geom(m, n, k, &g);
   if (rc != MNK_OK) return rc;
@@ -880,38 +475,25 @@ static int puct_step(void* workspace, int64_t N, int m, int n, int k, int iterat
       (temperature != 0 && temperature != 1) || !puct_leaves_ok(iterations, leaves))
     return MNK_EINVAL;
   if (last ? !actions : (!leaf_obs || !leaf_mask || !mnk_obs_dtype_ok(leaf_dtype))) return MNK_EINVAL;
+  *a = MnkPuctStepArgs{g, (unsigned char*)workspace, N, iterations, leaves ? leaves : 1, priors, priors_dtype, values,
+                       values_dtype, c, last, temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs,
+                       leaf_dtype, leaf_mask, actions, visits, root_value};
+  return MNK_OK;
+}
+
+// the round's launch: which of the four instantiations
+static int puct_step_round(const MnkPuctStepArgs& a, bool solver, bool with_fpu, int8_t* proof, float fpu, float fpu_root,
+                           void* stream, const char* what) {
   if (with_fpu && (!(fpu >= 0.0f && fpu <= 3.0e38f) || !(fpu_root >= 0.0f && fpu_root <= 3.0e38f))) return MNK_EINVAL;
-  if (N == 0) return MNK_OK;
-  const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
-  hipStream_t s = (hipStream_t)stream;
-#define MNK_PUCT_STEP_FPU(SOLVER)                                                                                        \
-  MNK_DISPATCH(g, hipLaunchKernelGGL(HIP_KERNEL_NAME(k_puct_step_fpu<NW, CN, CK, SOLVER>), grid, block, 0, s, g,         \
-                                     (unsigned char*)workspace, N, iterations, leaves, priors, priors_dtype, values,     \
-                                     values_dtype, c, last, temperature, seed, seed_dev, step, step_dev, env_id0,        \
-                                     deterministic, leaf_obs, leaf_dtype, leaf_mask, actions, visits, root_value, proof, \
-                                     fpu, fpu_root))
-  if (with_fpu) {
-    if (solver) MNK_PUCT_STEP_FPU(true);
-    else MNK_PUCT_STEP_FPU(false);
-    return mnk_launch_status("puct_step_fpu");
-  }
-#undef MNK_PUCT_STEP_FPU
-  if (solver)
-    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step_solver), grid, block, 0, s, g, (unsigned char*)workspace, N,
-                                       iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
-                                       temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs,
-                                       leaf_dtype, leaf_mask, actions, visits, root_value, proof));
-  else if (leaves)
-    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step_leaves), grid, block, 0, s, g, (unsigned char*)workspace, N,
-                                       iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
-                                       temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs,
-                                       leaf_dtype, leaf_mask, actions, visits, root_value));
-  else
-    MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step), grid, block, 0, s, g, (unsigned char*)workspace, N, iterations,
-                                       priors, priors_dtype, values, values_dtype, c, last, temperature, seed, seed_dev,
-                                       step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions,
-                                       visits, root_value));
-  return mnk_launch_status(solver ? "puct_step_solver" : leaves ? "puct_step_leaves" : "puct_step");
+  if (a.N == 0) return MNK_OK;
+#define MNK_PUCT_ROUND(SOLVER, FPU) \
+  MNK_DISPATCH(a.g, puct_launch(k_puct_step_leaves<NW, CN, CK, SOLVER, FPU>, a.N, stream, a, proof, fpu, fpu_root))
+  if (solver && with_fpu) MNK_PUCT_ROUND(true, true);
+  else if (with_fpu) MNK_PUCT_ROUND(false, true);
+  else if (solver) MNK_PUCT_ROUND(true, false);
+  else MNK_PUCT_ROUND(false, false);
+#undef MNK_PUCT_ROUND
+  return mnk_launch_status(what);
 }
 
 extern "C" {
@@ -951,29 +533,29 @@ int mnk_puct_step(void* workspace, int64_t N, int m, int n, int k, int iteration
                   const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0, int deterministic,
                   void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions, int32_t* visits,
                   float* root_value, void* stream) {
-  return puct_step(workspace, N, m, n, k, iterations, 0, priors, priors_dtype, values, values_dtype, c, last, temperature,
-                   seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions, visits,
-                   root_value, stream);
+  MnkPuctStepArgs a;
+  const int rc = puct_step_check(MNK_PUCT_STEP_COMMON(0, temperature), &a);
+  if (rc != MNK_OK || N == 0) return rc;
+  MNK_DISPATCH(a.g, puct_launch(MNK_K(k_puct_step), N, stream, a));
+  return mnk_launch_status("puct_step");
 }
 int mnk_puct_step_leaves(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
                          int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
                          uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                          int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                          int32_t* visits, float* root_value, void* stream) {
-  if (!leaves) return MNK_EINVAL;
-  return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
-                   temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
-                   actions, visits, root_value, stream);
+  MnkPuctStepArgs a;
+  const int rc = leaves ? puct_step_check(MNK_PUCT_STEP_COMMON(leaves, temperature), &a) : MNK_EINVAL;
+  return rc != MNK_OK ? rc : puct_step_round(a, false, false, nullptr, 0.0f, 0.0f, stream, "puct_step_leaves");
 }
 int mnk_puct_step_solver(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
                          int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
                          uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                          int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                          int32_t* visits, float* root_value, int8_t* proof, void* stream) {
-  if (!leaves) return MNK_EINVAL;
-  return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
-                   temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
-                   actions, visits, root_value, stream, true, proof);
+  MnkPuctStepArgs a;
+  const int rc = leaves ? puct_step_check(MNK_PUCT_STEP_COMMON(leaves, temperature), &a) : MNK_EINVAL;
+  return rc != MNK_OK ? rc : puct_step_round(a, true, false, proof, 0.0f, 0.0f, stream, "puct_step_solver");
 }
 
 int mnk_puct_step_fpu(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
@@ -982,10 +564,11 @@ int mnk_puct_step_fpu(void* workspace, int64_t N, int m, int n, int k, int itera
                       int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                       int32_t* visits, float* root_value, int8_t* proof, int solver, float fpu, float fpu_root,
                       void* stream) {
-  if (!leaves || (solver != 0 && solver != 1)) return MNK_EINVAL;
-  return puct_step(workspace, N, m, n, k, iterations, leaves, priors, priors_dtype, values, values_dtype, c, last,
-                   temperature, seed, seed_dev, step, step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask,
-                   actions, visits, root_value, stream, solver != 0, solver ? proof : nullptr, true, fpu, fpu_root);
+  MnkPuctStepArgs a;
+  const int rc = leaves && (solver == 0 || solver == 1) ? puct_step_check(MNK_PUCT_STEP_COMMON(leaves, temperature), &a)
+                                                        : MNK_EINVAL;
+  if (rc != MNK_OK) return rc;
+  return puct_step_round(a, solver != 0, true, solver ? proof : nullptr, fpu, fpu_root, stream, "puct_step_fpu");
 }
 
 int mnk_puct_step_gumbel(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
@@ -994,25 +577,15 @@ int mnk_puct_step_gumbel(void* workspace, int64_t N, int m, int n, int k, int it
                          uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
                          int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                          int32_t* visits, float* root_value, float* policy, void* stream) {
-  MnkGeom g;
-  const int rc = mnk_check_geom(m, n, k, &g);
+  MnkPuctStepArgs a;
+  const int rc = puct_step_check(MNK_PUCT_STEP_COMMON(leaves, 0), &a);  // (the Gumbel root has no temperature)
   if (rc != MNK_OK) return rc;
-  const bool dt_ok = (priors_dtype == MNK_LOGITS_F32 || priors_dtype == MNK_LOGITS_BF16) &&
-                     (values_dtype == MNK_LOGITS_F32 || values_dtype == MNK_LOGITS_BF16);
-  if (!workspace || !priors || !values || N < 0 || N > (int64_t)0x7fffffff * MNK_PUCT_ROWS || !dt_ok || iterations < 1 ||
-      iterations > MNK_PUCT_ITERS_MAX || !(c >= 0.0f && c <= 3.0e38f) || (last != 0 && last != 1) || leaves != 1 ||
-      considered < 1 || considered > MNK_PUCT_CONSIDERED_MAX || !(c_visit >= 0.0f && c_visit <= 3.0e38f) ||
-      !(c_scale >= 0.0f && c_scale <= 3.0e38f) || !table || !gscore)
-    return MNK_EINVAL;
-  if (last ? (!actions || (policy && !vroot)) : (!leaf_obs || !leaf_mask || !mnk_obs_dtype_ok(leaf_dtype)))
+  if (leaves != 1 || considered < 1 || considered > MNK_PUCT_CONSIDERED_MAX || !(c_visit >= 0.0f && c_visit <= 3.0e38f) ||
+      !(c_scale >= 0.0f && c_scale <= 3.0e38f) || !table || !gscore || (last && policy && !vroot))
     return MNK_EINVAL;
   if (N == 0) return MNK_OK;
-  const dim3 grid((unsigned)((N + MNK_PUCT_ROWS - 1) / MNK_PUCT_ROWS)), block(64 * MNK_PUCT_ROWS);
-  MNK_DISPATCH(g, hipLaunchKernelGGL(MNK_K(k_puct_step_gumbel), grid, block, 0, (hipStream_t)stream, g,
-                                     (unsigned char*)workspace, N, iterations, priors, priors_dtype, values, values_dtype, c,
-                                     last, considered, c_visit, c_scale, table, gscore, vroot, seed, seed_dev, step,
-                                     step_dev, env_id0, deterministic, leaf_obs, leaf_dtype, leaf_mask, actions, visits,
-                                     root_value, policy));
+  MNK_DISPATCH(a.g, puct_launch(MNK_K(k_puct_step_gumbel), N, stream, a, considered, c_visit, c_scale, table, gscore, vroot,
+                                policy));
   return mnk_launch_status("puct_step_gumbel");
 }
 

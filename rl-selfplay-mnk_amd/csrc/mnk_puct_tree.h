@@ -1,6 +1,8 @@
 // mnk_puct_tree.h -- the PUCT tree as device code shared by the kernels that search it (the PUCT player,
-// mnk_puct.hip, and search self-play with per-row budgets, mnk_search_selfplay_async.hip): the node record and the
-// workspace layout, a fresh row, the backup of one evaluation, the walk that selects the next leaf and the carry of a
+// mnk_puct.hip, and search self-play with per-row budgets, mnk_search_selfplay_async*.hip): the node record and the
+// workspace layout; a row's view of its workspace, its slots and its clamped header; the wave's LDS stage (packed planes
+// in, a selection's planes in, a selected slot out); a fresh row, the backup of one evaluation, the solver's root counts,
+// the Gumbel root's pick and improved policy, first-play urgency, the walk that selects the next leaf and the carry of a
 // subtree into the next search.  The rule: include/mnk_hip.h, mnk_puct_step and mnk_puct_rebase.
 #pragma once
 #include "mnk_wave_rows.h"
@@ -9,9 +11,9 @@
 struct MnkPuctNode {
   uint32_t n;
   float w;
-  uint32_t info;  // the move into the node | proof << 12 (k_puct_step_solver only; from w's point of view, 0: unknown,
+  uint32_t info;  // the move into the node | proof << 12 (the SOLVER kernels only; from w's point of view, 0: unknown,
                   // 1: WIN, 2: DRAW, 3: LOSS) | term << 16 (0: not terminal; 1: the move won; 2: it filled the board) |
-                  // the parent's id << 18 (what k_puct_rebase marks a subtree by; the root's is 0)
+                  // the parent's id << 18 (what k_puct_rebase_leaves marks a subtree by; the root's is 0)
 };
 #define MNK_PUCT_PROOF(info) (((info) >> 12) & 3u)
 #define MNK_PUCT_TERM(info) (((info) >> 16) & 3u)
@@ -21,7 +23,7 @@ static_assert(sizeof(MnkPuctNode) == 12, "node record");
 // The workspace of one row, at row * L.row bytes (every part 16-byte aligned, the row 256-byte aligned):
 //   header   u32[4]          nodes created, leaf depth, state (bit 0: a backup is pending; bits 1-2: the leaf's term, with
 //                            the solver its proof;
-//                            bit 3: the pending evaluation is of a root that k_puct_rebase carried over -- it only
+//                            bit 3: the pending evaluation is of a root that k_puct_rebase_leaves carried over -- it only
 //                            renews the root's priors), live (the root has a legal cell)
 //   root     u32[2][NWg]     the root's guard-column bit planes (plane 0 = the root's side to move), NWg = MnkGeom::NW
 //   leaf     u32[2][NWg]     the pending leaf's planes
@@ -125,6 +127,108 @@ __device__ __forceinline__ void puct_row_void_slots(const MnkGeom& g, unsigned c
   }
 }
 
+// ------------------------------------------------------------------ a row's view of its workspace
+// (what every kernel that steps a tree begins with; TI: the layout's iterations, the caller's)
+struct MnkPuctRow {
+  MnkPuctLayout L;
+  unsigned char* row;
+  uint32_t* hdr;
+  const uint32_t* root;
+  uint32_t* leaf;  // (slot 0's, as `path`)
+  uint16_t* path;
+  MnkPuctNode* node;
+  float* prior;
+  uint16_t* child;
+};
+__device__ __forceinline__ MnkPuctRow puct_row(unsigned char* ws, int64_t i, int NWg, int C, int TI, int leaves = 1) {
+  MnkPuctRow r;
+  r.L = mnk_puct_layout(NWg, C, TI, leaves);
+  r.row = ws + i * r.L.row;
+  r.hdr = (uint32_t*)r.row;
+  r.root = (const uint32_t*)(r.row + r.L.root);
+  r.leaf = (uint32_t*)(r.row + r.L.leaf);
+  r.path = (uint16_t*)(r.row + r.L.path);
+  r.node = (MnkPuctNode*)(r.row + r.L.node);
+  r.prior = (float*)(r.row + r.L.prior);
+  r.child = (uint16_t*)(r.row + r.L.child);
+  return r;
+}
+// slot j's {depth, state}, leaf planes and path (slot 0: the header's, `leaf`, `path`)
+__device__ __forceinline__ uint32_t* puct_slot_ds(const MnkPuctRow& r, int j) {
+  return j ? (uint32_t*)(r.row + r.L.xhdr) + 2 * (j - 1) : r.hdr + 1;
+}
+__device__ __forceinline__ uint32_t* puct_slot_leaf(const MnkPuctRow& r, int j, int NWg) {
+  return (uint32_t*)(r.row + (j ? r.L.xleaf + 8 * (int64_t)NWg * (j - 1) : r.L.leaf));
+}
+__device__ __forceinline__ uint16_t* puct_slot_path(const MnkPuctRow& r, int j) {
+  return (uint16_t*)(r.row + (j ? r.L.xpath + r.L.pstride * (j - 1) : r.L.path));
+}
+
+// The header, clamped by the layout's iterations: whatever the workspace holds, no id leaves the row and nodes - 1 is a
+// node.  (nodes >= 1 changes nothing for a workspace that mnk_puct_begin* / mnk_puct_rebase* set up -- the root is created
+// there and nodes never falls; it keeps `min(id, nodes - 1)` from going negative in one that nobody set up.)
+struct MnkPuctHeader {
+  int nodes, depth;
+  uint32_t state;
+  bool live;
+};
+__device__ __forceinline__ MnkPuctHeader puct_header(const uint32_t* hdr, int TI) {
+  MnkPuctHeader h;
+  h.nodes = (int)min(max(hdr[0], 1u), (uint32_t)(TI + 1));
+  h.depth = (int)min(hdr[1], (uint32_t)TI);
+  h.state = hdr[2];
+  h.live = hdr[3] != 0u;
+  return h;
+}
+
+// ------------------------------------------------------------------ the wave's stage
+// (pos: the wave's own 2 * NW words of LDS.  A piece that writes or reads pos says which row_wave_sync() its caller owes.)
+// packed planes of the workspace (a leaf's, the root's: u32[2][NWg]) into pos, padded to NW words a plane; every lane
+// calls it.  The caller owes a row_wave_sync() after it, and one before it when lanes may still read the stage.
+template <int NW>
+__device__ __forceinline__ void puct_stage_planes(uint32_t* pos, const uint32_t* src, int NWg, int lane) {
+  for (int q = lane; q < 2 * NW; q += 64) {
+    const int pl = q >= NW, w = q - (pl ? NW : 0);
+    pos[q] = w < NWg ? src[pl * NWg + w] : 0u;
+  }
+}
+
+// The planes a slot shows after a walk that started from e (so e is set up), by lane 0 into the stage: the walk's leaf, e,
+// when nstate != 0; else nothing is pending and the slot shows the root.  (A slot that no walk entered stages the root
+// with puct_stage_planes.)  e's words are read ahead of the choice: written as `nstate ? e.p[..] : root[..]` on a reference
+// the compiler selects between the two addresses, which costs the 19x19 kernels 5 VGPRs and 9 % more instructions.  The
+// caller owes a row_wave_sync() before it, when lanes may still read the stage; the one after it is
+// puct_store_selection's.
+template <int NW>
+__device__ __forceinline__ void puct_stage_selection(uint32_t* pos, const MnkEnv<NW>& e, uint32_t nstate,
+                                                     const uint32_t* root, int NWg, int lane) {
+  if (lane == 0) {
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+      const uint32_t l0 = e.p[0][w], l1 = e.p[1][w];
+      pos[w] = nstate ? l0 : (w < NWg ? root[w] : 0u);
+      pos[NW + w] = nstate ? l1 : (w < NWg ? root[NWg + w] : 0u);
+    }
+  }
+}
+
+// The slot's planes are staged (puct_stage_selection, or puct_stage_planes of the root): path[0] and the slot's {depth,
+// state} (ds) by lane 0, the sync, the planes to the workspace (leafp), the view as batch row b with parity d & 1.
+template <int NW, int CN>
+__device__ __forceinline__ void puct_store_selection(const MnkGeom& g, const uint32_t* pos, uint32_t nstate, int d,
+                                                     uint16_t* path, uint32_t* ds, uint32_t* leafp, int64_t b,
+                                                     void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int lane) {
+  const int NWg = g.NW;
+  if (lane == 0) {
+    path[0] = 0;
+    ds[0] = (uint32_t)d;
+    ds[1] = nstate;
+  }
+  row_wave_sync();
+  for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
+  row_write_view<NW, CN>(g, pos, d & 1, b, leaf_obs, leaf_dtype, leaf_mask, lane);
+}
+
 // The backup of one pending evaluation (state bit 0 set): batch row b of priors / values, the leaf's planes in pos (LDS).
 // SOLVER: the leaf's term is its proof (3: a proven loss of its mover, +1 for its side to move), and a proven leaf's
 // backup ends with the proofs of its path, leaf side first: one scan of a node's child row per level (the selection's
@@ -138,7 +242,7 @@ __device__ __forceinline__ void puct_backup(const MnkGeom& g, const uint32_t* po
   const int C = g.C;
   const int lf = min((int)path[depth], nodes - 1);
   const uint32_t term = (state >> 1) & 3u;
-  const bool renew = (state & 8u) != 0u;  // a carried root (k_puct_rebase): its priors again and nothing else
+  const bool renew = (state & 8u) != 0u;  // a carried root (k_puct_rebase_leaves): its priors again and nothing else
   float v;
   if (term) {
     v = term == 1u ? -1.0f : 0.0f;  // the mover into the leaf won: a loss for its side to move
@@ -315,6 +419,75 @@ __device__ __forceinline__ int puct_gumbel_pick(int C, int I, const MnkPuctNode*
     }
   }
   return __builtin_amdgcn_readfirstlane(ba != 0x7fffffff ? ba : aa);
+}
+
+// a sum over the wave, the same value in every lane
+__device__ __forceinline__ double puct_wave_sum(double x) {
+#pragma unroll
+  for (int off = 32; off; off >>= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
+
+// The improved policy of a Gumbel root after its last backup (the rule: include/mnk_hip.h, mnk_puct_step_gumbel); maxn is
+// puct_gumbel_pick<true>'s.  f64: five passes over the root's cells (the sum of the clamped priors; the visited cells'
+// sums for v_mix; the maximum of y; the sum of exp(y - max); the store), every pass recomputing a cell's terms from the
+// tree -- the same operations on the same inputs give the same y each time -- and reduced over the wave.  pr = the root's
+// stored priors (node 0's row), cl its child row.  store(a, policy_a) is called once for every cell a < C by the lane that
+// owns it (a = lane, lane + 64, ...), with 0 for an occupied cell.
+template <class Store>
+__device__ __forceinline__ void puct_gumbel_policy(int C, const MnkPuctNode* node, const float* pr, const uint16_t* cl,
+                                                   int nodes, const MnkPuctGumbel& gm, float vroot, uint32_t maxn, int lane,
+                                                   Store store) {
+  // a free cell's clamped prior, visit count and q (0 where it has no visit)
+  auto cell = [&](int a, double& p, uint32_t& na, double& q) {
+    const uint32_t ch = cl[a];
+    if (ch == MNK_PUCT_NONE) return false;
+    const float pa = pr[a];
+    p = (double)(pa > 0x1p-126f ? pa : 0x1p-126f);
+    na = 0u;
+    q = 0.0;
+    if (ch) {
+      const MnkPuctNode k = node[min((int)ch, nodes - 1)];
+      na = k.n;
+      if (na) q = (double)__fdiv_rn(k.w, (float)na);
+    }
+    return true;
+  };
+  double p, q, sp = 0.0;
+  uint32_t na, ns = 0u;
+  for (int a = lane; a < C; a += 64)
+    if (cell(a, p, na, q)) {
+      sp += p;
+      ns += na;
+    }
+  sp = puct_wave_sum(sp);
+#pragma unroll
+  for (int off = 32; off; off >>= 1) ns += (uint32_t)__shfl_xor((int)ns, off, 64);
+  double sv = 0.0, sq = 0.0;
+  for (int a = lane; a < C; a += 64)
+    if (cell(a, p, na, q) && na) {
+      sv += p / sp;
+      sq += p / sp * q;
+    }
+  sv = puct_wave_sum(sv);
+  sq = puct_wave_sum(sq);
+  const double vmix = sv > 0.0 ? ((double)vroot + (double)ns * sq / sv) / (1.0 + (double)ns) : (double)vroot;
+  const double K = ((double)gm.c_visit + (double)maxn) * (double)gm.c_scale;
+  auto y_of = [&](int a, double& y) {
+    if (!cell(a, p, na, q)) return false;
+    y = log(p) + K * (na ? q : vmix);
+    return true;
+  };
+  double y, my = -INFINITY;
+  for (int a = lane; a < C; a += 64)
+    if (y_of(a, y)) my = fmax(my, y);
+#pragma unroll
+  for (int off = 32; off; off >>= 1) my = fmax(my, __shfl_xor(my, off, 64));
+  double se = 0.0;
+  for (int a = lane; a < C; a += 64)
+    if (y_of(a, y)) se += exp(y - my);
+  se = puct_wave_sum(se);
+  for (int a = lane; a < C; a += 64) store(a, y_of(a, y) ? (float)(exp(y - my) / se) : 0.0f);
 }
 
 // ------------------------------------------------------------------ first-play urgency
@@ -495,7 +668,7 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
 //      be a lower lane's source), the prior and child rows B nodes at a time, a cell per lane.  new <= old, and a
 //      destination slot was itself moved or dropped before, so no second workspace is needed; a cell's column of the
 //      prior and child rows is only ever touched by the one lane that owns the cell.
-// Wave-uniform; returns kept (>= 1).  Shared by k_puct_rebase / k_puct_rebase_leaves (v = where the match ended) and
+// Wave-uniform; returns kept (>= 1).  Shared by k_puct_rebase_leaves (v = where the match ended) and
 // k_search_selfplay_advance_keep (v = the root's child through the move just played).
 template <int NW, int B = 8>
 __device__ __forceinline__ int puct_carry_subtree(int C, int NWg, unsigned char* row, const MnkPuctLayout& L,

@@ -1,13 +1,16 @@
 // mnk_search_selfplay_advance.h -- what the launches of search self-play with per-row budgets share (gfx950 / MI355X
-// only): the argument block, the host's check of it and the launch shape, and the steps of a row as device functions that
-// every advance kernel inlines -- k_search_selfplay_advance, _opts and _keep (mnk_search_selfplay_async.hip), _leaves
-// (mnk_search_selfplay_async_leaves.hip) and _gumbel (mnk_search_selfplay_async_gumbel.hip).  A kernel body is a short
-// composition of these pieces around what is its own; a change to the outcome labels, the error row or the budget draw is
-// made here, once.  The rule: include/mnk_hip.h, mnk_search_selfplay_advance.
+// only): the argument block, the host's check of it and the launch shape, and the self-play steps of a row as device
+// functions that every advance kernel inlines -- k_search_selfplay_advance, _opts and _keep
+// (mnk_search_selfplay_async.hip), _leaves (mnk_search_selfplay_async_leaves.hip) and _gumbel
+// (mnk_search_selfplay_async_gumbel.hip): the budget draw, the root's noise and visit counts, the end of a ply, the fresh
+// root, the error row.  What a row does as a PUCT tree -- its view of the workspace, the clamped header, the stage's
+// planes, a selection's write-out -- is mnk_puct_tree.h's, shared with the lockstep player (mnk_puct.hip).  A kernel body
+// is a short composition of these pieces around what is its own; a change to the outcome labels, the error row or the
+// budget draw is made here, once.  The rule: include/mnk_hip.h, mnk_search_selfplay_advance.
 //
 // The shape of every kernel: one wave per row, MNK_PUCT_ROWS rows per workgroup, no workgroup barrier (which branch a row
-// takes is wave-uniform; the rows of a workgroup diverge), `pos` the wave's own LDS stage of 2 * NW words.  A piece that
-// writes or reads pos says which row_wave_sync() its caller owes.
+// takes is wave-uniform; the rows of a workgroup diverge), `pos` the wave's own LDS stage of 2 * NW words
+// (mnk_puct_tree.h).  A piece that writes or reads pos says which row_wave_sync() its caller owes.
 #pragma once
 #include "mnk_puct_noise.h"
 #include "mnk_puct_tree.h"
@@ -107,59 +110,7 @@ inline void mnk_advance_launch(void (*kernel)(MnkAdvanceArgs, P...), const MnkAd
                      (hipStream_t)stream, a, own...);
 }
 
-// ================================================================== the row's workspace
-struct MnkAdvanceRow {
-  MnkPuctLayout L;
-  unsigned char* row;
-  uint32_t* hdr;
-  const uint32_t* root;
-  uint32_t* leaf;  // (slot 0's, as `path`)
-  uint16_t* path;
-  MnkPuctNode* node;
-  float* prior;
-  uint16_t* child;
-};
-// TI: the layout's iterations, the caller's
-__device__ __forceinline__ MnkAdvanceRow advance_row(unsigned char* ws, int64_t i, int NWg, int C, int TI, int leaves = 1) {
-  MnkAdvanceRow r;
-  r.L = mnk_puct_layout(NWg, C, TI, leaves);
-  r.row = ws + i * r.L.row;
-  r.hdr = (uint32_t*)r.row;
-  r.root = (const uint32_t*)(r.row + r.L.root);
-  r.leaf = (uint32_t*)(r.row + r.L.leaf);
-  r.path = (uint16_t*)(r.row + r.L.path);
-  r.node = (MnkPuctNode*)(r.row + r.L.node);
-  r.prior = (float*)(r.row + r.L.prior);
-  r.child = (uint16_t*)(r.row + r.L.child);
-  return r;
-}
-
-// the header, clamped by the layout's iterations as in k_puct_step: whatever the workspace holds, no id leaves the row
-struct MnkAdvanceHeader {
-  int nodes, depth;
-  uint32_t state;
-  bool live;
-};
-__device__ __forceinline__ MnkAdvanceHeader advance_header(const uint32_t* hdr, int TI) {
-  MnkAdvanceHeader h;
-  h.nodes = (int)min(max(hdr[0], 1u), (uint32_t)(TI + 1));
-  h.depth = (int)min(hdr[1], (uint32_t)TI);
-  h.state = hdr[2];
-  h.live = hdr[3] != 0u;
-  return h;
-}
-
 // ================================================================== the wave's stage
-// packed planes of the workspace (a leaf's, the root's: u32[2][NWg]) into pos, padded to NW words a plane; every lane
-// calls it.  The caller owes a row_wave_sync() after it, and one before it when lanes may still read the stage.
-template <int NW>
-__device__ __forceinline__ void stage_planes(uint32_t* pos, const uint32_t* src, int NWg, int lane) {
-  for (int q = lane; q < 2 * NW; q += 64) {
-    const int pl = q >= NW, w = q - (pl ? NW : 0);
-    pos[q] = w < NWg ? src[pl * NWg + w] : 0u;
-  }
-}
-
 // the canonical position of e (plane 0 = the side to move) into pos, by lane 0.  The caller owes a row_wave_sync() before
 // it (every lane is done with what the stage held) and one after it.
 template <int NW>
@@ -307,7 +258,7 @@ __device__ __forceinline__ MnkPly advance_finish_ply(const MnkAdvanceArgs& a, Mn
 // the search of the position reached, e: a fresh tree, its root the pending leaf, shown as batch row b.  The syncs around
 // the staging are inside.
 template <int NW, int CN>
-__device__ __forceinline__ void advance_fresh_root(const MnkAdvanceArgs& a, const MnkAdvanceRow& r, uint32_t* pos,
+__device__ __forceinline__ void advance_fresh_root(const MnkAdvanceArgs& a, const MnkPuctRow& r, uint32_t* pos,
                                                    const MnkEnv<NW>& e, int64_t b, int lane) {
   row_wave_sync();  // (every lane is done with the position before this ply)
   stage_env<NW>(pos, e, lane);
@@ -320,52 +271,15 @@ __device__ __forceinline__ void advance_fresh_root(const MnkAdvanceArgs& a, cons
 // a root without a legal cell (or, of a workspace that is not this position's, without a move on a free cell): reported,
 // left alone, the root shown again in `count` batch rows from b.  The syncs around the staging are inside.
 template <int NW, int CN>
-__device__ __forceinline__ void advance_error_row(const MnkAdvanceArgs& a, const MnkAdvanceRow& r, uint32_t* pos, int64_t i,
+__device__ __forceinline__ void advance_error_row(const MnkAdvanceArgs& a, const MnkPuctRow& r, uint32_t* pos, int64_t i,
                                                   int64_t b, int count, int lane) {
   if (lane == 0) {
     mnk_report(a.err, MNK_ERR_VISITS, i);
     if (a.fresh) a.fresh[i] = 0;
   }
   row_wave_sync();
-  stage_planes<NW>(pos, r.root, a.g.NW, lane);
+  puct_stage_planes<NW>(pos, r.root, a.g.NW, lane);
   row_wave_sync();
   for (int j = 0; j < count; ++j)
     row_write_view<NW, CN>(a.g, pos, 0, b + j, a.leaf_obs, a.leaf_dtype, a.leaf_mask, lane);
-}
-
-// ================================================================== the selection's write-out, one slot
-// The planes a slot shows after a walk that started from e (so e is set up), by lane 0 into the stage: the walk's leaf, e,
-// when nstate != 0; else nothing is pending and the slot shows the root.  (A slot that no walk entered stages the root
-// with stage_planes.)  e's words are read ahead of the choice: written as `nstate ? e.p[..] : root[..]` on a reference the
-// compiler selects between the two addresses, which costs the 19x19 kernels 5 VGPRs and 9 % more instructions.  The
-// caller owes a row_wave_sync() before it, when lanes may still read the stage; the one after it is
-// advance_store_selection's.
-template <int NW>
-__device__ __forceinline__ void stage_selection(uint32_t* pos, const MnkEnv<NW>& e, uint32_t nstate, const uint32_t* root,
-                                                int NWg, int lane) {
-  if (lane == 0) {
-#pragma unroll
-    for (int w = 0; w < NW; ++w) {
-      const uint32_t l0 = e.p[0][w], l1 = e.p[1][w];
-      pos[w] = nstate ? l0 : (w < NWg ? root[w] : 0u);
-      pos[NW + w] = nstate ? l1 : (w < NWg ? root[NWg + w] : 0u);
-    }
-  }
-}
-
-// The slot's planes are staged (stage_selection, or stage_planes of the root): path[0] and the slot's {depth, state} (ds)
-// by lane 0, the sync, the planes to the workspace (leafp), the view as batch row b with parity d & 1.
-template <int NW, int CN>
-__device__ __forceinline__ void advance_store_selection(const MnkAdvanceArgs& a, const uint32_t* pos, uint32_t nstate, int d,
-                                                        uint16_t* path, uint32_t* ds, uint32_t* leafp, int64_t b,
-                                                        int lane) {
-  const int NWg = a.g.NW;
-  if (lane == 0) {
-    path[0] = 0;
-    ds[0] = (uint32_t)d;
-    ds[1] = nstate;
-  }
-  row_wave_sync();
-  for (int q = lane; q < 2 * NWg; q += 64) leafp[q] = pos[(q >= NWg) * NW + q - (q >= NWg ? NWg : 0)];
-  row_write_view<NW, CN>(a.g, pos, d & 1, b, a.leaf_obs, a.leaf_dtype, a.leaf_mask, lane);
 }

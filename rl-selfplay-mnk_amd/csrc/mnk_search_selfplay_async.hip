@@ -26,11 +26,11 @@ __global__ void __launch_bounds__(256) k_search_selfplay_advance(MnkAdvanceArgs 
   const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
   if (i >= a.N) return;
   const int C = a.g.C, NWg = a.g.NW, I = a.I;
-  const MnkAdvanceRow r = advance_row(a.ws, i, NWg, C, I);
-  const MnkAdvanceHeader h = advance_header(r.hdr, I);
+  const MnkPuctRow r = puct_row(a.ws, i, NWg, C, I);
+  const MnkPuctHeader h = puct_header(r.hdr, I);
   int nodes = h.nodes;
   uint32_t* pos = lds_pos[wave];
-  stage_planes<NW>(pos, r.leaf, NWg, lane);
+  puct_stage_planes<NW>(pos, r.leaf, NWg, lane);
   row_wave_sync();
 
   // ---- backup of the pending evaluation
@@ -81,11 +81,12 @@ __global__ void __launch_bounds__(256) k_search_selfplay_advance(MnkAdvanceArgs 
     puct_env_root<NW>(e, r.root, NWg);
     nstate = puct_walk<NW, CN, CK, false>(a.g, e, I, a.c, r.node, r.prior, r.child, r.path, nodes, d, lane);
     if (nstate == 0u) d = 0;
-    stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
+    puct_stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
   } else {
-    stage_planes<NW>(pos, r.root, NWg, lane);  // (a full tree: no walk, the root again)
+    puct_stage_planes<NW>(pos, r.root, NWg, lane);  // (a full tree: no walk, the root again)
   }
-  advance_store_selection<NW, CN>(a, pos, nstate, d, r.path, r.hdr + 1, r.leaf, i, lane);
+  puct_store_selection<NW, CN>(a.g, pos, nstate, d, r.path, r.hdr + 1, r.leaf, i, a.leaf_obs, a.leaf_dtype,
+                               a.leaf_mask, lane);
   if (lane == 0) {
     r.hdr[0] = (uint32_t)nodes;
     if (a.fresh) a.fresh[i] = 0;
@@ -111,11 +112,11 @@ k_search_selfplay_advance_opts(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_ep
   const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
   if (i >= a.N) return;
   const int C = a.g.C, NWg = a.g.NW, I = a.I;
-  const MnkAdvanceRow r = advance_row(a.ws, i, NWg, C, I);
-  const MnkAdvanceHeader h = advance_header(r.hdr, I);
+  const MnkPuctRow r = puct_row(a.ws, i, NWg, C, I);
+  const MnkPuctHeader h = puct_header(r.hdr, I);
   int nodes = h.nodes;
   uint32_t* pos = lds_pos[wave];
-  stage_planes<NW>(pos, r.leaf, NWg, lane);
+  puct_stage_planes<NW>(pos, r.leaf, NWg, lane);
   row_wave_sync();
 
   // ---- the budget of the row's ply (before the backup: whether a root is noised depends on it)
@@ -164,7 +165,7 @@ k_search_selfplay_advance_opts(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_ep
     return;
   }
 
-  // ---- selection: k_puct_step's (SOLVER: k_puct_step_solver's at one leaf per row; the root has no proof here)
+  // ---- selection: k_puct_step's (SOLVER: k_puct_step_leaves<true>'s at one leaf per row; the root has no proof here)
   int d = 0;
   uint32_t nstate = 0u;  // nothing pending: a full tree shows its root again (it cannot happen: nodes <= n_root <= I)
   if (nodes <= I) {
@@ -172,11 +173,12 @@ k_search_selfplay_advance_opts(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_ep
     nstate = puct_walk<NW, CN, CK, false, SOLVER, false, FPU>(a.g, e, I, a.c, r.node, r.prior, r.child, r.path, nodes, d,
                                                               lane, 0, 0u, nullptr, 0, nullptr, fpu, fpu_root);
     if (nstate == 0u) d = 0;
-    stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
+    puct_stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
   } else {
-    stage_planes<NW>(pos, r.root, NWg, lane);  // (a full tree: no walk, the root again)
+    puct_stage_planes<NW>(pos, r.root, NWg, lane);  // (a full tree: no walk, the root again)
   }
-  advance_store_selection<NW, CN>(a, pos, nstate, d, r.path, r.hdr + 1, r.leaf, i, lane);
+  puct_store_selection<NW, CN>(a.g, pos, nstate, d, r.path, r.hdr + 1, r.leaf, i, a.leaf_obs, a.leaf_dtype,
+                               a.leaf_mask, lane);
   if (lane == 0) {
     r.hdr[0] = (uint32_t)nodes;
     if (a.fresh) a.fresh[i] = 0;
@@ -206,14 +208,14 @@ k_search_selfplay_advance_keep(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_ep
   const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
   if (i >= a.N) return;
   const int C = a.g.C, NWg = a.g.NW, I = a.I;
-  const MnkAdvanceRow r = advance_row(a.ws, i, NWg, C, TI);  // (the layout and the clamps are TI's)
-  const MnkAdvanceHeader h = advance_header(r.hdr, TI);
+  const MnkPuctRow r = puct_row(a.ws, i, NWg, C, TI);  // (the layout and the clamps are TI's)
+  const MnkPuctHeader h = puct_header(r.hdr, TI);
   int nodes = h.nodes;
   uint32_t* pos = lds_pos[wave];
   const int MS = (TI + 3) & ~1;
   uint16_t* map = (uint16_t*)(lds_gamma + (nz.alpha > 0.0 ? MNK_PUCT_ROWS * C : 0)) + (int64_t)wave * 2 * MS;
   uint16_t* inv = map + MS;
-  stage_planes<NW>(pos, r.leaf, NWg, lane);
+  puct_stage_planes<NW>(pos, r.leaf, NWg, lane);
   row_wave_sync();
 
   // ---- the budget of the row's ply (before the backup: whether a root is noised depends on it)
@@ -310,7 +312,7 @@ k_search_selfplay_advance_keep(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_ep
     return;
   }
 
-  // ---- selection: k_puct_step's (SOLVER: k_puct_step_solver's at one leaf per row; the root has no proof here)
+  // ---- selection: k_puct_step's (SOLVER: k_puct_step_leaves<true>'s at one leaf per row; the root has no proof here)
   int d = 0;
   uint32_t nstate = 0u;  // nothing pending: a full tree shows its root again (it cannot happen: nodes <= keep_nodes + it)
   if (nodes <= TI) {
@@ -318,11 +320,12 @@ k_search_selfplay_advance_keep(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_ep
     nstate = puct_walk<NW, CN, CK, false, SOLVER, false, FPU>(a.g, e, TI, a.c, r.node, r.prior, r.child, r.path, nodes, d,
                                                               lane, 0, 0u, nullptr, 0, nullptr, fpu, fpu_root);
     if (nstate == 0u) d = 0;
-    stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
+    puct_stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
   } else {
-    stage_planes<NW>(pos, r.root, NWg, lane);  // (a full tree: no walk, the root again)
+    puct_stage_planes<NW>(pos, r.root, NWg, lane);  // (a full tree: no walk, the root again)
   }
-  advance_store_selection<NW, CN>(a, pos, nstate, d, r.path, r.hdr + 1, r.leaf, i, lane);
+  puct_store_selection<NW, CN>(a.g, pos, nstate, d, r.path, r.hdr + 1, r.leaf, i, a.leaf_obs, a.leaf_dtype,
+                               a.leaf_mask, lane);
   if (lane == 0) {
     r.hdr[0] = (uint32_t)nodes;
     if (a.fresh) a.fresh[i] = 0;

@@ -4,9 +4,10 @@
 // schedule table of the ply's budget, its move and its improved policy at the end of the ply -- all inside the one launch.
 // The rule: include/mnk_hip.h, mnk_search_selfplay_advance_gumbel.
 //
-// What a row does in every advance kernel -- the prologue, the budget draw, the end of a ply, the error row, the
-// selection's write-out -- and the host's common check are mnk_search_selfplay_advance.h's; the root's draw, the pick and
-// the policy's quantisation are this kernel's own.  So are, for the registers of one variant (15x15: 127 VGPRs, four waves
+// What a row does in every advance kernel -- the budget draw, the end of a ply, the error row -- and the host's common
+// check are mnk_search_selfplay_advance.h's; the row's view, the selection's write-out, the root's pick and the improved
+// policy (puct_gumbel_policy, the one the lockstep player's move calls) are mnk_puct_tree.h's; the root's draw and the
+// policy's quantisation are this kernel's own.  So are, for the registers of one variant (15x15: 127 VGPRs, four waves
 // per SIMD), its parameter list -- the kernel puts the argument block together itself -- and the start of the next search
 // (profiles/exp_search_selfplay_advance_pieces_kernels.md).  A translation unit of its own all the same: compiled beside its
 // siblings a kernel changes the code the compiler makes of them (profiles/exp_search_selfplay_async_leaves_kernels.md).
@@ -18,79 +19,6 @@
 
 #define MNK_ADVANCE_GUMBEL_CELLS_MAX 1024  // 64 * MNK_MAX_W: no supported board has more cells than a plane has bits
 static_assert(MNK_ADVANCE_GUMBEL_CELLS_MAX == 64 * MNK_MAX_W, "the cell range follows the packed planes");
-
-// a sum over the wave, the same value in every lane
-__device__ __forceinline__ double advance_wave_sum(double x) {
-#pragma unroll
-  for (int off = 32; off; off >>= 1) x += __shfl_xor(x, off, 64);
-  return x;
-}
-
-// The improved policy of a Gumbel root after its last backup: the policy part of puct_move_gumbel (mnk_puct.hip; the
-// rule: include/mnk_hip.h, mnk_puct_step_gumbel), operation for operation, without that function's `actions` / `visits`
-// outputs.  This unit's own copy: moving the function into mnk_puct_tree.h, called from both, changed the code objects of
-// k_puct_step_gumbel (profiles/exp_search_selfplay_async_gumbel_kernels.md), so the original stays where it is and any
-// change to the rule is made in both.  The move is puct_gumbel_pick<true> (mnk_puct_tree.h), which also gives maxn.
-// f64: five passes over the root's cells (the sum of the clamped priors; the visited cells' sums for v_mix; the maximum
-// of y; the sum of exp(y - max); the store), every pass recomputing a cell's terms from the tree -- the same operations on
-// the same inputs give the same y each time -- and reduced over the wave.  pr = the root's stored priors (node 0's row),
-// cl its child row.  store(a, policy_a) is called once for every cell a < C by the lane that owns it (a = lane,
-// lane + 64, ...), with 0 for an occupied cell.
-template <class Store>
-__device__ __forceinline__ void advance_gumbel_policy(int C, const MnkPuctNode* node, const float* pr, const uint16_t* cl,
-                                                      int nodes, const MnkPuctGumbel& gm, float vroot, uint32_t maxn,
-                                                      int lane, Store store) {
-  // a free cell's clamped prior, visit count and q (0 where it has no visit)
-  auto cell = [&](int a, double& p, uint32_t& na, double& q) {
-    const uint32_t ch = cl[a];
-    if (ch == MNK_PUCT_NONE) return false;
-    const float pa = pr[a];
-    p = (double)(pa > 0x1p-126f ? pa : 0x1p-126f);
-    na = 0u;
-    q = 0.0;
-    if (ch) {
-      const MnkPuctNode k = node[min((int)ch, nodes - 1)];
-      na = k.n;
-      if (na) q = (double)__fdiv_rn(k.w, (float)na);
-    }
-    return true;
-  };
-  double p, q, sp = 0.0;
-  uint32_t na, ns = 0u;
-  for (int a = lane; a < C; a += 64)
-    if (cell(a, p, na, q)) {
-      sp += p;
-      ns += na;
-    }
-  sp = advance_wave_sum(sp);
-#pragma unroll
-  for (int off = 32; off; off >>= 1) ns += (uint32_t)__shfl_xor((int)ns, off, 64);
-  double sv = 0.0, sq = 0.0;
-  for (int a = lane; a < C; a += 64)
-    if (cell(a, p, na, q) && na) {
-      sv += p / sp;
-      sq += p / sp * q;
-    }
-  sv = advance_wave_sum(sv);
-  sq = advance_wave_sum(sq);
-  const double vmix = sv > 0.0 ? ((double)vroot + (double)ns * sq / sv) / (1.0 + (double)ns) : (double)vroot;
-  const double K = ((double)gm.c_visit + (double)maxn) * (double)gm.c_scale;
-  auto y_of = [&](int a, double& y) {
-    if (!cell(a, p, na, q)) return false;
-    y = log(p) + K * (na ? q : vmix);
-    return true;
-  };
-  double y, my = -INFINITY;
-  for (int a = lane; a < C; a += 64)
-    if (y_of(a, y)) my = fmax(my, y);
-#pragma unroll
-  for (int off = 32; off; off >>= 1) my = fmax(my, __shfl_xor(my, off, 64));
-  double se = 0.0;
-  for (int a = lane; a < C; a += 64)
-    if (y_of(a, y)) se += exp(y - my);
-  se = advance_wave_sum(se);
-  for (int a = lane; a < C; a += 64) store(a, y_of(a, y) ? (float)(exp(y - my) / se) : 0.0f);
-}
 
 // k_search_selfplay_advance with the Gumbel root.  The same shape: one wave per row, MNK_PUCT_ROWS rows per workgroup, no
 // workgroup barrier (which branch a row takes is wave-uniform; the rows of a workgroup diverge), every id read from the
@@ -116,11 +44,11 @@ k_search_selfplay_advance_gumbel(MnkGeom g, unsigned char* ws, uint64_t* planes,
   const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
   if (i >= a.N) return;
   const int C = a.g.C, NWg = a.g.NW, I = a.I;
-  const MnkAdvanceRow r = advance_row(a.ws, i, NWg, C, I);
-  const MnkAdvanceHeader h = advance_header(r.hdr, I);
+  const MnkPuctRow r = puct_row(a.ws, i, NWg, C, I);
+  const MnkPuctHeader h = puct_header(r.hdr, I);
   int nodes = h.nodes;
   uint32_t* pos = lds_pos[wave];
-  stage_planes<NW>(pos, r.leaf, NWg, lane);
+  puct_stage_planes<NW>(pos, r.leaf, NWg, lane);
   row_wave_sync();
 
   // ---- the budget of the row's ply: B, and the schedule table that goes with it
@@ -178,8 +106,8 @@ k_search_selfplay_advance_gumbel(MnkGeom g, unsigned char* ws, uint64_t* planes,
     const int64_t t = (int64_t)(bg.p % (uint64_t)a.T);
     uint16_t* rv = a.ring_visits + (t * a.N + i) * C;
     if (bg.full) {
-      // k_search_selfplay_step_moves's quantisation of puct_move_gumbel's policy, a cell at a time
-      advance_gumbel_policy(C, r.node, r.prior, r.child, nodes, gm, vroot[i], maxn, lane, [&](int q, float pa) {
+      // k_search_selfplay_step_moves's quantisation of the improved policy, a cell at a time
+      puct_gumbel_policy(C, r.node, r.prior, r.child, nodes, gm, vroot[i], maxn, lane, [&](int q, float pa) {
         const bool occ = row_stone<CN>(a.g, pos, q) || row_stone<CN>(a.g, pos + NW, q);
         const float v = rintf(__fmul_rn(pa, 65535.0f));
         rv[q] = (occ || !(v > 0.0f)) ? (uint16_t)0 : (uint16_t)fminf(v, 65535.0f);
@@ -219,11 +147,12 @@ k_search_selfplay_advance_gumbel(MnkGeom g, unsigned char* ws, uint64_t* planes,
     nstate = puct_walk<NW, CN, CK, false, false, true>(a.g, e, B, a.c, r.node, r.prior, r.child, r.path, nodes, d, lane, 0,
                                                        0u, nullptr, 0, &gm);
     if (nstate == 0u) d = 0;
-    stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
+    puct_stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
   } else {
-    stage_planes<NW>(pos, r.root, NWg, lane);  // (a full tree: no walk, the root again)
+    puct_stage_planes<NW>(pos, r.root, NWg, lane);  // (a full tree: no walk, the root again)
   }
-  advance_store_selection<NW, CN>(a, pos, nstate, d, r.path, r.hdr + 1, r.leaf, i, lane);
+  puct_store_selection<NW, CN>(a.g, pos, nstate, d, r.path, r.hdr + 1, r.leaf, i, a.leaf_obs, a.leaf_dtype,
+                               a.leaf_mask, lane);
   if (lane == 0) {
     r.hdr[0] = (uint32_t)nodes;
     if (a.fresh) a.fresh[i] = 0;

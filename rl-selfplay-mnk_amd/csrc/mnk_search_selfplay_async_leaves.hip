@@ -5,15 +5,16 @@
 // include/mnk_hip.h, mnk_search_selfplay_advance_leaves.
 //
 // What a row does in every advance kernel -- the budget draw, the root's noise and visit counts, the end of a ply, the
-// error row, a slot's write-out -- and the host's common checks are mnk_search_selfplay_advance.h's; the slot loops,
-// row_sims and the virtual visits are this kernel's own.  A translation unit of its own all the same: every function here
-// is inlined, but the module's passes see sibling call sites, and compiled beside its siblings the kernel changes the code
-// the compiler makes of them (profiles/exp_search_selfplay_async_leaves_kernels.md).
+// error row -- and the host's common checks are mnk_search_selfplay_advance.h's; the row's view, its slots and a slot's
+// write-out are mnk_puct_tree.h's; the slot loops, row_sims and the virtual visits are this kernel's own.  A translation
+// unit of its own all the same: every function here is inlined, but the module's passes see sibling call sites, and
+// compiled beside its siblings the kernel changes the code the compiler makes of them
+// (profiles/exp_search_selfplay_async_leaves_kernels.md).
 #include "mnk_search_selfplay_advance.h"
 
-// The backup loop and the selection loop of k_puct_step_leaves / k_puct_step_solver (mnk_puct.hip) around the shared end
-// of a ply.  The siblings' shape: one wave per row, MNK_PUCT_ROWS rows per workgroup, no workgroup barrier, every id read
-// from the workspace clamped to the row.  Slot j of row i is batch row i * leaves + j; the slots' paths stay in the
+// The backup loop and the selection loop of the lockstep player's round (puct_step_row, mnk_puct.hip) around the shared
+// end of a ply.  The siblings' shape: one wave per row, MNK_PUCT_ROWS rows per workgroup, no workgroup barrier, every id
+// read from the workspace clamped to the row.  Slot j of row i is batch row i * leaves + j; the slots' paths stay in the
 // workspace.  Whether the ply ends is decided by row_sims, the simulations the ply has been offered, not by the root's
 // visits: a slot that the walk makes void is a simulation spent.  The three branches after the backups -- the ply ends, an
 // error row, the selections -- are disjoint and wave-uniform, so the one MnkEnv serves the ply and the walks.
@@ -28,14 +29,10 @@ k_search_selfplay_advance_leaves(MnkAdvanceArgs a, int leaves, MnkPuctNoise nz, 
   const int64_t i = (int64_t)blockIdx.x * MNK_PUCT_ROWS + wave;
   if (i >= a.N) return;
   const int C = a.g.C, NWg = a.g.NW, I = a.I;
-  const MnkAdvanceRow r = advance_row(a.ws, i, NWg, C, I, leaves);
-  const MnkAdvanceHeader h = advance_header(r.hdr, I);  // (nodes and live; depth and state are a slot's)
+  const MnkPuctRow r = puct_row(a.ws, i, NWg, C, I, leaves);
+  const MnkPuctHeader h = puct_header(r.hdr, I);  // (nodes and live; depth and state are a slot's)
   int nodes = h.nodes;
   uint32_t* pos = lds_pos[wave];
-  // slot j's {depth, state}, leaf planes and path (slot 0: the header's, `leaf`, `path`)
-  auto slot_ds = [&](int j) { return j ? (uint32_t*)(r.row + r.L.xhdr) + 2 * (j - 1) : r.hdr + 1; };
-  auto slot_leaf = [&](int j) { return (uint32_t*)(r.row + (j ? r.L.xleaf + 8 * (int64_t)NWg * (j - 1) : r.L.leaf)); };
-  auto slot_path = [&](int j) { return (uint16_t*)(r.row + (j ? r.L.xpath + r.L.pstride * (j - 1) : r.L.path)); };
 
   // ---- the budget of the row's ply (before the backups: whether a root is noised depends on it)
   const MnkAdvanceBudget bg = advance_budget(a, i);
@@ -44,13 +41,13 @@ k_search_selfplay_advance_leaves(MnkAdvanceArgs a, int leaves, MnkPuctNoise nz, 
 
   // ---- the backups of the pending evaluations, in slot order
   for (int j = 0; j < leaves && h.live; ++j) {
-    const uint32_t* ds = slot_ds(j);
+    const uint32_t* ds = puct_slot_ds(r, j);
     const int depth = (int)min(ds[0], (uint32_t)I);
     const uint32_t state = ds[1];
     if (!(state & 1u)) continue;
-    stage_planes<NW>(pos, slot_leaf(j), NWg, lane);
+    puct_stage_planes<NW>(pos, puct_slot_leaf(r, j, NWg), NWg, lane);
     row_wave_sync();
-    puct_backup<NW, CN, SOLVER>(a.g, pos, slot_path(j), r.node, r.prior, r.child, nodes, depth, state, a.priors,
+    puct_backup<NW, CN, SOLVER>(a.g, pos, puct_slot_path(r, j), r.node, r.prior, r.child, nodes, depth, state, a.priors,
                                 a.priors_dtype, a.values, a.values_dtype, i * leaves + j, lane);
     // evaluation 0 (pending in slot 0) is batch row i * leaves.  The sync is this kernel's: the next slot's planes
     // overwrite the stage the noise reads
@@ -99,18 +96,18 @@ k_search_selfplay_advance_leaves(MnkAdvanceArgs a, int leaves, MnkPuctNoise nz, 
     return;
   }
 
-  // ---- the selections: k_puct_step_leaves's (SOLVER: k_puct_step_solver's; the root has no proof here), slots 0 .. s - 1;
+  // ---- the selections: puct_step_row's with VL (the root has no proof here), slots 0 .. s - 1;
   // the slots from s on are void, so that the ply is offered its budget exactly
   const int s = (int)min((uint32_t)leaves, budget - sims);
   const int nodes0 = nodes;
-  const uint16_t* epath = slot_path(min(lane, leaves - 1));  // lane l < leaves: slot l's path
+  const uint16_t* epath = puct_slot_path(r, min(lane, leaves - 1));  // lane l < leaves: slot l's path
   int edepth = 0;                                            // and, once it has selected, its leaf's depth
   uint32_t active = 0u;                                      // the slots of this round that have a leaf
   bool open = true;                                          // no slot was void yet
   for (int j = 0; j < leaves; ++j) {
     int d = 0;
     uint32_t nstate = 0u;
-    uint16_t* path = slot_path(j);
+    uint16_t* path = puct_slot_path(r, j);
     if (open && j < s && nodes <= I) {
       puct_env_root<NW>(e, r.root, NWg);
       nstate = puct_walk<NW, CN, CK, true, SOLVER>(a.g, e, I, a.c, r.node, r.prior, r.child, path, nodes, d, lane, nodes0,
@@ -123,9 +120,10 @@ k_search_selfplay_advance_leaves(MnkAdvanceArgs a, int leaves, MnkPuctNoise nz, 
       d = 0;
       open = false;
     }
-    if (nstate) stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
-    else stage_planes<NW>(pos, r.root, NWg, lane);  // (a void slot shows the root)
-    advance_store_selection<NW, CN>(a, pos, nstate, d, path, slot_ds(j), slot_leaf(j), i * leaves + j, lane);
+    if (nstate) puct_stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
+    else puct_stage_planes<NW>(pos, r.root, NWg, lane);  // (a void slot shows the root)
+    puct_store_selection<NW, CN>(a.g, pos, nstate, d, path, puct_slot_ds(r, j), puct_slot_leaf(r, j, NWg), i * leaves + j,
+                                 a.leaf_obs, a.leaf_dtype, a.leaf_mask, lane);
     row_wave_sync();  // (the next slot's walk reads this one's node, child entry and path; its write-out reuses pos)
   }
   if (lane == 0) {

@@ -25,6 +25,9 @@ CASES = {
     "16x15x5": ((16, 15, 5), 4, 32, (4,)),               # <8,15,5> with 240 cells: a plane that fills its last word
     "12x13x5": ((12, 13, 5), 3, 32, (4,)),               # <6,13,5> with 156 cells; a partial workgroup
     "18x19x5": ((18, 19, 5), 3, 32, (4,)),               # <12,19,5> with 342 cells; a partial workgroup
+    # the generic forms of four and of eight words
+    "7x9x7": ((7, 9, 7), 3, 16, (4,)),                   # three words
+    "12x12x5": ((12, 12, 5), 3, 16, (4,)),               # five words
 }
 PARAMS = [(name, L) for name, (_, _, _, Ls) in CASES.items() for L in Ls]
 

@@ -26,6 +26,9 @@ CASES = {
     "12x13x5": ((12, 13, 5), 7, 32),   # <6,13,5>: 156 cells for 169
     "16x15x5": ((16, 15, 5), 7, 32),   # <8,15,5>: 240 cells for 225, 256 bits
     "18x19x5": ((18, 19, 5), 7, 32),   # <12,19,5>: 342 cells for 361
+    # the generic forms of four and of eight words
+    "7x9x7": ((7, 9, 7), 8, 32),       # three words
+    "12x12x5": ((12, 12, 5), 8, 16),   # five words
 }
 SIBLINGS = ("8x3x3", "7x9x5", "12x13x5", "16x15x5", "18x19x5")
 LEAVES = (1, 4)

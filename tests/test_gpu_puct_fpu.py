@@ -25,16 +25,29 @@ BOARDS = {"3x3x3": 12,    # one pass per lane
           "9x9x5": 24,    # C = 81: the mass spans two passes and the lanes
           "7x9x5": 16,    # a sibling of the 9x9x5 variant
           "5x5x4": 20,    # the generic form
-          "19x19x5": 8}   # the multi-word form
+          "19x19x5": 8,   # the multi-word form
+          "12x13x5": 32,  # <6,13,5>: 156 cells for the variant's 169
+          "16x15x5": 32,  # <8,15,5>: 240 cells for 225
+          "12x12x5": 8,   # generic, five words: the eight-word instantiation
+          "7x9x7": 8}     # generic, three words: the four-word instantiation
+SEVEN = ("12x13x5", "16x15x5")  # boards that take all seven rows of ``sibling_positions``
+GENERIC = {"12x12x5": (12, 12, 5), "7x9x7": (7, 9, 7)}  # boards tests/puct_solver_cases.py has no rows of: ``start`` positions
 LEAVES = (1, 4)
+
+
+def board_of(name):
+    return GENERIC[name] if name in GENERIC else CASES[name][0]
 
 
 def rows_of(name, early=False):
     """five rows of the board: those of tests/puct_solver_cases.py (late positions, wins at once, full boards; 19x19x5
-    has four and takes an empty board as its fifth), or with ``early`` an empty board and four a few stones in"""
-    (m, n, k), _, _ = CASES[name]
-    if early:
+    has four and takes an empty board as its fifth; the boards of SEVEN take all seven), or with ``early``, and on the
+    boards of GENERIC, an empty board and four a few stones in"""
+    m, n, k = board_of(name)
+    if early or name in GENERIC:
         return start(m, n, k, ROWS, 7)
+    if name in SEVEN:
+        return positions(name)
     obs = positions(name)[:ROWS]
     return obs if len(obs) == ROWS else np.concatenate([obs, np.zeros((ROWS - len(obs), 2, m, n), np.float32)])
 
@@ -60,7 +73,7 @@ def losing_torch(C, record=None, scale=1.0):
 @functools.lru_cache(maxsize=None)
 def reference(name, L, solver, temperature=0, fpu=FPU, losing=False):
     """(obs, (actions, visits, root_value, carried, proof), every evaluation's (leaf_obs, leaf_mask)) of the rule"""
-    (m, n, k), _, _ = CASES[name]
+    m, n, k = board_of(name)
     obs, seen = rows_of(name, losing), []
     ev = losing_np(m * n) if losing else exact_np(m * n)
     rule = FpuPuct(k, BOARDS[name], C_PUCT, ev, L, seed=SEED, env_id0=ENV_ID0, temperature=temperature, leaves=seen,
@@ -69,7 +82,7 @@ def reference(name, L, solver, temperature=0, fpu=FPU, losing=False):
 
 
 def policy(hip, name, L, solver, evaluator, step=2, fpu=FPU, **kw):
-    (m, n, k), _, _ = CASES[name]
+    m, n, k = board_of(name)
     pol = hip.policy.PUCTSearchPolicy(k, evaluator=evaluator, iterations=BOARDS[name], c=C_PUCT, seed=SEED, leaves=L,
                                       solver=solver, fpu=fpu, **kw)
     pol._sampler.env_id0, pol._sampler.calls = ENV_ID0, step
@@ -101,7 +114,7 @@ def same_act(got, want, what):
 @pytest.mark.parametrize("L", LEAVES)
 @pytest.mark.parametrize("name", list(BOARDS))
 def test_an_act_equals_the_rule(hip, name, L, solver, temperature):
-    (m, n, k), _, _ = CASES[name]
+    m, n, k = board_of(name)
     obs, want, leaves = reference(name, L, solver, temperature)
     rec = []
     pol = policy(hip, name, L, solver, exact_torch(m * n, record=rec), temperature=temperature)
