@@ -31,6 +31,7 @@ noise, as in the lockstep run).
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fast-iterations 6 --full-prob 0.25 --leaves 4 --noise builtin --solver
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --search gumbel --iterations 16 --fast-iterations 4 --full-prob 0.25
     python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --fpu 0.2 [--fpu-root 0.1] [--fast-iterations 8 --full-prob 0.25]
+    python examples/alphazero_selfplay.py --board 3x3x3 --rounds 12 --forced 2 --noise builtin [--fast-iterations 8 --full-prob 0.25]
 """
 import argparse
 import os
@@ -119,14 +120,15 @@ def greedy(net):
 
 def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates=40, batch=512, lr=2e-3, seed=0,
           noise=True, reuse=False, leaves=1, solver=False, search="puct", considered=4, fast_iterations=None,
-          full_prob=None, fpu=None, log=print):
+          full_prob=None, fpu=None, forced=None, log=print):
     """self-play and training rounds; returns the network.  ``noise``: True / "wrapper" (``RootNoise``), "builtin" (the
     search's own root noise, same alpha and eps) or False / "off" (none).  ``search``: "puct", or "gumbel" -- a Gumbel
     root over ``considered`` moves (``SearchSelfPlay(gumbel=...)``): the exploration is the Gumbel draw and the targets are
     the improved policy, so ``noise`` is not used, and a small ``iterations`` (16) is what it is meant for.
     ``fast_iterations`` and ``full_prob`` (both, or neither): play through ``AsyncSearchSelfPlay`` with per-ply budgets.
     ``fpu``: None, a number or (fpu, fpu_root) -- first-play urgency (``SearchSelfPlay(fpu=...)``): an untried move is
-    valued at its parent's mean value less a reduction, not at 0"""
+    valued at its parent's mean value less a reduction, not at 0.  ``forced``: None or k -- forced playouts and policy
+    target pruning (``SearchSelfPlay(forced=k)``; 2 is usual), what makes root noise useful as a policy target"""
     entry.build()
     from selfplay.policy import model_evaluator
     from selfplay.search_selfplay import SearchSelfPlay
@@ -147,13 +149,13 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
     if fast_iterations is not None:
         return _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies,
                             updates, batch, seed, noise, solver, reuse, leaves,
-                            considered if search == "gumbel" else None, fpu, log)
+                            considered if search == "gumbel" else None, fpu, forced, log)
     if noise == "wrapper":
         evaluator = RootNoise(evaluator, iterations // leaves + 1)
     sp = SearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, temp_plies=max(1, C // 3),
                         capacity=2 * C, seed=seed, reuse=reuse, leaves=leaves, solver=solver,
                         root_noise=(0.3, 0.25) if noise == "builtin" else None,
-                        gumbel=considered if search == "gumbel" else None, fpu=fpu)
+                        gumbel=considered if search == "gumbel" else None, fpu=fpu, forced=forced)
     assert sp.policy.evaluations_per_act == iterations // leaves + 1
     plies = C if plies is None else plies
     gen = torch.Generator(device=dev)
@@ -181,7 +183,7 @@ def train(m=3, n=3, k=3, envs=256, iterations=32, rounds=12, plies=None, updates
 
 
 def _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations, full_prob, rounds, plies, updates, batch,
-                 seed, noise, solver, reuse, leaves, gumbel, fpu, log):
+                 seed, noise, solver, reuse, leaves, gumbel, fpu, forced, log):
     """``train`` through ``AsyncSearchSelfPlay``: a training round follows as many evaluator calls as ``plies`` plies of
     every row cost on average; the loss is ``train``'s (a fast ply's policy target is all zero: only its value counts).
     ``gumbel``: None, or the moves a Gumbel root considers (``train`` has turned the noise off then)"""
@@ -196,7 +198,7 @@ def _train_async(net, opt, evaluator, m, n, k, envs, iterations, fast_iterations
     sp = AsyncSearchSelfPlay(m, n, k, envs, evaluator=evaluator, iterations=iterations, fast_iterations=fast_iterations,
                              full_prob=full_prob, temp_plies=max(1, C // 3), capacity=2 * C, seed=seed, solver=solver,
                              root_noise=(0.3, 0.25) if noise == "builtin" else None, keep_tree=reuse, leaves=leaves,
-                             gumbel=gumbel, fpu=fpu)
+                             gumbel=gumbel, fpu=fpu, forced=forced)
     if noise == "wrapper":
         evaluator.fresh = lambda: sp.fresh
     # (evaluator calls per ply: ceil(B / L) + 1 for a budget of B)
@@ -269,6 +271,11 @@ def main():
                          "prior mass) instead of 0 (0.2 is usual; not with --search gumbel, nor with --leaves above 1 "
                          "under per-ply budgets)")
     ap.add_argument("--fpu-root", type=float, default=None, help="with --fpu: the reduction at the root (default: --fpu)")
+    ap.add_argument("--forced", type=float, default=None, metavar="K",
+                    help="forced playouts and policy target pruning: a visited root move is searched again while its "
+                         "visits squared lie below K * prior * root visits, and the visits PUCT alone would not have spent "
+                         "leave the policy target (2 is usual; meant for --noise builtin; not with --search gumbel, nor "
+                         "with --reuse or --leaves above 1 under per-ply budgets)")
     a = ap.parse_args()
     if a.fpu_root is not None and a.fpu is None:
         ap.error("--fpu-root needs --fpu")
@@ -276,7 +283,7 @@ def main():
     m, n, k = (int(x) for x in a.board.lower().split("x"))
     net = train(m, n, k, envs=a.envs, iterations=a.iterations, rounds=a.rounds, updates=a.updates, seed=a.seed,
                 noise=a.noise, reuse=a.reuse, leaves=a.leaves, solver=a.solver, search=a.search, considered=a.considered,
-                fast_iterations=a.fast_iterations, full_prob=a.full_prob, fpu=fpu)
+                fast_iterations=a.fast_iterations, full_prob=a.full_prob, fpu=fpu, forced=a.forced)
     for name, res in validate(net, m, n, k).items():
         print(f"vs {name}: win {res['win_rate']:.3f} loss {res['loss_rate']:.3f} draw {res['draw_rate']:.3f} "
               f"score {res['score_rate']:.3f}")

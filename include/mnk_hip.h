@@ -570,6 +570,52 @@ int mnk_puct_step_fpu(void* workspace, int64_t N, int m, int n, int k, int itera
                       int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
                       int32_t* visits, float* root_value, int8_t* proof, int solver, float fpu, float fpu_root,
                       void* stream);
+/* mnk_puct_step_leaves, mnk_puct_step_solver (solver = 1) or mnk_puct_step_fpu (fpu_on = 1) with FORCED PLAYOUTS AND POLICY
+ * TARGET PRUNING (Wu, "Accelerating self-play learning in Go", 2019, section 3.2; optional: a search that never calls it
+ * is the search above).  With noise on the root's priors and a small budget, a move the noise promotes gets one visit,
+ * looks mediocre and is never tried again, and that one visit goes into the policy target as noise.  Forced playouts give
+ * every visited root child a floor of visits that grows with its prior and the root's total; pruning takes those visits
+ * back out of the counts that are handed out and played from, wherever PUCT alone would not have spent them.  The
+ * workspace is that of mnk_puct_begin_leaves / mnk_puct_rebase_leaves, leaves in [1, MNK_PUCT_LEAVES_MAX]; every step of an
+ * act is this entry point.  forced_k = k: f32, finite, > 0 (KataGo's 2).  fpu_on in {0, 1}: 0 = no first-play urgency, fpu
+ * and fpu_root are not read (fpu = 0 is not "off", hence the flag).
+ * Notation: node 0 is the root, P_0[a] its stored prior of cell a (after mnk_puct_root_noise, if any), n_a and w_a the
+ * stored counts of the root's child through cell a, vl(.) the round's virtual visits, c the exploration constant.  Every
+ * float operation is a correctly rounded f32 operation, no contraction; priors are taken to be finite.
+ *   selection, at the root only (below it the walk is unchanged): S' = n_0 + vl(0) - 1.  A free cell a is FORCED iff
+ *     (1) its child exists with stored n_a > 0 -- a child created earlier in the same round has no evaluation and is never
+ *     forced: with leaves > 1 a new child of high prior would otherwise pull the round's next slot into an unevaluated
+ *     node and void the rest of the round; (2) with the solver, the child is not proven LOSS; (3) with n'_a = n_a + vl(a),
+ *     fmul((float)n'_a, (float)n'_a) < fmul(fmul(k, P_0[a]), (float)S').  If any cell is FORCED, the candidates are the
+ *     FORCED cells alone, scored by the unchanged s (first-play urgency cannot matter: n'_a > 0), the maximum wins, ties
+ *     to the lowest cell.  If none is, the selection is the one above.
+ *   pruning, on last = 1: n' = the counts the move would be drawn from above (the children's n; with the solver the
+ *     adjusted counts).  If the solver keeps the WIN children alone, nothing is pruned: n'' = n'.  Otherwise
+ *       c* = the cell of maximal n', ties to the lowest cell (all n' zero: nothing is pruned);
+ *       s_a(j) = fadd(fdiv(w_a, (float)n_a), fdiv(fmul(fmul(c, P_0[a]), fsqrt((float)n_0)), (float)(1 + j)));
+ *       s* = s_{c*}(n'_{c*});
+ *       c* keeps its count; a cell with n'_a = 0 or P_0[a] <= 0 keeps its count; for every other cell
+ *         t_a = fmul(fmul(k, P_0[a]), (float)(n_0 - 1)),
+ *         F_a = the least integer F >= 0 with fmul((float)F, (float)F) >= t_a,
+ *         lo = n'_a - min(n'_a, F_a),
+ *         n''_a = the least j in [lo, n'_a] with s_a(j) < s*, and n'_a if there is none;
+ *         if that leaves n''_a = 1 where n'_a > 1, then n''_a = 0.
+ *     For P_0[a] > 0, s_a(j) does not increase with j (a correctly rounded quotient by a growing divisor, then a correctly
+ *     rounded sum), and fmul((float)F, (float)F) does not decrease with F: the kernel bisects where this text walks, and
+ *     finds the same j and the same min(n'_a, F_a).
+ *   visits = n''; the move is drawn from n'' by the unchanged rules (both temperatures, deterministic).  root_value and
+ *   proof are unchanged.  raw_visits (optional, int32 [N][C], NULL = off) takes n'.  WITH PRUNING visits NO LONGER SUM TO THE
+ *   NUMBER OF ITERATIONS.
+ * Everything else is unchanged: the backup, the proofs, where a walk ends.  proof may be NULL, and is not written, when
+ * solver = 0.  solver or fpu_on outside {0, 1}, leaves outside [1, MNK_PUCT_LEAVES_MAX], a NaN, infinite or negative fpu or
+ * fpu_root with fpu_on = 1, a forced_k that is NaN, infinite or <= 0 are MNK_EINVAL; every host check runs before anything
+ * is enqueued; N = 0 returns MNK_OK after them. */
+int mnk_puct_step_forced(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                         int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                         uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                         int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                         int32_t* visits, float* root_value, int8_t* proof, int solver, float fpu, float fpu_root,
+                         int fpu_on, float forced_k, int32_t* raw_visits, void* stream);
 /* The search above with a GUMBEL ROOT ("Policy improvement by planning with Gumbel", Danihelka et al., ICLR 2022;
  * optional: a search that never calls these is the search above).  One Gumbel variable per root move, the budget spent on
  * the `considered` best moves by Sequential Halving, the survivor played -- an exact sample from the improved policy --
@@ -840,6 +886,29 @@ int mnk_search_selfplay_advance_keep_fpu(void* workspace, uint64_t* planes, uint
                                          uint64_t* plies_max, int64_t* stats, int32_t* err, int solver, float noise_alpha,
                                          float noise_eps, int noise_fast, float* root_priors, int tree_iterations,
                                          int keep_nodes, int32_t* carried, float fpu, float fpu_root, void* stream);
+/* mnk_search_selfplay_advance_opts (fpu_on = 0) or mnk_search_selfplay_advance_opts_fpu (fpu_on = 1) with FORCED PLAYOUTS
+ * AND POLICY TARGET PRUNING (the rule: mnk_puct_step_forced at leaves = 1, with or without the solver): their arguments,
+ * then fpu_on and forced_k before the stream.  Row i's ply p_i FORCES iff its root is NOISED by the rule above -- the ply
+ * is FULL, or noise_fast != 0 -- whether or not noise_alpha is 0.  On a ply that FORCES the selection at the root is
+ * mnk_puct_step_forced's, and in the launch that ends the ply n' = the clamped counts the move would be drawn from above,
+ * n'' = their pruned counts by mnk_puct_step_forced's rule; the move is drawn from n'', and a FULL ply records n'' in the
+ * ring (a fast ply zero visits, as before).  A ply that does not force is searched, played and recorded exactly as by
+ * mnk_search_selfplay_advance_opts[_fpu].  Nothing else differs: the backup, the budget, the noise, ring slot, the Philox
+ * word of the move, labels, stats, the reset.  With full_threshold = 2^32 and rows that start together the launches are
+ * the lockstep player's with mnk_puct_step_forced in the place of its step, bit for bit, with the exceptions
+ * mnk_search_selfplay_advance_opts states for the solver.  forced_k: finite, > 0; fpu_on in {0, 1}; fpu and fpu_root are
+ * checked when fpu_on = 1 (else MNK_EINVAL); every host check runs before anything is enqueued; N = 0 returns MNK_OK after
+ * them. */
+int mnk_search_selfplay_advance_opts_forced(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n,
+                                            int k, int iterations, int fast_iterations, uint64_t full_threshold,
+                                            const void* priors, int priors_dtype, const void* values, int values_dtype,
+                                            float c, int temp_plies, uint64_t seed, const uint64_t* seed_dev,
+                                            int64_t env_id0, uint64_t* row_plies, int64_t T, uint64_t* ring_planes,
+                                            uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs, int leaf_dtype,
+                                            uint8_t* leaf_mask, uint8_t* fresh, uint64_t* plies_max, int64_t* stats,
+                                            int32_t* err, int solver, float noise_alpha, float noise_eps, int noise_fast,
+                                            float* root_priors, float fpu, float fpu_root, int fpu_on, float forced_k,
+                                            void* stream);
 /* mnk_search_selfplay_advance_opts for rows that search with L = leaves slots per row and evaluator call (the lockstep
  * player's mnk_puct_step_leaves / mnk_puct_step_solver inside the one launch).  Every argument but leaves and row_sims,
  * and every rule not named here, is mnk_search_selfplay_advance_opts's.

@@ -6,13 +6,14 @@
 // search with L leaves per row and evaluation (a round = L backups, then L selections under virtual visits), so the
 // evaluator sees I / L + 1 batches of N * L rows.  mnk_puct_step_solver is mnk_puct_step_leaves with exact proofs of wins,
 // draws and losses in the backup (a 2-bit proof per node, propagated up the leaf's path), mnk_puct_step_fpu either of them
-// with first-play urgency, mnk_puct_step_gumbel mnk_puct_step with a Gumbel root.  The rule: include/mnk_hip.h.
+// with first-play urgency, mnk_puct_step_forced any of those with forced playouts and policy target pruning,
+// mnk_puct_step_gumbel mnk_puct_step with a Gumbel root.  The rule: include/mnk_hip.h.
 //
 // What is here: one begin kernel and one rebase kernel (an entry point without `leaves` launches them with 1: the layout of
-// one leaf is the layout without the argument); the moves; ONE body of a step, puct_step_row, which the six step kernels
+// one leaf is the layout without the argument); the moves; ONE body of a step, puct_step_row, which the ten step kernels
 // instantiate -- k_puct_step and k_puct_step_gumbel with one leaf and the walk without virtual visits,
-// k_puct_step_leaves<SOLVER, FPU> as the round -- around the pieces of mnk_puct_tree.h; and the host side: one argument
-// block, one check of it, one launch shape.
+// k_puct_step_leaves<SOLVER, FPU, FORCED> as the round -- around the pieces of mnk_puct_tree.h; and the host side: one
+// argument block, one check of it, one launch shape.
 #include "mnk_host.h"
 #include "mnk_wave_rows.h"
 #include "mnk_puct_tree.h"
@@ -255,6 +256,53 @@ __device__ __forceinline__ void puct_move(const MnkPuctStepArgs& a, const MnkPuc
   }
 }
 
+// puct_move<SOLVER> of a search with forced playouts (the rule: include/mnk_hip.h, mnk_puct_step_forced): the counts n' of
+// puct_move go to raw_visits, and visits and the move take the pruned counts n'' (puct_prune_root, puct_pruned_count;
+// nothing is pruned when the solver keeps the WIN children alone).  pr = the root's stored priors.  A cell's n'' is
+// computed again wherever it is read -- the store, the sum, the pick -- from the same inputs: no scratch.
+template <bool SOLVER>
+__device__ __forceinline__ void puct_move_forced(const MnkPuctStepArgs& a, const MnkPuctNode* node, const float* pr,
+                                                 const uint16_t* child, int nodes, bool live, int64_t i, int lane,
+                                                 int8_t* proof, float forced_k, int32_t* raw_visits) {
+  const int C = a.g.C;
+  const bool sample = a.temperature == 1 && !a.deterministic;
+  const uint32_t x = puct_move_draw(a, i);
+  int move = (int)__umulhi(x, (uint32_t)C);  // no legal cell: a draw over all C cells
+  uint32_t maxn = 0u, tot = 0u;
+  int keep = 0;
+  if constexpr (SOLVER) keep = puct_root_keep(C, node, child, nodes, live, lane, maxn, tot);
+  auto kid = [&](int q) { return puct_root_kid(C, node, child, nodes, live, q); };  // (n = 0 for q >= C)
+  auto count = [&](int q) { return puct_kept_count(kid(q), keep); };
+  MnkPuctPrune pp = puct_prune_root(C, forced_k, a.c, node, pr, child, nodes, live, count, lane);
+  if (keep == 1) pp.on = false;
+  auto pruned = [&](int q) { return puct_pruned_count(pp, q, count(q), kid(q), q < C ? pr[q] : 0.0f); };
+  maxn = 0u;
+  tot = 0u;
+  for (int q = lane; q < C; q += 64) {
+    const uint32_t na = pruned(q);
+    if (raw_visits) raw_visits[i * C + q] = (int32_t)count(q);
+    if (a.visits) a.visits[i * C + q] = (int32_t)na;
+    maxn = max(maxn, na);
+    tot += na;
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    maxn = max(maxn, (uint32_t)__shfl_xor((int)maxn, off, 64));
+    tot += (uint32_t)__shfl_xor((int)tot, off, 64);
+  }
+  if (maxn) mnk_pick_by_visits(C, x, sample, maxn, tot, lane, pruned, move);
+  if (lane == 0) {
+    a.actions[i] = move;
+    if constexpr (SOLVER) {
+      const uint32_t pf = MNK_PUCT_PROOF(node[0].info);  // from the view of the side that is NOT to move
+      if (a.root_value) a.root_value[i] = pf ? (float)((int)pf - 2) : __fdiv_rn(-node[0].w, (float)node[0].n);
+      if (proof) proof[i] = pf ? (int8_t)((int)pf - 2) : (int8_t)MNK_PROOF_UNKNOWN;
+    } else {
+      if (a.root_value) a.root_value[i] = __fdiv_rn(-node[0].w, (float)node[0].n);
+    }
+  }
+}
+
 // The move, the visits, the root value and the improved policy (puct_gumbel_policy, mnk_puct_tree.h) of row i, after its
 // last backup (the rule: include/mnk_hip.h, mnk_puct_step_gumbel).  pr = the root's stored priors (node 0's row), cl its
 // child row.
@@ -299,11 +347,13 @@ __device__ __forceinline__ void puct_move_gumbel(const MnkPuctStepArgs& a, const
 //   FPU     a free cell without a visit scores from its parent's own mean value (fpu below the root, fpu_root at it).  The
 //           rule: mnk_puct_step_fpu.
 //   GUMBEL  the root's part of the walk is puct_gumbel_pick (gm: the row's Gumbel inputs).  The rule: mnk_puct_step_gumbel.
+//   FORCED  forced playouts: at the root a visited child short of its floor of visits is selected before any other
+//           (forced_k; the kernel's move prunes them again).  The rule: mnk_puct_step_forced.
 // move(r, nodes, live): the kernel's move on a.last.
-template <int NW, int CN, int CK, bool VL, bool SOLVER, bool FPU, bool GUMBEL, class Move>
+template <int NW, int CN, int CK, bool VL, bool SOLVER, bool FPU, bool GUMBEL, class Move, bool FORCED = false>
 __device__ __forceinline__ void puct_step_row(const MnkPuctStepArgs& a, int leaves, int64_t i, uint32_t* pos, int lane,
                                               Move move, float fpu = 0.0f, float fpu_root = 0.0f,
-                                              const MnkPuctGumbel* gm = nullptr) {
+                                              const MnkPuctGumbel* gm = nullptr, float forced_k = 0.0f) {
   const int C = a.g.C, NWg = a.g.NW, I = a.I;
   const MnkPuctRow r = puct_row(a.ws, i, NWg, C, I, leaves);
   const MnkPuctHeader h = puct_header(r.hdr, I);  // (nodes and live; depth and state are a slot's)
@@ -341,8 +391,9 @@ __device__ __forceinline__ void puct_step_row(const MnkPuctStepArgs& a, int leav
     MnkEnv<NW> e;
     if (open && nodes <= I) {
       puct_env_root<NW>(e, r.root, NWg);
-      nstate = puct_walk<NW, CN, CK, VL, SOLVER, GUMBEL, FPU>(a.g, e, I, a.c, r.node, r.prior, r.child, path, nodes, d,
-                                                              lane, nodes0, active, epath, edepth, gm, fpu, fpu_root);
+      nstate = puct_walk<NW, CN, CK, VL, SOLVER, GUMBEL, FPU, FORCED>(a.g, e, I, a.c, r.node, r.prior, r.child, path,
+                                                                      nodes, d, lane, nodes0, active, epath, edepth, gm,
+                                                                      fpu, fpu_root, forced_k, true);
     }
     if (nstate) {
       active |= 1u << j;
@@ -370,14 +421,17 @@ __global__ void __launch_bounds__(256) k_puct_step(MnkPuctStepArgs a) {
   });
 }
 
-// the round; proof is read with SOLVER only, fpu and fpu_root with FPU
-template <int NW, int CN, int CK, bool SOLVER, bool FPU>
-__global__ void __launch_bounds__(256) k_puct_step_leaves(MnkPuctStepArgs a, int8_t* proof, float fpu, float fpu_root) {
+// the round; proof is read with SOLVER only, fpu and fpu_root with FPU, forced_k and raw_visits with FORCED
+template <int NW, int CN, int CK, bool SOLVER, bool FPU, bool FORCED = false>
+__global__ void __launch_bounds__(256)
+k_puct_step_leaves(MnkPuctStepArgs a, int8_t* proof, float fpu, float fpu_root, float forced_k, int32_t* raw_visits) {
   MNK_PUCT_WAVE_ROW(a.N)
   auto move = [&](const MnkPuctRow& r, int nodes, bool live) {
-    puct_move<SOLVER>(a, r.node, r.child, nodes, live, i, lane, proof);
+    if constexpr (FORCED) puct_move_forced<SOLVER>(a, r.node, r.prior, r.child, nodes, live, i, lane, proof, forced_k, raw_visits);
+    else puct_move<SOLVER>(a, r.node, r.child, nodes, live, i, lane, proof);
   };
-  puct_step_row<NW, CN, CK, true, SOLVER, FPU, false>(a, a.leaves, i, pos, lane, move, fpu, fpu_root);
+  puct_step_row<NW, CN, CK, true, SOLVER, FPU, false, decltype(move), FORCED>(a, a.leaves, i, pos, lane, move, fpu, fpu_root,
+                                                                              nullptr, forced_k);
 }
 
 // one leaf, the root a Gumbel root (the same workspace as k_puct_step's)
@@ -481,17 +535,25 @@ static int puct_step_check(void* workspace, int64_t N, int m, int n, int k, int 
   return MNK_OK;
 }
 
-// the round's launch: which of the four instantiations
+// the round's launch: which of the eight instantiations (forced: forced_k is read, finite and > 0)
 static int puct_step_round(const MnkPuctStepArgs& a, bool solver, bool with_fpu, int8_t* proof, float fpu, float fpu_root,
-                           void* stream, const char* what) {
+                           void* stream, const char* what, bool forced = false, float forced_k = 0.0f,
+                           int32_t* raw_visits = nullptr) {
   if (with_fpu && (!(fpu >= 0.0f && fpu <= 3.0e38f) || !(fpu_root >= 0.0f && fpu_root <= 3.0e38f))) return MNK_EINVAL;
+  if (forced && !(forced_k > 0.0f && forced_k <= 3.0e38f)) return MNK_EINVAL;
   if (a.N == 0) return MNK_OK;
-#define MNK_PUCT_ROUND(SOLVER, FPU) \
-  MNK_DISPATCH(a.g, puct_launch(k_puct_step_leaves<NW, CN, CK, SOLVER, FPU>, a.N, stream, a, proof, fpu, fpu_root))
-  if (solver && with_fpu) MNK_PUCT_ROUND(true, true);
-  else if (with_fpu) MNK_PUCT_ROUND(false, true);
-  else if (solver) MNK_PUCT_ROUND(true, false);
-  else MNK_PUCT_ROUND(false, false);
+#define MNK_PUCT_ROUND(SOLVER, FPU, FORCED)                                                                          \
+  MNK_DISPATCH(a.g, puct_launch(k_puct_step_leaves<NW, CN, CK, SOLVER, FPU, FORCED>, a.N, stream, a, proof, fpu, fpu_root, \
+                                forced_k, raw_visits))
+  if (forced) {
+    if (solver && with_fpu) MNK_PUCT_ROUND(true, true, true);
+    else if (with_fpu) MNK_PUCT_ROUND(false, true, true);
+    else if (solver) MNK_PUCT_ROUND(true, false, true);
+    else MNK_PUCT_ROUND(false, false, true);
+  } else if (solver && with_fpu) MNK_PUCT_ROUND(true, true, false);
+  else if (with_fpu) MNK_PUCT_ROUND(false, true, false);
+  else if (solver) MNK_PUCT_ROUND(true, false, false);
+  else MNK_PUCT_ROUND(false, false, false);
 #undef MNK_PUCT_ROUND
   return mnk_launch_status(what);
 }
@@ -569,6 +631,21 @@ int mnk_puct_step_fpu(void* workspace, int64_t N, int m, int n, int k, int itera
                                                         : MNK_EINVAL;
   if (rc != MNK_OK) return rc;
   return puct_step_round(a, solver != 0, true, solver ? proof : nullptr, fpu, fpu_root, stream, "puct_step_fpu");
+}
+
+int mnk_puct_step_forced(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,
+                         int priors_dtype, const void* values, int values_dtype, float c, int last, int temperature,
+                         uint64_t seed, const uint64_t* seed_dev, uint64_t step, const uint64_t* step_dev, int64_t env_id0,
+                         int deterministic, void* leaf_obs, int leaf_dtype, uint8_t* leaf_mask, int64_t* actions,
+                         int32_t* visits, float* root_value, int8_t* proof, int solver, float fpu, float fpu_root,
+                         int fpu_on, float forced_k, int32_t* raw_visits, void* stream) {
+  MnkPuctStepArgs a;
+  const int rc = leaves && (solver == 0 || solver == 1) && (fpu_on == 0 || fpu_on == 1)
+                     ? puct_step_check(MNK_PUCT_STEP_COMMON(leaves, temperature), &a)
+                     : MNK_EINVAL;
+  if (rc != MNK_OK) return rc;
+  return puct_step_round(a, solver != 0, fpu_on != 0, solver ? proof : nullptr, fpu, fpu_root, stream, "puct_step_forced",
+                         true, forced_k, raw_visits);
 }
 
 int mnk_puct_step_gumbel(void* workspace, int64_t N, int m, int n, int k, int iterations, int leaves, const void* priors,

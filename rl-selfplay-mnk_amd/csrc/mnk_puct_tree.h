@@ -345,6 +345,77 @@ __device__ __forceinline__ int puct_root_keep(int C, const MnkPuctNode* node, co
   return keep;
 }
 
+// ------------------------------------------------------------------ policy target pruning
+// What a search with forced playouts plays from and records (the rule: include/mnk_hip.h, mnk_puct_step_forced): shared by
+// its move, puct_move_forced, and by the ply of search self-play with per-row budgets.  One wave per row, a cell per lane.
+// The root's constants and the cell of most visits with its score (wave-uniform); on = false: nothing is pruned.
+struct MnkPuctPrune {
+  bool on;
+  int cstar;
+  float k, c, sq, t1, sstar;  // k; c; fsqrt((float)n_0); (float)(n_0 - 1); s*
+};
+// s_a(j): the score of the root's child `kid` through a cell of prior p, had it j visits
+__device__ __forceinline__ float puct_prune_score(const MnkPuctPrune& pp, const MnkPuctNode& kid, float p, uint32_t j) {
+  return __fadd_rn(__fdiv_rn(kid.w, (float)kid.n), __fdiv_rn(__fmul_rn(__fmul_rn(pp.c, p), pp.sq), (float)(1u + j)));
+}
+// count(q): n' of cell q, 0 for q >= C and where there is no child.  pr = the root's stored priors, `child` its child row.
+// The arg-max (ties to the lowest cell) by one pass and one __shfl_xor reduction; s* from the winner's record.
+template <class Count>
+__device__ __forceinline__ MnkPuctPrune puct_prune_root(int C, float k, float c, const MnkPuctNode* node, const float* pr,
+                                                        const uint16_t* child, int nodes, bool live, Count count,
+                                                        int lane) {
+  uint32_t bn = 0u;
+  int ba = 0x7fffffff;
+  for (int a = lane; a < C; a += 64) {
+    const uint32_t na = count(a);
+    if (na > bn) {  // (a rises: ">" keeps the lowest cell of a tie)
+      bn = na;
+      ba = a;
+    }
+  }
+#pragma unroll
+  for (int off = 32; off; off >>= 1) {
+    const uint32_t on = (uint32_t)__shfl_xor((int)bn, off, 64);
+    const int oa = __shfl_xor(ba, off, 64);
+    if (on > bn || (on == bn && oa < ba)) {
+      bn = on;
+      ba = oa;
+    }
+  }
+  MnkPuctPrune pp;
+  pp.on = bn != 0u;
+  pp.cstar = min(ba, C - 1);  // (bn = 0: no cell; nothing is read through it then)
+  pp.c = c;
+  pp.k = k;
+  const uint32_t n0 = max(node[0].n, 1u);
+  pp.sq = puct_sqrt_rn(n0);
+  pp.t1 = (float)(n0 - 1u);
+  pp.sstar = 0.0f;
+  if (pp.on) pp.sstar = puct_prune_score(pp, puct_root_kid(C, node, child, nodes, live, pp.cstar), pr[pp.cstar], bn);
+  return pp;
+}
+// n'' of cell a from its n' = na, its child's record and its prior.  The rule walks j upwards; s_a(j) does not increase
+// with j for p > 0 (a correctly rounded quotient by a growing divisor, then a correctly rounded sum), and neither does
+// "F * F >= t" turn false again as F grows, so both searches bisect: at most 2 * 24 probes a cell, no memory.
+__device__ __forceinline__ uint32_t puct_pruned_count(const MnkPuctPrune& pp, int a, uint32_t na, const MnkPuctNode& kid,
+                                                      float p) {
+  if (!pp.on || a == pp.cstar || na == 0u || p <= 0.0f) return na;
+  const float t = __fmul_rn(__fmul_rn(pp.k, p), pp.t1);
+  uint32_t lo = 0u, hi = na;  // min(n', F_a): the least F in [0, n') with F * F >= t, n' when there is none
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (__fmul_rn((float)mid, (float)mid) >= t) hi = mid;
+    else lo = mid + 1u;
+  }
+  uint32_t jl = na - lo, jh = na;  // the least j in [n' - min(n', F_a), n') with s_a(j) < s*, n' when there is none
+  while (jl < jh) {
+    const uint32_t mid = (jl + jh) >> 1;
+    if (puct_prune_score(pp, kid, p, mid) < pp.sstar) jh = mid;
+    else jl = mid + 1u;
+  }
+  return jl == 1u && na > 1u ? 0u : jl;
+}
+
 // ------------------------------------------------------------------ the Gumbel root
 // (k_puct_step_gumbel and k_search_selfplay_advance_gumbel)
 // What the root of row i reads besides the tree: its row of gscore (mnk_puct_gumbel_root), the table of considered visits
@@ -523,14 +594,20 @@ __device__ __forceinline__ float puct_fpu_q(uint64_t T, const MnkPuctNode& k, fl
 // FPU: first-play urgency (the rule: include/mnk_hip.h, mnk_puct_step_fpu).  A free cell without a visit scores with
 // q = max(q_v - r * mass, -1) in the place of 0, r = fpu_root at the root and fpu below it: puct_fpu_q, one more pass over
 // the node's child row and priors before the scoring loop, in its access shape.
-template <int NW, int CN, int CK, bool VL, bool SOLVER = false, bool GUMBEL = false, bool FPU = false>
+// FORCED: forced playouts at the root (the rule: include/mnk_hip.h, mnk_puct_step_forced), when `force` (wave-uniform: the
+// per-row loop's "this ply forces") is set.  A root cell whose child has a stored visit, is not proven LOSS and has
+// n'^2 < k * P * S' is of class 2, above SOLVER's two: the test stands beside the score in the per-cell loop (S' = nv - 1,
+// the nv the loop already has), and `bc` orders the candidates as it does for SOLVER -- no pass and no reduction more.
+template <int NW, int CN, int CK, bool VL, bool SOLVER = false, bool GUMBEL = false, bool FPU = false,
+          bool FORCED = false>
 __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, int I, float c, MnkPuctNode* node,
                                               const float* prior, uint16_t* child, uint16_t* path, int& nodes, int& d,
                                               int lane, int nodes0 = 0, uint32_t share = 0u,
                                               const uint16_t* epath = nullptr, int edepth = 0,
                                               const MnkPuctGumbel* gm = nullptr, float fpu = 0.0f,
-                                              float fpu_root = 0.0f) {
+                                              float fpu_root = 0.0f, float forced_k = 0.0f, bool force = false) {
   const int C = g.C;
+  constexpr bool CLS = SOLVER || FORCED;  // the candidates have classes: `bc` orders before the score
   int v = 0;
   for (;;) {
     uint32_t nxt = 0u;  // VL: where lane l's slot goes from v (0: not through v, or its leaf is v)
@@ -581,12 +658,14 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
       uint32_t na = 0u;
       float wa = 0.0f;
       [[maybe_unused]] int cls = 1;
+      [[maybe_unused]] uint32_t stored = 0u;  // FORCED: the child's n without the round's virtual visits
       if (ch) {
         const int kk = min((int)ch, nodes - 1);
         const MnkPuctNode k = node[kk];
         na = k.n;
         wa = k.w;
         if constexpr (SOLVER) cls = MNK_PUCT_PROOF(k.info) != 3u;
+        if constexpr (FORCED) stored = na;
         if (VL && share) {
           uint32_t vl = 0u;  // (nx is 0, never a child's id, for a slot that is not in `share`)
 #pragma unroll
@@ -597,7 +676,12 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
       }
       const float q = na ? __fdiv_rn(wa, (float)na) : (FPU ? qu : 0.0f);
       const float s = __fadd_rn(q, __fdiv_rn(__fmul_rn(__fmul_rn(c, pr[a]), sq), (float)(1u + na)));
-      if constexpr (SOLVER) {
+      if constexpr (FORCED) {  // (a child of this round has no stored visit: never forced)
+        if (v == 0 && force && stored && cls == 1 &&
+            __fmul_rn((float)na, (float)na) < __fmul_rn(__fmul_rn(forced_k, pr[a]), (float)(nv - 1u)))
+          cls = 2;
+      }
+      if constexpr (CLS) {
         if (ba == 0x7fffffff || cls > bc || (cls == bc && s > best)) {
           best = s;
           ba = a;
@@ -612,7 +696,7 @@ __device__ __forceinline__ uint32_t puct_walk(const MnkGeom& g, MnkEnv<NW>& e, i
     for (int off = 32; off; off >>= 1) {
       const float ob = __shfl_xor(best, off, 64);
       const int oa = __shfl_xor(ba, off, 64);
-      if constexpr (SOLVER) {
+      if constexpr (CLS) {
         const int oc = __shfl_xor(bc, off, 64);
         if (oa != 0x7fffffff &&
             (ba == 0x7fffffff || oc > bc || (oc == bc && (ob > best || (ob == best && oa < ba))))) {

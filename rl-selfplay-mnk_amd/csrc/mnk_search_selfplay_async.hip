@@ -8,7 +8,8 @@
 //
 // Three kernels live here: the plain launch; mnk_search_selfplay_advance_opts, the launch with two of the lockstep
 // player's options built in -- Dirichlet noise on the roots (mnk_puct_root_noise's draw, at the backup of a fresh tree's
-// root) and the solver (mnk_puct_step_solver's backup and selection; a ply ends as soon as its root is proven); and
+// root) and the solver (mnk_puct_step_solver's backup and selection; a ply ends as soon as its root is proven), and behind
+// template flags first-play urgency and forced playouts with policy target pruning (mnk_puct_step_forced's); and
 // mnk_search_selfplay_advance_keep, the launch with the options for rows that keep the played move's subtree from ply to
 // ply (the lockstep player's mnk_puct_rebase, inside the launch that plays the ply).  The steps they share with each other
 // and with the leaves and Gumbel kernels -- the row's prologue, the budget draw, the root's noise and visit counts, the end
@@ -101,11 +102,14 @@ __global__ void __launch_bounds__(256) k_search_selfplay_advance(MnkAdvanceArgs 
 // puct_walk's inner loop), and so is FPU, first-play urgency (puct_walk's, the rule: include/mnk_hip.h,
 // mnk_puct_step_fpu; fpu and fpu_root are read by the FPU form alone); the noise is a wave-uniform run-time branch that
 // only a wave whose pending leaf is the root of a fresh tree takes, once per ply.  nz.alpha = 0: no noise, and then the
-// launch has no dynamic LDS.
-template <int NW, int CN, int CK, bool SOLVER, bool FPU>
+// launch has no dynamic LDS.  FORCED: forced playouts and policy target pruning (the rule: include/mnk_hip.h,
+// mnk_puct_step_forced) on the plies the noise applies to -- `force`, wave-uniform: the ply is full, or noise_fast is set
+// -- in puct_walk's per-cell loop and, where the ply is played, over the counts the move is drawn from and the ring records
+// (puct_prune_root, puct_pruned_count); forced_k is read by the FORCED form alone.
+template <int NW, int CN, int CK, bool SOLVER, bool FPU, bool FORCED = false>
 __global__ void __launch_bounds__(256)
 k_search_selfplay_advance_opts(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_eps, int noise_fast, float* root_priors,
-                               float fpu, float fpu_root) {
+                               float fpu, float fpu_root, float forced_k) {
   __shared__ uint32_t lds_pos[MNK_PUCT_ROWS][2 * NW];
   extern __shared__ double lds_gamma[];  // with noise: [MNK_PUCT_ROWS][C], a root's log-gammas between the two passes
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -151,9 +155,33 @@ k_search_selfplay_advance_opts(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_ep
     const int64_t t = (int64_t)(bg.p % (uint64_t)a.T);
     const uint32_t x = mnk_rand_u32(bg.seed, (uint64_t)(a.env_id0 + i), bg.p, MNK_STREAM_SELFPLAY);
     uint16_t* rv = a.ring_visits + (t * a.N + i) * C;
-    for (int q = lane; q < C; q += 64) rv[q] = bg.full ? (uint16_t)visits_of(q) : (uint16_t)0;  // a fast ply: no policy target
     int move = 0;
-    mnk_pick_by_visits(C, x, (int64_t)(e.meta >> 1) < (int64_t)a.temp_plies, maxn, tot, lane, visits_of, move);
+    if constexpr (FORCED) {
+      // the pruned counts n'' in the place of n' = visits_of, on a ply that forces (else pp.on is false: n'' = n'); a
+      // cell's n'' is computed again wherever it is read -- the store, the sum, the pick -- from the same inputs
+      MnkPuctPrune pp;
+      pp.on = false;
+      if (bg.full || noise_fast) {
+        pp = puct_prune_root(C, forced_k, a.c, r.node, r.prior, r.child, nodes, true, visits_of, lane);
+        if (visits_of.keep == 1) pp.on = false;  // (the solver keeps the WIN children alone: nothing is pruned)
+      }
+      auto pruned = [&](int q) {
+        return puct_pruned_count(pp, q, visits_of(q), puct_root_kid(C, r.node, r.child, nodes, true, q),
+                                 q < C ? r.prior[q] : 0.0f);
+      };
+      tot = 0u;  // (the maximum is c*'s count, which is kept)
+      for (int q = lane; q < C; q += 64) {
+        const uint32_t na = pruned(q);
+        rv[q] = bg.full ? (uint16_t)na : (uint16_t)0;  // a fast ply: no policy target
+        tot += na;
+      }
+#pragma unroll
+      for (int off = 32; off; off >>= 1) tot += (uint32_t)__shfl_xor((int)tot, off, 64);
+      mnk_pick_by_visits(C, x, (int64_t)(e.meta >> 1) < (int64_t)a.temp_plies, maxn, tot, lane, pruned, move);
+    } else {
+      for (int q = lane; q < C; q += 64) rv[q] = bg.full ? (uint16_t)visits_of(q) : (uint16_t)0;  // a fast ply: no policy target
+      mnk_pick_by_visits(C, x, (int64_t)(e.meta >> 1) < (int64_t)a.temp_plies, maxn, tot, lane, visits_of, move);
+    }
     advance_finish_ply<NW, CN, CK>(a, e, pos, move, bg.p, t, i, lane);
     // ---- the search of the position reached: a fresh tree (no proof), its root the pending leaf
     advance_fresh_root<NW, CN>(a, r, pos, e, i, lane);
@@ -170,8 +198,9 @@ k_search_selfplay_advance_opts(MnkAdvanceArgs a, MnkPuctNoise nz, float noise_ep
   uint32_t nstate = 0u;  // nothing pending: a full tree shows its root again (it cannot happen: nodes <= n_root <= I)
   if (nodes <= I) {
     puct_env_root<NW>(e, r.root, NWg);
-    nstate = puct_walk<NW, CN, CK, false, SOLVER, false, FPU>(a.g, e, I, a.c, r.node, r.prior, r.child, r.path, nodes, d,
-                                                              lane, 0, 0u, nullptr, 0, nullptr, fpu, fpu_root);
+    nstate = puct_walk<NW, CN, CK, false, SOLVER, false, FPU, FORCED>(a.g, e, I, a.c, r.node, r.prior, r.child, r.path,
+                                                                      nodes, d, lane, 0, 0u, nullptr, 0, nullptr, fpu,
+                                                                      fpu_root, forced_k, bg.full || noise_fast);
     if (nstate == 0u) d = 0;
     puct_stage_selection<NW>(pos, e, nstate, r.root, NWg, lane);
   } else {
@@ -351,24 +380,33 @@ int mnk_search_selfplay_advance(void* workspace, uint64_t* planes, uint32_t* met
   return mnk_launch_status("search_selfplay_advance");
 }
 
-// (what mnk_search_selfplay_advance_opts and its _fpu form share: the option checks, then the launch)
+// (what mnk_search_selfplay_advance_opts and its _fpu and _forced forms share: the option checks, then the launch)
 static int advance_opts(const MnkAdvanceArgs& a, int solver, float noise_alpha, float noise_eps, int noise_fast,
-                        float* root_priors, bool with_fpu, float fpu, float fpu_root, void* stream) {
+                        float* root_priors, bool with_fpu, float fpu, float fpu_root, void* stream, bool forced = false,
+                        float forced_k = 0.0f) {
   if (mnk_advance_options_check(a.g, solver, noise_alpha, noise_eps, noise_fast) != MNK_OK) return MNK_EINVAL;
   if (with_fpu && !mnk_advance_fpu_ok(fpu, fpu_root)) return MNK_EINVAL;
+  if (forced && !(forced_k > 0.0f && forced_k <= 3.0e38f)) return MNK_EINVAL;
   if (a.N == 0) return MNK_OK;
   const MnkPuctNoise nz = mnk_advance_noise(noise_alpha);
   const size_t lds = mnk_advance_noise_lds(a.g, noise_alpha);
-#define MNK_ADVANCE_OPTS(SOLVER, FPU)                                                                                \
-  MNK_DISPATCH(a.g, mnk_advance_launch(k_search_selfplay_advance_opts<NW, CN, CK, SOLVER, FPU>, a, lds, stream, nz, \
-                                       noise_eps, noise_fast, root_priors, fpu, fpu_root))
+#define MNK_ADVANCE_OPTS(SOLVER, FPU, FORCED)                                                                    \
+  MNK_DISPATCH(a.g, mnk_advance_launch(k_search_selfplay_advance_opts<NW, CN, CK, SOLVER, FPU, FORCED>, a, lds, \
+                                       stream, nz, noise_eps, noise_fast, root_priors, fpu, fpu_root, forced_k))
+  if (forced) {
+    if (solver && with_fpu) MNK_ADVANCE_OPTS(true, true, true);
+    else if (with_fpu) MNK_ADVANCE_OPTS(false, true, true);
+    else if (solver) MNK_ADVANCE_OPTS(true, false, true);
+    else MNK_ADVANCE_OPTS(false, false, true);
+    return mnk_launch_status("search_selfplay_advance_opts_forced");
+  }
   if (with_fpu) {
-    if (solver) MNK_ADVANCE_OPTS(true, true);
-    else MNK_ADVANCE_OPTS(false, true);
+    if (solver) MNK_ADVANCE_OPTS(true, true, false);
+    else MNK_ADVANCE_OPTS(false, true, false);
     return mnk_launch_status("search_selfplay_advance_opts_fpu");
   }
-  if (solver) MNK_ADVANCE_OPTS(true, false);
-  else MNK_ADVANCE_OPTS(false, false);
+  if (solver) MNK_ADVANCE_OPTS(true, false, false);
+  else MNK_ADVANCE_OPTS(false, false, false);
 #undef MNK_ADVANCE_OPTS
   return mnk_launch_status("search_selfplay_advance_opts");
 }
@@ -398,6 +436,23 @@ int mnk_search_selfplay_advance_opts_fpu(void* workspace, uint64_t* planes, uint
   const int rc = mnk_advance_check(MNK_ADVANCE_COMMON(temp_plies), &a);
   if (rc != MNK_OK) return rc;
   return advance_opts(a, solver, noise_alpha, noise_eps, noise_fast, root_priors, true, fpu, fpu_root, stream);
+}
+int mnk_search_selfplay_advance_opts_forced(void* workspace, uint64_t* planes, uint32_t* meta, int64_t N, int m, int n,
+                                            int k, int iterations, int fast_iterations, uint64_t full_threshold,
+                                            const void* priors, int priors_dtype, const void* values, int values_dtype,
+                                            float c, int temp_plies, uint64_t seed, const uint64_t* seed_dev,
+                                            int64_t env_id0, uint64_t* row_plies, int64_t T, uint64_t* ring_planes,
+                                            uint16_t* ring_visits, int8_t* ring_z, void* leaf_obs, int leaf_dtype,
+                                            uint8_t* leaf_mask, uint8_t* fresh, uint64_t* plies_max, int64_t* stats,
+                                            int32_t* err, int solver, float noise_alpha, float noise_eps, int noise_fast,
+                                            float* root_priors, float fpu, float fpu_root, int fpu_on, float forced_k,
+                                            void* stream) {
+  MnkAdvanceArgs a;
+  const int rc = mnk_advance_check(MNK_ADVANCE_COMMON(temp_plies), &a);
+  if (rc != MNK_OK) return rc;
+  if (fpu_on != 0 && fpu_on != 1) return MNK_EINVAL;
+  return advance_opts(a, solver, noise_alpha, noise_eps, noise_fast, root_priors, fpu_on != 0, fpu, fpu_root, stream, true,
+                      forced_k);
 }
 
 // the LDS one workgroup of a plain launch may hold on the current device, read once (64 KiB where no device answers: the

@@ -119,6 +119,10 @@ SIGNATURES = {
     # mnk_puct_step_solver's arguments, then solver, fpu, fpu root before the stream: first-play urgency
     "mnk_puct_step_fpu": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i,
                           _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _vp],
+    # mnk_puct_step_fpu's arguments, then fpu on, forced k, raw visits (int32 [N][C]) before the stream: forced playouts
+    # and policy target pruning
+    "mnk_puct_step_forced": [_vp, _i64, _i, _i, _i, _i, _i, _vp, _i, _vp, _i, _f, _i, _i, _u64, _vp, _u64, _vp, _i64, _i,
+                             _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f, _f, _i, _f, _vp, _vp],
     # priors, priors dtype, mask, N, C, leaves, alpha, eps, then seed, seed_dev, step, step_dev, env_id0, out (f32
     # [N * leaves][C]), stream
     "mnk_puct_root_noise": [_vp, _i, _vp, _i64, _i, _i, _f, _f, _u64, _vp, _u64, _vp, _i64, _vp, _vp],
@@ -161,6 +165,10 @@ SIGNATURES = {
     "mnk_search_selfplay_advance_keep_fpu": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i, _u64,
                                              _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _f,
                                              _f, _i, _vp, _i, _i, _vp, _f, _f, _vp],
+    # mnk_search_selfplay_advance_opts_fpu's arguments, then fpu on, forced k before the stream
+    "mnk_search_selfplay_advance_opts_forced": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i,
+                                                _u64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp,
+                                                _i, _f, _f, _i, _vp, _f, _f, _i, _f, _vp],
     # mnk_search_selfplay_advance_opts's arguments with leaves behind the fast iterations and row sims (u32 [N]) before the
     # stream
     "mnk_search_selfplay_advance_leaves": [_vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _u64, _vp, _i, _vp, _i, _f, _i, _u64,

@@ -347,12 +347,23 @@ class PUCTSearchPolicy(Policy):
     reduction; 0.2 is their usual value, and ``fpu=0`` still differs from ``None`` (the parent's value, not 0).  Every
     step is then ``mnk_puct_step_fpu``, at any ``leaves``, with or without ``reuse``, ``solver`` and ``root_noise``; the
     evaluator sees the same batch shapes.  It does not combine with ``gumbel`` yet (``ValueError``).  ``None`` (the
-    default): the search above, launch for launch, and nothing is allocated."""
+    default): the search above, launch for launch, and nothing is allocated.
+
+    ``forced=k`` (a number, finite and > 0; KataGo's 2) turns on forced playouts and policy target pruning (Wu 2019,
+    section 3.2; the rule: include/mnk_hip.h, mnk_puct_step_forced) -- what makes ``root_noise`` useful as a policy target
+    at small ``iterations``.  At the root a visited child is selected before any other while its visits n satisfy ``n * n
+    < k * P * (root visits - 1)``, so a move the noise promotes is tried more than once; where the move is made those
+    visits are taken out again wherever PUCT alone would not have spent them (and a lone remaining visit is dropped), so
+    ``visits`` -- the counts the move is drawn from -- no longer sum to ``iterations``.  ``act(raw_visits=...)`` hands out
+    the counts before the pruning.  Every step is then ``mnk_puct_step_forced``, at any ``leaves``, with or without
+    ``reuse``, ``solver``, ``root_noise`` and ``fpu``; no launch and no buffer is added.  It does not combine with
+    ``gumbel`` (``ValueError``): Sequential Halving has its own allocation of the budget.  ``None`` (the default): the
+    search above, launch for launch."""
 
     def __init__(self, k: int, model=None, evaluator=None, iterations: int = 256, c: float = 1.25, temperature: int = 0,
                  leaf_dtype=torch.float32, seed=None, reuse: bool = False, tree_nodes: int = None, leaves: int = 1,
                  root_noise=None, solver: bool = False, gumbel: int = None, gumbel_c=(50.0, 0.5),
-                 gumbel_scale: float = 1.0, fpu=None):
+                 gumbel_scale: float = 1.0, fpu=None, forced=None):
         if (model is None) == (evaluator is None):
             raise ValueError("PUCTSearchPolicy needs exactly one of model and evaluator")
         self.k = int(k)
@@ -401,6 +412,9 @@ class PUCTSearchPolicy(Policy):
         self.fpu = self._checked_fpu(fpu)
         if self.fpu is not None and self.gumbel is not None:
             raise ValueError("fpu does not combine with gumbel yet")
+        self.forced = self._checked_forced(forced)
+        if self.forced is not None and self.gumbel is not None:
+            raise ValueError("forced does not combine with gumbel: Sequential Halving has its own allocation")
         self._bufs = None  # (key, workspace, leaf_obs, leaf_mask, noised priors or None)
         self._gumbel_bufs = None  # gumbel: (key, table, gscore, vroot)
 
@@ -434,6 +448,21 @@ class PUCTSearchPolicy(Policy):
             if not (math.isfinite(x) and 0.0 <= x <= 3.0e38):
                 raise ValueError(f"fpu: the reductions must be finite and >= 0, got {fpu!r}")
         return pair
+
+    @staticmethod
+    def _checked_forced(forced):
+        """None, or k as a float: finite and > 0 (as a float32 too)"""
+        if forced is None:
+            return None
+        try:
+            if isinstance(forced, (bool, str)):
+                raise ValueError
+            k = float(forced)
+        except (TypeError, ValueError):
+            raise ValueError(f"forced must be None or a number k > 0, got {forced!r}") from None
+        if not (math.isfinite(k) and k <= 3.0e38 and ctypes.c_float(k).value > 0.0):
+            raise ValueError(f"forced: k must be finite and > 0 as a float32, got {forced!r}")
+        return k
 
     @staticmethod
     def _checked_gumbel(gumbel, gumbel_c, gumbel_scale):
@@ -499,7 +528,7 @@ class PUCTSearchPolicy(Policy):
             self._bufs[1].zero_()
 
     def act(self, obs: Dict[str, torch.Tensor], deterministic: bool = False, visits=None, root_value=None,
-            carried=None, proof=None, policy=None) -> torch.Tensor:
+            carried=None, proof=None, policy=None, raw_visits=None) -> torch.Tensor:
         """``visits``: optional int32 ``[B, m*n]`` tensor that receives each row's root visit counts (an AlphaZero policy
         target; they sum to ``iterations`` on a row with a legal cell, to the carried visits plus ``iterations`` on a row
         that kept its tree); ``root_value``: optional float32 ``[B]`` tensor that receives the root's mean value for the
@@ -510,9 +539,12 @@ class PUCTSearchPolicy(Policy):
         wins alone when there is one, else all but the proven losses) and do not sum to ``iterations``, and
         ``root_value`` is exactly +1, 0 or -1 on a proven root; ``policy`` (``gumbel=m``): optional float32 ``[B, m*n]``
         tensor that receives the improved policy (it sums to 1 over the free cells; 0 on occupied cells and on a row
-        without a free cell)"""
+        without a free cell).  With ``forced=k`` ``visits`` are the pruned counts, and ``raw_visits``: optional int32 ``[B,
+        m*n]`` tensor that receives the counts before the pruning (what ``visits`` would be without it)"""
         if policy is not None and self.gumbel is None:
             raise ValueError("policy is an output of a search with a Gumbel root: it needs gumbel=m")
+        if raw_visits is not None and self.forced is None:
+            raise ValueError("raw_visits is an output of a search with forced playouts: it needs forced=k")
         observation = _canonical_observation(obs)
         b, _, m, n = observation.shape
         dev = observation.device
@@ -523,7 +555,8 @@ class PUCTSearchPolicy(Policy):
         for name, t, shape, dtype in (("visits", visits, (b, m * n), torch.int32),
                                       ("root_value", root_value, (b,), torch.float32),
                                       ("carried", carried, (b, 2), torch.int32), ("proof", proof, (b,), torch.int8),
-                                      ("policy", policy, (b, m * n), torch.float32)):
+                                      ("policy", policy, (b, m * n), torch.float32),
+                                      ("raw_visits", raw_visits, (b, m * n), torch.int32)):
             if t is not None and (t.shape != shape or t.dtype != dtype or not t.is_contiguous() or t.device != dev):
                 raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} {shape} tensor on {dev}")
         actions = torch.empty(b, dtype=torch.long, device=dev)
@@ -537,10 +570,15 @@ class PUCTSearchPolicy(Policy):
             # leaves = 1 stays on the entry points without the argument (the same results either way: include/mnk_hip.h)
             # (the solver's step takes `leaves` always, and the workspace the *_leaves entry points set up)
             # (so does the step with first-play urgency, which takes the solver as an argument)
-            sfx, lv = ("_leaves", (self.leaves,)) if self.leaves > 1 or self.solver or self.fpu is not None else ("", ())
+            # (and the step with forced playouts, which takes both)
+            sfx, lv = (("_leaves", (self.leaves,))
+                       if self.leaves > 1 or self.solver or self.fpu is not None or self.forced is not None else ("", ()))
             step, out = ("mnk_puct_step_solver", (mnk_hip.ptr(proof),)) if self.solver else ("mnk_puct_step" + sfx, ())
             if self.fpu is not None:
                 step, out = "mnk_puct_step_fpu", (mnk_hip.ptr(proof), int(self.solver), *self.fpu)
+            if self.forced is not None:
+                step, out = "mnk_puct_step_forced", (mnk_hip.ptr(proof), int(self.solver), *(self.fpu or (0.0, 0.0)),
+                                                     int(self.fpu is not None), self.forced, mnk_hip.ptr(raw_visits))
             if self.reuse:
                 mnk_hip.call("mnk_puct_rebase" + sfx, mnk_hip.ptr(observation), mnk_hip.obs_code(observation), b, m, n, k,
                              cap, self.tree_nodes - I, *lv, mnk_hip.ptr(ws), mnk_hip.ptr(leaf_obs), code,

@@ -35,6 +35,10 @@ the improved policy, drawn at the ring's ply counter like the noise -- and the r
 include/mnk_hip.h, mnk_puct_step_fpu): a move without a visit is valued at its parent's mean value less a reduction, not
 at 0, so a root that looks lost still concentrates its visits -- and its policy target -- on few moves.
 
+``forced=k`` searches with forced playouts and policy target pruning (``PUCTSearchPolicy(forced=k)``, the rule:
+include/mnk_hip.h, mnk_puct_step_forced): with ``root_noise`` a move the noise promotes is tried more than once, and the
+visits that PUCT alone would not have spent are taken out of the counts the step kernel plays from and records.
+
 ``AsyncSearchSelfPlay`` (below) is the same loop without the lockstep: one launch per evaluator call, a search budget per
 row and ply, rows that play on as soon as their search is done.  It takes ``root_noise`` and ``solver`` too, built into
 its one launch (``mnk_search_selfplay_advance_opts``): the noise of a row's ply is a function of (seed, row id, the row's
@@ -60,7 +64,7 @@ class SearchSelfPlay:
                  c: float = 1.25, temp_plies: int = None, capacity: int = None, seed=None, leaf_dtype=torch.float32,
                  device="cuda", reuse: bool = False, tree_nodes: int = None, leaves: int = 1, root_noise=None,
                  solver: bool = False, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0,
-                 fpu=None):
+                 fpu=None, forced=None):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -73,12 +77,12 @@ class SearchSelfPlay:
         capacity = 2 * C if capacity is None else int(capacity)
         if capacity < C:
             raise ValueError(f"capacity must be at least m*n = {C} plies, got {capacity}")
-        # (the policy checks model / evaluator, iterations, c, leaves, root_noise, fpu and leaf_dtype before anything touches the
-        # GPU)
+        # (the policy checks model / evaluator, iterations, c, leaves, root_noise, fpu, forced and leaf_dtype before anything
+        # touches the GPU)
         self.policy = PUCTSearchPolicy(self.k, model=model, evaluator=evaluator, iterations=iterations, c=c,
                                        temperature=0, leaf_dtype=leaf_dtype, seed=seed, reuse=reuse, tree_nodes=tree_nodes,
                                        leaves=leaves, root_noise=root_noise, solver=solver, gumbel=gumbel,
-                                       gumbel_c=gumbel_c, gumbel_scale=gumbel_scale, fpu=fpu)
+                                       gumbel_c=gumbel_c, gumbel_scale=gumbel_scale, fpu=fpu, forced=forced)
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
@@ -248,6 +252,15 @@ class AsyncSearchSelfPlay:
     full the games are those of ``SearchSelfPlay(fpu=..., same options)`` of the same seed, bit for bit (the solver
     excepted, as above).  With ``leaves > 1`` or ``gumbel`` it raises ``ValueError``.
 
+    ``forced=k`` is ``SearchSelfPlay``'s ``forced``: forced playouts at the root and policy target pruning where the ply is
+    played (the rule: include/mnk_hip.h, mnk_puct_step_forced and mnk_search_selfplay_advance_opts_forced), on exactly the
+    plies the built-in noise applies to -- the full plies, and the fast ones too under ``noise_on_fast=True`` -- with or
+    without ``root_noise``, ``solver`` and ``fpu``.  A ply that does not force is searched, played and recorded as without
+    the option; a full ply records the pruned counts.  ``advance`` then calls ``mnk_search_selfplay_advance_opts_forced``;
+    with every ply full the games are those of ``SearchSelfPlay(forced=k, same options)`` of the same seed, bit for bit
+    (the solver excepted, as above).  With ``keep_tree``, ``leaves > 1`` or ``gumbel`` it raises ``ValueError`` (DESIGN
+    section 10).
+
     With no option ``advance`` calls ``mnk_search_selfplay_advance``, as before; with ``root_noise`` or ``solver`` it
     calls ``mnk_search_selfplay_advance_opts``; with ``keep_tree`` it calls ``mnk_search_selfplay_advance_keep``, which
     takes the other two; with ``leaves > 1`` it calls ``mnk_search_selfplay_advance_leaves``, which takes ``root_noise``
@@ -257,7 +270,8 @@ class AsyncSearchSelfPlay:
                  fast_iterations: int = None, full_prob: float = 1.0, c: float = 1.25, temp_plies: int = None,
                  capacity: int = None, seed=None, leaf_dtype=torch.float32, device="cuda", root_noise=None,
                  noise_on_fast: bool = False, solver: bool = False, keep_tree: bool = False, tree_nodes: int = None,
-                 leaves: int = 1, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0, fpu=None):
+                 leaves: int = 1, gumbel: int = None, gumbel_c=(50.0, 0.5), gumbel_scale: float = 1.0, fpu=None,
+                 forced=None):
         self.m, self.n, self.k, self.num_envs = int(m), int(n), int(k), int(num_envs)
         C = self.m * self.n
         self.temp_plies = C // 4 if temp_plies is None else int(temp_plies)
@@ -306,6 +320,12 @@ class AsyncSearchSelfPlay:
                 raise ValueError("fpu does not combine with gumbel yet")
             if self.leaves > 1:
                 raise ValueError("fpu does not combine with leaves > 1 in the per-row loop yet")
+        self.forced = PUCTSearchPolicy._checked_forced(forced)
+        if self.forced is not None:
+            for name, on in (("gumbel", self.gumbel is not None), ("keep_tree=True", self.keep_tree),
+                             ("leaves > 1", self.leaves > 1)):
+                if on:
+                    raise ValueError(f"forced does not combine with {name} in the per-row loop yet")
         self.env = TorchVectorMnkEnv(self.m, self.n, self.k, self.num_envs, device=device)
         dev = self.env._dev
         self.buffer = SearchReplayBuffer(capacity, self.num_envs, self.m, self.n, dev)
@@ -384,6 +404,11 @@ class AsyncSearchSelfPlay:
                 alpha, eps = self.root_noise or (0.0, 0.0)
                 mnk_hip.call("mnk_search_selfplay_advance_leaves", *head, self.leaves, *tail, int(self.solver), alpha, eps,
                              int(self.noise_on_fast), mnk_hip.ptr(self.root_priors), mnk_hip.ptr(self.row_sims), stream)
+            elif self.forced is not None:
+                alpha, eps = self.root_noise or (0.0, 0.0)
+                mnk_hip.call("mnk_search_selfplay_advance_opts_forced", *args, int(self.solver), alpha, eps,
+                             int(self.noise_on_fast), mnk_hip.ptr(self.root_priors), *(self.fpu or (0.0, 0.0)),
+                             int(self.fpu is not None), self.forced, stream)
             elif self.fpu is not None:
                 alpha, eps = self.root_noise or (0.0, 0.0)
                 opts = (*args, int(self.solver), alpha, eps, int(self.noise_on_fast), mnk_hip.ptr(self.root_priors))
