@@ -69,6 +69,20 @@ def positions(m, n, k, count, seed, max_fill=1.0):
     return obs
 
 
+def mostly_full(m, n, k, count, seed, fill=0.75):
+    """positions filled to about ``fill``: a drawn board less stones taken off at random, either side to move (no run
+    on the board); the last row a finished game, a run of the opponent along row 0.  For the boards on which the numpy
+    rules take too long from positions with many free cells"""
+    from puct_solver_cases import drawn_board  # (that module imports this one)
+
+    rng, full = np.random.default_rng(seed), drawn_board(m, n, k)
+    obs = np.zeros((count, 2, m, n), np.float32)
+    for i in range(count):
+        obs[i] = full[:: 1 if i % 2 else -1] & (rng.random((m, n)) < fill)
+    obs[-1, 1, 0, :k], obs[-1, 0, 0, :k] = 1, 0
+    return obs
+
+
 def header_constants():
     return dict(re.findall(r"#define (MNK_\w+) (\d+)", open(HEADER).read()))
 

@@ -14,7 +14,7 @@ import numpy as np
 from oracle.packing import unpack_boards
 from puct_forced_rule import AsyncOptsForcedRule, ForcedPuct
 from puct_solver_cases import C_PUCT, ENV_ID0, SEED
-from search_selfplay_async_fpu_cases import FAINT, NOISE, late_start
+from search_selfplay_async_fpu_cases import FAINT, NOISE
 from search_selfplay_async_keep_cases import FAST, FULL, THRESHOLD, start_state
 from tactical_rule import random_positions
 
@@ -69,7 +69,12 @@ BOARDS = {"3x3x3": ((3, 3, 3), 12, 0.125, 1.0),      # one pass per lane
           "7x9x5": ((7, 9, 5), 16, 0.25, 1.0),       # a sibling of a built-in variant
           "5x5x4": ((5, 5, 4), 20, 0.0625, 0.75),    # the generic form
           "19x19x5": ((19, 19, 5), 8, 0.25, 1.0),    # the multi-word form
-          "12x12x5": ((12, 12, 5), 8, 0.125, 1.0)}   # generic, five words
+          "12x12x5": ((12, 12, 5), 8, 0.125, 1.0),   # generic, five words
+          "12x13x5": ((12, 13, 5), 16, 0.25, 1.0),   # <6,13,5>: 156 cells for the variant's 169
+          "16x15x5": ((16, 15, 5), 12, 0.25, 1.0),   # <8,15,5>: 240 cells for 225, a plane that fills its last word
+          "7x9x7": ((7, 9, 7), 12, 0.25, 1.0),       # generic, three words: the four-word instantiation
+          "17x17x5": ((17, 17, 5), 12, 0.25, 1.0),   # generic, ten words: the sixteen-word instantiation
+          "25x25x5": ((25, 25, 5), 8, 0.25, 1.0)}    # generic, 21 words: the 32-word instantiation
 SPIKES = {"12x12x5": 2}  # boards with fewer than three spike cells: the first of ``spikes_of``
 # L, solver, fpu, temperature: the whole cross (an act of these budgets takes milliseconds)
 OPTIONS = [(L, solver, fpu, t) for L in (1, 4) for solver in (False, True) for fpu in (None, FPU) for t in (0, 1)]
@@ -118,6 +123,31 @@ EDGES = {"above": dict(above=5), "zero": dict(zero=0, lost=True)}
 def edge_reference(which, L):
     obs, seen = rows_of(EDGE_NAME), []
     rule = new_rule(EDGE_NAME, L, False, None, seen=seen, evaluator=evaluator_of(EDGE_NAME, **EDGES[which]))
+    return obs, rule.act(obs, step=2), seen, rule
+
+
+# the floor's t = k P (n_0 - 1) on the large generic boards: under the evaluator for which every move looks bad, with a
+# spike prior of 1/8, I = 16 and four leaves, cells are pruned down to n' - F with n' >= F + 2, so that a floor taken from
+# n_0 in the place of n_0 - 1 leaves other counts (tests/test_puct_forced_cpu.py plants it).  None of the cases of BOARDS
+# on a board of more than 256 cells tells the two apart
+FLOOR_NAMES, FLOOR_I, FLOOR_SPIKE, FLOOR_L = ("17x17x5", "25x25x5"), 16, 0.125, 4
+
+
+def floor_evaluator(name, **kw):
+    m, n, k = BOARDS[name][0]
+    return spike_np(m * n, spikes_of(m, n, k), FLOOR_SPIKE, 1.0, lost=True, **kw)
+
+
+def floor_rule(name, seen=None):
+    k = BOARDS[name][0][2]
+    return ForcedPuct(k, FLOOR_I, C_PUCT, floor_evaluator(name), FLOOR_L, seed=SEED, env_id0=ENV_ID0, leaves=seen, fpu=FPU,
+                      forced=K_FORCED)
+
+
+@functools.lru_cache(maxsize=None)
+def floor_reference(name):
+    obs, seen = rows_of(name), []
+    rule = floor_rule(name, seen)
     return obs, rule.act(obs, step=2), seen, rule
 
 
@@ -184,9 +214,7 @@ N = ROWS
 
 
 def state_of(board, start):
-    if start == "late":
-        return late_start(*board, N)
-    return start_state(board, start)
+    return start_state(board, start)  # ("late": ``late_start`` of N rows)
 
 
 def free_spikes(board, state):
@@ -211,6 +239,14 @@ ASYNC_CASES = [
     ((19, 19, 5), "golden", 4, 150, 6, FAINT, False, True, FPU),
     ((12, 12, 5), "golden", 4, 150, 6, None, False, False, None),
     ((7, 7, 4), None, 4, 500, 6, NOISE, False, True, FPU),
+    # the variants <6,13,5> and <8,15,5> and the four-word generic form.  (Noise only where no stored row is two stones
+    # short of a drawn board, as in tests/search_selfplay_async_fpu_cases.py.)
+    ((12, 13, 5), "golden", 4, 150, 6, None, False, True, FPU),
+    ((16, 15, 5), "golden", 4, 150, 6, None, False, False, FPU),
+    ((7, 9, 7), "late", 4, 150, 6, NOISE, False, True, None),
+    # the generic forms of sixteen and of thirty-two words: ten and 21 words a plane
+    ((17, 17, 5), "late", 4, 150, 6, NOISE, False, True, FPU),
+    ((25, 25, 5), "late", 4, 150, 6, NOISE, False, True, FPU),
 ]
 
 

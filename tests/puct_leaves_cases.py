@@ -28,7 +28,11 @@ CASES = {
     # the generic forms of four and of eight words
     "7x9x7": ((7, 9, 7), 3, 16, (4,)),                   # three words
     "12x12x5": ((12, 12, 5), 3, 16, (4,)),               # five words
+    # the generic forms of sixteen and of thirty-two words
+    "17x17x5": ((17, 17, 5), 3, 8, (1, 4)),              # ten words; 289 cells: five trips, leaf rows of 289 bytes
+    "25x25x5": ((25, 25, 5), 3, 8, (1, 4)),              # 21 words, an odd count; 625 cells: ten trips
 }
+LARGE = {"17x17x5": "uint8", "25x25x5": "bfloat16"}      # and the leaf dtype each takes in the GPU test's dtype case
 PARAMS = [(name, L) for name, (_, _, _, Ls) in CASES.items() for L in Ls]
 
 

@@ -32,9 +32,7 @@ def late_start(m, n, k, rows, seed=1):
 
 
 def state_of(board, start):
-    if start == "late":
-        return late_start(*board, N)
-    return start_state(board, start)
+    return start_state(board, start)  # ("late": ``late_start`` of N rows)
 
 
 # board, start, temp_plies, rounds, seed, root_noise, solver, keep_tree, tree_nodes.  The rows are N, or as many as a
@@ -63,6 +61,12 @@ CASES = [
     ((12, 13, 5), "golden", 4, 150, 6, None, True, True, 13),
     ((12, 12, 5), "golden", 4, 150, 6, None, True, False, None),
     ((7, 7, 4), None, 4, 500, 6, NOISE, False, False, None),
+    # both entry points on the generic forms of sixteen and of thirty-two words (ten and 21 words a plane), from a
+    # computed start: no row of ``late_start`` has a root with a single free cell, so the noise may be on
+    ((17, 17, 5), "late", 4, 150, 6, NOISE, True, False, None),
+    ((25, 25, 5), "late", 4, 150, 6, NOISE, False, True, 13),
+    ((17, 17, 5), "late", 4, 150, 6, None, True, True, 13),
+    ((25, 25, 5), "late", 4, 150, 6, NOISE, True, False, None),
 ]
 
 

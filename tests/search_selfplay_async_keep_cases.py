@@ -29,13 +29,26 @@ MIXED = [
     # the solver under keep_nodes = 2: the child that proved a carried root is dropped by the truncation while an older
     # sibling stays, and the root then starts unknown (twice in this run; five roots keep their proof)
     ((3, 3, 3), 7, "float32", "float32", False, 2, 200, None, 6, None, False, True, 8, "exact"),
+    # the generic forms of sixteen and of thirty-two words (ten and 21 words a plane), from a computed start
+    ((17, 17, 5), 5, "uint8", "float32", False, 4, 150, "late", 6, None, False, True, 13, "peaked"),
+    ((25, 25, 5), 5, "float32", "bfloat16", False, 4, 150, "late", 6, NOISE, False, False, 13, "peaked"),
 ]
+TRUNCATED_SOLVER = 6  # the case of the comment above it
+
+
+LATE_ROWS = 5  # the rows of a "late" start
 
 
 def start_state(board, start):
+    """None, a stored state ("golden") or a computed one ("late": ``late_start`` of
+    tests/search_selfplay_async_fpu_cases.py, LATE_ROWS rows -- no fixture, so any board)"""
     if start is None:
         return None
     m, n, k = board
+    if start == "late":
+        from search_selfplay_async_fpu_cases import late_start  # (that module imports this one)
+
+        return late_start(m, n, k, LATE_ROWS)
     with np.load(GOLDEN) as z:
         return z[f"{m}x{n}x{k}_planes"], z[f"{m}x{n}x{k}_meta"]
 

@@ -6,7 +6,7 @@ import numpy as np
 import pytest
 import torch
 
-from player_cases import MC, _score, hip, positions  # noqa: F401 (hip: the fixture)
+from player_cases import MC, _score, hip, mostly_full, positions  # noqa: F401 (hip: the fixture)
 from playout_rule import playout_moves
 from tactical_rule import completions
 
@@ -16,11 +16,15 @@ OBS_DTYPES = (torch.float32, torch.bfloat16, torch.uint8)
 
 # ----------------------------------------------------------------------------- 1. bit for bit against the rule
 @pytest.mark.parametrize("board,rows,ps", [((3, 3, 3), 40, (1, 3, 16)), ((9, 9, 5), 12, (3, 8)), ((19, 19, 5), 4, (3,)),
-                                           ((4, 4, 3), 24, (1, 5, 7)), ((7, 9, 7), 8, (3, 4))])
+                                           ((4, 4, 3), 24, (1, 5, 7)), ((7, 9, 7), 8, (3, 4)),
+                                           ((17, 17, 5), 5, (1, 3)), ((25, 25, 5), 5, (1, 3))])
 def test_counts_and_actions_equal_the_rule(hip, board, rows, ps):
-    """(3x3x3, 9x9x5, 19x19x5: built-in variants; 4x4x3, 7x9x7: the generic NW forms)"""
+    """(3x3x3, 9x9x5, 19x19x5: built-in variants; 4x4x3, 7x9x7: the generic NW forms; 17x17x5, 25x25x5: those of sixteen
+    and of thirty-two words, ten and 21 words a plane, from positions three quarters full -- the numpy rule plays every
+    playout out, and from an empty 25x25 board that takes it seconds a row)"""
     m, n, k = board
-    obs = positions(m, n, k, rows, m * 100 + n * 10 + k)
+    seed = m * 100 + n * 10 + k
+    obs = mostly_full(m, n, k, rows, seed) if board in ((17, 17, 5), (25, 25, 5)) else positions(m, n, k, rows, seed)
     finished = [i for i in range(rows) if completions(obs[i:i + 1, 1], np.ones((1, m, n), bool), k).any()
                 or completions(obs[i:i + 1, 0], np.ones((1, m, n), bool), k).any()]
     assert finished  # boards that already hold a run are in the comparison

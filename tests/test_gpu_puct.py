@@ -68,6 +68,7 @@ def act(hip, obs_np, k, I, evaluator, seed, step=0, env_id0=0, dtype=torch.float
 @pytest.mark.parametrize("board,rows,I", [
     ((3, 3, 3), 24, 40), ((9, 9, 5), 8, 96), ((13, 13, 5), 4, 48), ((15, 15, 5), 4, 40), ((19, 19, 5), 4, 48),
     ((7, 7, 4), 8, 64), ((12, 12, 5), 4, 40), ((7, 9, 7), 4, 40),  # (generic NW forms: two, eight and four words)
+    ((17, 17, 5), 3, 8), ((25, 25, 5), 3, 8),  # (10 and 21 words: the forms of sixteen and of thirty-two)
 ])
 def test_exact_evaluator_equals_the_rule(hip, board, rows, I):
     m, n, k = board

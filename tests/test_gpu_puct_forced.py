@@ -169,6 +169,22 @@ def test_a_prior_above_one_and_a_prior_of_zero_on_a_visited_cell(hip, which, L):
     same_act(got, want, rule.raw_visits, (which, L))
 
 
+@pytest.mark.parametrize("name", cases.FLOOR_NAMES)
+def test_cells_pruned_to_a_floor_of_two_visits_or_more_below_their_count(hip, name):
+    """the large generic boards under the evaluator for which every move looks bad: the pruned counts depend on
+    t = k P (n_0 - 1) exactly (tests/test_puct_forced_cpu.py plants n_0)"""
+    (m, n, k), _, _, _ = BOARDS[name]
+    obs, want, leaves, rule = cases.floor_reference(name)
+    rec = []
+    ev = spike_torch(m * n, cases.spikes_of(m, n, k), cases.FLOOR_SPIKE, 1.0, lost=True, record=rec)
+    pol = hip.policy.PUCTSearchPolicy(k, evaluator=ev, iterations=cases.FLOOR_I, c=C_PUCT, seed=SEED, leaves=cases.FLOOR_L,
+                                      fpu=FPU, forced=K_FORCED)
+    pol._sampler.env_id0, pol._sampler.calls = ENV_ID0, 2
+    got = gpu_act(pol, obs)
+    same_leaves(rec, leaves, name)
+    same_act(got, want, rule.raw_visits, name)
+
+
 def test_a_captured_act_replayed_twice_equals_eager(hip):
     name, L = "9x9x5", 4
     (m, n, k), _, _, _ = BOARDS[name]

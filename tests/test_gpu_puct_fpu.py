@@ -29,8 +29,10 @@ BOARDS = {"3x3x3": 12,    # one pass per lane
           "12x13x5": 32,  # <6,13,5>: 156 cells for the variant's 169
           "16x15x5": 32,  # <8,15,5>: 240 cells for 225
           "12x12x5": 8,   # generic, five words: the eight-word instantiation
-          "7x9x7": 8}     # generic, three words: the four-word instantiation
-SEVEN = ("12x13x5", "16x15x5")  # boards that take all seven rows of ``sibling_positions``
+          "7x9x7": 8,     # generic, three words: the four-word instantiation
+          "17x17x5": 16,  # generic, ten words: the sixteen-word instantiation; the mass spans five passes
+          "25x25x5": 8}   # generic, 21 words: the 32-word instantiation; ten passes
+SEVEN = ("12x13x5", "16x15x5", "17x17x5", "25x25x5")  # boards that take all seven rows of ``sibling_positions``
 GENERIC = {"12x12x5": (12, 12, 5), "7x9x7": (7, 9, 7)}  # boards tests/puct_solver_cases.py has no rows of: ``start`` positions
 LEAVES = (1, 4)
 

@@ -33,7 +33,9 @@ CASES = {"3x3x3": ((3, 3, 3), 8, 4),     # NW = 1, C = 9: no multiple of 4
          # not square, and on the k = 5 ones the Philox layout (C + 3) & ~3 of a cell count the variant's board has not
          "8x3x3": ((8, 3, 3), 16, 4), "7x9x5": ((7, 9, 5), 16, 8), "16x15x5": ((16, 15, 5), 16, 8),
          "12x13x5": ((12, 13, 5), 8, 8), "18x19x5": ((18, 19, 5), 8, 8),
-         "7x9x7": ((7, 9, 7), 8, 8)}     # generic, three words: the four-word instantiation
+         "7x9x7": ((7, 9, 7), 8, 8),     # generic, three words: the four-word instantiation
+         # generic, ten and 21 words: the instantiations of sixteen and of thirty-two; C = 289 and 625, no multiples of 4
+         "17x17x5": ((17, 17, 5), 8, 4), "25x25x5": ((25, 25, 5), 8, 4)}
 SIBLINGS = ("8x3x3", "7x9x5", "16x15x5", "12x13x5", "18x19x5")
 DTYPES = {"f32": torch.float32, "bf16": torch.bfloat16}
 

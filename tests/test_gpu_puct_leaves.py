@@ -10,7 +10,7 @@ import pytest
 import torch
 
 from player_cases import DEV, _score, hip  # noqa: F401 (hip: the fixture)
-from puct_leaves_cases import C_PUCT, CASES, ENV_ID0, PARAMS, SEED, positions, reference
+from puct_leaves_cases import C_PUCT, CASES, ENV_ID0, LARGE, PARAMS, SEED, positions, reference
 from puct_leaves_rule import LeavesPuct
 from search_selfplay_rule import SelfPlayRule
 from test_gpu_puct_reuse import advance, exact_np, exact_torch, gpu_act, same, same_leaves, start
@@ -149,6 +149,10 @@ def test_a_captured_act_replayed_equals_eager(hip):
     (torch.float32, torch.uint8, torch.bfloat16, 8), (torch.uint8, torch.bfloat16, torch.bfloat16, 2)])
 def test_narrow_dtypes_on_one_board(hip, dtype, leaf_dtype, out_dtype, L, name="9x9x5"):
     """(the evaluator's priors are powers of two and its values eighths: exact in bfloat16)"""
+    narrow_act_equals_the_rule(hip, name, dtype, leaf_dtype, out_dtype, L)
+
+
+def narrow_act_equals_the_rule(hip, name, dtype, leaf_dtype, out_dtype, L):
     (m, n, k), rows, I, _ = CASES[name]
     obs, want, leaves, _ = reference(name, L)
     rec = []
@@ -156,6 +160,14 @@ def test_narrow_dtypes_on_one_board(hip, dtype, leaf_dtype, out_dtype, L, name="
     got = gpu_act(pol, obs, dtype)
     same_leaves(rec, leaves, (dtype, L))
     same(got, want + (np.zeros((rows, 2), np.int32),), (dtype, L))
+
+
+@pytest.mark.parametrize("name", list(LARGE))
+def test_narrow_leaves_on_the_large_generic_boards(hip, name):
+    """``uint8`` leaf rows of 289 bytes and ``bfloat16`` ones of 625 elements: rows at odd offsets"""
+    leaf_dtype = getattr(torch, LARGE[name])
+    narrow_act_equals_the_rule(hip, name, torch.uint8 if leaf_dtype is torch.bfloat16 else torch.float32, leaf_dtype,
+                               torch.bfloat16, 4)
 
 
 # ----------------------------------------------------------------------------- 6. search self-play

@@ -64,7 +64,8 @@ def test_header_and_binding_agree(hip):
 # ----------------------------------------------------------------------------- 2. the kernel against the rule
 @pytest.mark.parametrize("N,L,dtype,through_dev", [(5, 1, torch.float32, False), (7, 4, torch.bfloat16, True),
                                                    (5, 4, torch.float32, True), (7, 1, torch.bfloat16, False)])
-@pytest.mark.parametrize("C,alpha", [(9, 0.3), (24, 0.3), (81, 0.3), (361, 0.03), (63, 0.3), (240, 0.1), (342, 0.03)])
+@pytest.mark.parametrize("C,alpha", [(9, 0.3), (24, 0.3), (81, 0.3), (361, 0.03), (63, 0.3), (240, 0.1), (342, 0.03),
+                                     (289, 0.03), (625, 0.03)])  # (17x17 and 25x25: five and ten trips, odd row sizes)
 def test_the_kernel_equals_the_rule(hip, C, alpha, N, L, dtype, through_dev):
     lib = hip.lib
     step = 6

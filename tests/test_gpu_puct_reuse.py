@@ -22,7 +22,9 @@ BOARDS = [((3, 3, 3), 6, 10),    # NW = 1; games end inside the sequence
           ((4, 6, 3), 5, 12),    # generic, not square
           ((9, 9, 5), 6, 16),    # C > 64: every per-cell loop takes two trips; a built-in variant
           ((19, 19, 5), 3, 8),   # C = 361; fewer rows than one workgroup holds
-          ((7, 9, 7), 5, 24)]    # generic
+          ((7, 9, 7), 5, 24),    # generic
+          ((17, 17, 5), 3, 8),   # generic, ten words: the sixteen-word instantiation
+          ((25, 25, 5), 3, 8)]   # generic, 21 words: the 32-word instantiation
 
 
 def prior_table(C, mult=1):

@@ -29,9 +29,12 @@ def first_most_visited(stats):
     ((19, 19, 5), 4, ((64, 8, 1.0),)),       # I < |L|: the root is never fully expanded
     ((7, 7, 4), 8, ((80, 16, 1.0),)),        # generic NW forms
     ((12, 12, 5), 4, ((48, 8, 0.7),)),
+    ((17, 17, 5), 5, ((8, 4, 1.0),)),        # the forms of sixteen and of thirty-two words: ten and 21 words a plane
+    ((25, 25, 5), 5, ((8, 4, 1.0),)),
 ])
 def test_actions_and_stats_equal_the_rule(hip, board, rows, runs):
-    """(3x3x3, 9x9x5, 13x13x5, 15x15x5, 19x19x5: built-in variants; 7x7x4, 12x12x5: the generic NW forms)"""
+    """(3x3x3, 9x9x5, 13x13x5, 15x15x5, 19x19x5: built-in variants; 7x7x4, 12x12x5, 17x17x5, 25x25x5: the generic NW
+    forms)"""
     m, n, k = board
     obs = positions(m, n, k, rows, m * 100 + n * 10 + k, max_fill=0.6 if m > 9 else 1.0)
     finished = [i for i in range(rows) if completions(obs[i:i + 1, 1], np.ones((1, m, n), bool), k).any()

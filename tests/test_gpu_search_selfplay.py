@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from player_cases import DEV, hip  # noqa: F401 (hip: the fixture)
+from search_selfplay_async_fpu_cases import late_start
 from search_selfplay_rule import SelfPlayRule, gather
 
 pytestmark = pytest.mark.gpu
@@ -29,13 +30,16 @@ def exact_torch(C):
     return evaluate
 
 
-def run(hip, m, n, k, N, plies, dtype, temp_plies, keys, I=6, seed=7, env_id0=3):
+def run(hip, m, n, k, N, plies, dtype, temp_plies, keys, I=6, seed=7, env_id0=3, start=None):
     """plays ``plies`` plies through the entry point, replaying each ply's visits into the rule; compares the next roots
-    every ply and returns (rule, ring tensors)"""
+    every ply and returns (rule, ring tensors).  ``start``: the env state (planes, meta) both begin from"""
     lib = hip.lib
     C, T = m * n, m * n  # the smallest ring: wraps every C plies
     env = hip.Env(m, n, k, N, device=DEV)
     env.reset()
+    if start is not None:
+        env._planes.copy_(torch.from_numpy(start[0].view(np.int64)))
+        env._meta.copy_(torch.from_numpy(start[1].astype(np.int64)).to(env._meta.dtype))
     pol = hip.policy.PUCTSearchPolicy(k, evaluator=exact_torch(C), iterations=I, seed=seed + 1)
     W = lib.state_words(m, n)
     ring_planes = torch.zeros((T, 2, W, N), dtype=torch.int64, device=DEV)
@@ -50,6 +54,8 @@ def run(hip, m, n, k, N, plies, dtype, temp_plies, keys, I=6, seed=7, env_id0=3)
     seed_dev = torch.tensor([seed], dtype=torch.int64, device=DEV) if keys else None
     step_dev = torch.zeros(1, dtype=torch.int64, device=DEV) if keys else None
     rule = SelfPlayRule(m, n, k, N, T)
+    if start is not None:
+        rule.load(*start)
     for p in range(plies):
         pol.act({"observation": obs, "action_mask": mask}, visits=visits)
         if keys:
@@ -92,6 +98,20 @@ def test_the_step_equals_the_rule(hip, board, N, dt, temp, keys):
     run(hip, m, n, k, N, 2 * C + 5, DTYPES[dt], C if temp == "C" else temp, keys)
 
 
+# the generic forms of sixteen and of thirty-two words (ten and 21 words a plane: the ring's rows of 64-bit words hold
+# five, and ten and a half), a few plies from ``late_start``: five rows three to eight stones short of a drawn board, so
+# every row's game ends, is labelled and starts again inside the run
+LATE_PLIES = 12
+LATE_CASES = [((17, 17, 5), 5, 2, 3, True), ((25, 25, 5), 5, 1, 0, False)]
+
+
+@pytest.mark.parametrize("board,N,dt,temp,keys", LATE_CASES)
+def test_the_step_equals_the_rule_from_a_late_start(hip, board, N, dt, temp, keys):
+    m, n, k = board
+    rule, _, _, _ = run(hip, m, n, k, N, LATE_PLIES, DTYPES[dt], temp, keys, start=late_start(m, n, k, N))
+    assert rule.stats[0] >= N and rule.ring_planes.shape[2] == (m * (n + 1) + 63) // 64
+
+
 def test_a_row_without_visits_is_reported_and_left_alone(hip):
     lib = hip.lib
     m, n, k, N = 3, 3, 3, 4
@@ -110,17 +130,21 @@ def test_a_row_without_visits_is_reported_and_left_alone(hip):
     assert obs[2].sum().item() == 0 and obs[0, 1, 1, 1].item() == 1
 
 
-@pytest.mark.parametrize("board", [(3, 3, 3), (9, 9, 5), (5, 7, 4)])
+@pytest.mark.parametrize("board", [(3, 3, 3), (9, 9, 5), (5, 7, 4), (17, 17, 5), (25, 25, 5)])
 def test_the_gather_equals_the_rule(hip, board):
     lib = hip.lib
     m, n, k = board
     C, N = m * n, 5
-    rule, planes, visits, z = run(hip, m, n, k, N, C + 7, torch.float32, 2, False)
+    late = C > 256  # (the large generic boards: LATE_PLIES plies from a late start; the written slots are sampled most)
+    rule, planes, visits, z = run(hip, m, n, k, N, LATE_PLIES if late else C + 7, torch.float32, 2, False,
+                                  start=late_start(m, n, k, N) if late else None)
     T = C
     count = 8 if m == n else 4
     rng = np.random.default_rng(C)
     B = 300
     idx = rng.integers(-T * N, T * N, B)
+    if late:
+        idx[3:250] = rng.integers(0, LATE_PLIES * N, 247) - T * N * rng.integers(0, 2, 247)
     idx[:3] = [T * N, -T * N - 1, 10 ** 9]  # out of range
     sym = rng.integers(0, count, B).astype(np.int8)
     idx_t = torch.from_numpy(idx).to(DEV)  # (held: a temporary's block could be handed to the next tensor)

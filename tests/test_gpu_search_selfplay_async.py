@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 import torch
 
+import search_selfplay_async_keep_cases as keep_cases
 from player_cases import DEV, hip  # noqa: F401 (hip: the fixture)
 from search_selfplay_async_rule import AsyncSelfPlayRule, exact_np
 
@@ -32,11 +33,12 @@ def exact_torch(C, out_dtype=torch.float32):
 
 
 def new_async(hip, board, N, seed, full=FULL, fast=FAST, full_prob=0.75, leaf_dtype=torch.float32,
-              out_dtype=torch.float32, **kw):
+              out_dtype=torch.float32, evaluator=None, **kw):
     from selfplay.search_selfplay import AsyncSearchSelfPlay
 
     m, n, k = board
-    return AsyncSearchSelfPlay(m, n, k, N, evaluator=exact_torch(m * n, out_dtype), iterations=full, fast_iterations=fast,
+    return AsyncSearchSelfPlay(m, n, k, N, evaluator=evaluator or exact_torch(m * n, out_dtype), iterations=full,
+                               fast_iterations=fast,
                                full_prob=full_prob, seed=seed, leaf_dtype=leaf_dtype, **kw)
 
 
@@ -54,7 +56,8 @@ def assert_same_state(sp, rule, what=""):
 
 
 # ----------------------------------------------------------------------------- 1. every ply full: the lockstep player
-@pytest.mark.parametrize("board,N,plies,capacity", [((3, 3, 3), 6, 2 * 9 + 5, None), ((9, 9, 5), 5, 81 + 5, 81)])
+@pytest.mark.parametrize("board,N,plies,capacity", [((3, 3, 3), 6, 2 * 9 + 5, None), ((9, 9, 5), 5, 81 + 5, 81),
+                                                    ((17, 17, 5), 5, 6, None)])  # (ten words, a few plies)
 def test_with_every_ply_full_it_is_the_lockstep_player(hip, board, N, plies, capacity):
     from selfplay.search_selfplay import SearchSelfPlay
 
@@ -97,18 +100,20 @@ CASES = [
     ((12, 13, 5), 5, torch.uint8, torch.float32, False, 4, 150, "golden", 6),
     ((16, 15, 5), 5, torch.float32, torch.bfloat16, True, 4, 150, "golden", 6),
     ((18, 19, 5), 5, torch.bfloat16, torch.float32, False, 4, 150, "golden", 6),
+    # the generic forms of sixteen and of thirty-two words: ten and 21 words a plane (an odd count: a ring row of planes
+    # is no whole number of 64-bit words a plane), 289- and 625-byte leaf rows, from a computed start ("late": five rows
+    # three to eight stones short of a drawn board)
+    ((17, 17, 5), 5, torch.uint8, torch.float32, False, 4, 150, "late", 6),
+    ((25, 25, 5), 5, torch.bfloat16, torch.float32, True, 4, 150, "late", 6),
 ]
+LARGE_CASES = CASES[-2:]
 SIBLING_BOARDS = ((8, 3, 3), (7, 9, 5), (12, 13, 5), (16, 15, 5), (18, 19, 5))
 SIBLING_CASES = [case for case in CASES if case[0] in SIBLING_BOARDS]
 ENV_ID0 = 3
 
 
 def start_state(board, start):
-    if start is None:
-        return None
-    m, n, k = board
-    with np.load(GOLDEN) as z:
-        return z[f"{m}x{n}x{k}_planes"], z[f"{m}x{n}x{k}_meta"]
+    return keep_cases.start_state(board, start)  # (None, "golden", or "late": computed, five rows)
 
 
 def new_rule(board, N, temp, seed, start, T=None):

@@ -4,7 +4,8 @@
 a stored start; the FULL / FAST budgets and round counts of the cases with first-play urgency; with and without root noise,
 ``noise_on_fast``, the solver and first-play urgency -- where tests/test_puct_forced_cpu.py shows with the rule alone that
 each forces, prunes a full ply's record and leaves a ply that does not force as it was.  With every ply full it must leave,
-bit for bit, what the lockstep ``SearchSelfPlay(forced=k)`` of the same seed leaves (3x3x3 and 9x9x5).
+bit for bit, what the lockstep ``SearchSelfPlay(forced=k)`` of the same seed leaves (3x3x3 and 9x9x5; six plies on 16x15x5,
+12x12x5 and 17x17x5).
 
 Everything is bit-exact except the noised priors of a root against numpy's, at the ``rtol=1e-6`` of
 tests/test_gpu_puct_noise.py (``Beside`` of tests/test_gpu_search_selfplay_async_opts.py makes it); the rule then takes the
@@ -66,7 +67,10 @@ def test_mixed_budgets_equal_the_rule_launch_for_launch(hip, case):
 
 # ----------------------------------------------------------------------------- every ply full: the lockstep player
 @pytest.mark.parametrize("noise,fpu", [(None, None), (NOISE, FPU)])
-@pytest.mark.parametrize("board,plies,capacity", [((3, 3, 3), 2 * 9 + 5, None), ((9, 9, 5), 24, 81)])
+@pytest.mark.parametrize("board,plies,capacity", [((3, 3, 3), 2 * 9 + 5, None), ((9, 9, 5), 24, 81),
+                                                  # a multi-word variant and the generic forms of five and of ten
+                                                  # words, a few plies
+                                                  ((16, 15, 5), 6, None), ((12, 12, 5), 6, None), ((17, 17, 5), 6, None)])
 def test_with_every_ply_full_it_is_the_lockstep_player(hip, board, plies, capacity, noise, fpu):
     from selfplay.search_selfplay import SearchSelfPlay
 

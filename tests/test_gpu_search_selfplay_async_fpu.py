@@ -56,7 +56,8 @@ def test_mixed_budgets_equal_the_rule_launch_for_launch(hip, board, start, temp,
 @pytest.mark.parametrize("keep,tree_nodes", [(False, None), (True, 13), (True, 8)])
 @pytest.mark.parametrize("board,plies,capacity", [((3, 3, 3), 2 * 9 + 5, None), ((9, 9, 5), 24, 81),
                                                   # a multi-word variant and the generic form of five words, a few plies
-                                                  ((16, 15, 5), 6, None), ((12, 12, 5), 6, None)])
+                                                  ((16, 15, 5), 6, None), ((12, 12, 5), 6, None),
+                                                  ((17, 17, 5), 6, None)])  # (and the generic form of ten words)
 def test_with_every_ply_full_it_is_the_lockstep_player(hip, board, plies, capacity, keep, tree_nodes, noise):
     from selfplay.search_selfplay import SearchSelfPlay
 
@@ -75,7 +76,7 @@ def test_with_every_ply_full_it_is_the_lockstep_player(hip, board, plies, capaci
     assert sp.fresh.tolist() == [1] * N and sp.row_plies.tolist() == [plies] * N
     assert sp.buffer.plies.item() == plies and sp.env._err.tolist() == [0, 0]
     assert lock.buffer.visits.any()
-    if board in ((16, 15, 5), (12, 12, 5)):
+    if board in ((16, 15, 5), (12, 12, 5), (17, 17, 5)):
         # (six plies of six iterations from the empty board: no game ends, and no unvisited cell's urgency decides a
         # selection -- the player without fpu records the same; the mixed cases above hold the urgency on these boards)
         assert lock.pop_game_stats() == sp.pop_game_stats()

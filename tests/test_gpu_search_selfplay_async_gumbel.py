@@ -52,7 +52,10 @@ def ring(sp):
                                                            ((12, 13, 5), 5, 4, 4, 6, None),
                                                            ((16, 15, 5), 5, 4, 4, 6, None),
                                                            ((19, 19, 5), 3, 4, 4, 6, None),
-                                                           ((12, 12, 5), 3, 4, 4, 6, None)])
+                                                           ((12, 12, 5), 3, 4, 4, 6, None),
+                                                           # and those of ten and of 21 words
+                                                           ((25, 25, 5), 3, 4, 4, 6, None),
+                                                           ((17, 17, 5), 5, 4, 4, 6, None)])
 def test_with_every_ply_full_it_is_the_lockstep_gumbel_player(hip, board, N, I, cons, plies, capacity):
     from selfplay.search_selfplay import SearchSelfPlay
 

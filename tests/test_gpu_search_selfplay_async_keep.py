@@ -48,17 +48,21 @@ class KeepBeside(Beside):
 # ----------------------------------------------------------------------------- 1. every ply full: the lockstep player
 @pytest.mark.parametrize("noise", [None, NOISE])
 @pytest.mark.parametrize("tree_nodes", [13, 8])  # (8: keep_nodes = 2, children are dropped on every carried ply)
-@pytest.mark.parametrize("board,N,plies,capacity", [((3, 3, 3), 6, 2 * 9 + 5, None), ((9, 9, 5), 5, 81 + 5, 81)])
+@pytest.mark.parametrize("board,N,plies,capacity", [((3, 3, 3), 6, 2 * 9 + 5, None), ((9, 9, 5), 5, 81 + 5, 81),
+                                                    ((25, 25, 5), 5, 6, None)])  # (21 words, a few plies)
 def test_with_every_ply_full_it_is_the_lockstep_player_that_keeps_its_trees(hip, board, N, plies, capacity, tree_nodes,
                                                                             noise):
     from selfplay.search_selfplay import SearchSelfPlay
 
     m, n, k = board
     I = 6
-    lock = SearchSelfPlay(m, n, k, N, evaluator=exact_torch(m * n), iterations=I, seed=13, temp_plies=3, capacity=capacity,
+    # (on 625 cells six iterations under the dyadic evaluator never visit a child twice, every ply would carry the child
+    # alone and the records would be those of the player that keeps nothing: that board searches under the peaked one)
+    ev = peaked_torch if board == (25, 25, 5) else exact_torch
+    lock = SearchSelfPlay(m, n, k, N, evaluator=ev(m * n), iterations=I, seed=13, temp_plies=3, capacity=capacity,
                           reuse=True, tree_nodes=tree_nodes, root_noise=noise)
     lock.play(plies)
-    kw = dict(full=I, fast=None, full_prob=1.0, temp_plies=3, capacity=capacity, root_noise=noise)
+    kw = dict(full=I, fast=None, full_prob=1.0, temp_plies=3, capacity=capacity, root_noise=noise, evaluator=ev(m * n))
     sp = new_async(hip, board, N, 13, keep_tree=True, tree_nodes=tree_nodes, **kw)
     sp.advance(plies * (I + 1))
     torch.cuda.synchronize()

@@ -15,6 +15,7 @@ import torch
 from player_cases import DEV, hip  # noqa: F401 (hip: the fixture)
 from search_selfplay_async_leaves_rule import AsyncLeavesRule
 from test_gpu_search_selfplay_async import assert_same_state, exact_torch, load_start, new_async, start_state
+from test_gpu_search_selfplay_async_keep import peaked_torch
 from test_gpu_search_selfplay_async_opts import NOISE, Beside, same_players
 from test_search_selfplay_async_leaves_cpu import (ENV_ID0, GPU_CASES, GPU_FAST, GPU_FULL, THRESHOLD,
                                                    assert_every_branch_was_reached, gpu_rule)
@@ -77,16 +78,20 @@ def test_with_one_leaf_the_new_entry_point_is_the_old_launch(hip, board, N, roun
 
 # ----------------------------------------------------------------------------- 2. every ply full: the lockstep player
 @pytest.mark.parametrize("board,N,plies,capacity,I,L", [((3, 3, 3), 6, 2 * 9 + 5, None, 8, 2), ((3, 3, 3), 6, 2 * 9 + 5, None, 8, 4),
-                                                       ((9, 9, 5), 5, 81 + 5, 81, 8, 4), ((9, 9, 5), 5, 81 + 5, 81, 16, 16)])
+                                                       ((9, 9, 5), 5, 81 + 5, 81, 8, 4), ((9, 9, 5), 5, 81 + 5, 81, 16, 16),
+                                                       ((17, 17, 5), 5, 6, None, 8, 4)])  # (ten words, a few plies)
 def test_with_every_ply_full_it_is_the_lockstep_player_with_leaves(hip, board, N, plies, capacity, I, L):
     from selfplay.search_selfplay import SearchSelfPlay
 
     m, n, k = board
-    lock = SearchSelfPlay(m, n, k, N, evaluator=exact_torch(m * n), iterations=I, seed=13, temp_plies=3, capacity=capacity,
+    # (on 289 cells eight iterations under the dyadic evaluator go to eight unvisited cells, one leaf at a time or four,
+    # and the records would be those of one leaf: that board searches under the peaked evaluator)
+    ev = peaked_torch if board == (17, 17, 5) else exact_torch
+    lock = SearchSelfPlay(m, n, k, N, evaluator=ev(m * n), iterations=I, seed=13, temp_plies=3, capacity=capacity,
                           root_noise=NOISE, leaves=L)
     lock.play(plies)
     sp = new_async(hip, board, N, 13, full=I, fast=None, full_prob=1.0, temp_plies=3, capacity=capacity, root_noise=NOISE,
-                   leaves=L)
+                   leaves=L, evaluator=ev(m * n))
     sp.advance(plies * (I // L + 1))
     torch.cuda.synchronize()
     same_players(sp, lock)
@@ -95,7 +100,8 @@ def test_with_every_ply_full_it_is_the_lockstep_player_with_leaves(hip, board, N
         assert torch.equal(sp.leaf_obs[j::L], lock.obs) and torch.equal(sp.leaf_mask[j::L], lock.mask), j
     assert sp.fresh.tolist() == [1] * N and sp.row_plies.tolist() == [plies] * N and sp.row_sims.tolist() == [0] * N
     assert sp.buffer.plies.item() == plies and sp.env._err.tolist() == [0, 0]
-    one = new_async(hip, board, N, 13, full=I, fast=None, full_prob=1.0, temp_plies=3, capacity=capacity, root_noise=NOISE)
+    one = new_async(hip, board, N, 13, full=I, fast=None, full_prob=1.0, temp_plies=3, capacity=capacity, root_noise=NOISE,
+                    evaluator=ev(m * n))
     one.advance(plies * (I + 1))
     assert not torch.equal(sp.buffer.visits, one.buffer.visits), "the leaves changed no search"
     assert lock.pop_game_stats() == sp.pop_game_stats() and lock.buffer.visits.any()

@@ -33,7 +33,8 @@ def same_players(a, b):
 
 
 # ----------------------------------------------------------------------------- 1. every ply full, noise: the lockstep player
-@pytest.mark.parametrize("board,N,plies,capacity", [((3, 3, 3), 6, 2 * 9 + 5, None), ((9, 9, 5), 5, 81 + 5, 81)])
+@pytest.mark.parametrize("board,N,plies,capacity", [((3, 3, 3), 6, 2 * 9 + 5, None), ((9, 9, 5), 5, 81 + 5, 81),
+                                                    ((25, 25, 5), 5, 6, None)])  # (21 words, a few plies)
 def test_with_every_ply_full_and_noise_it_is_the_lockstep_player(hip, board, N, plies, capacity):
     from selfplay.search_selfplay import SearchSelfPlay
 
@@ -100,7 +101,11 @@ CASES = [
     ((8, 3, 3), 7, torch.uint8, torch.bfloat16, False, 2, 400, None, 6, None, False, True),
     ((19, 19, 5), 3, torch.float32, torch.float32, False, 4, 150, "golden", 6, (0.03, 0.25), False, True),
     ((16, 15, 5), 5, torch.float32, torch.bfloat16, False, 4, 150, "golden", 6, None, False, True),
+    # the generic forms of sixteen and of thirty-two words, from a computed start ("late": no root has a single free cell)
+    ((17, 17, 5), 5, torch.float32, torch.bfloat16, False, 4, 150, "late", 6, NOISE, False, True),
+    ((25, 25, 5), 5, torch.uint8, torch.float32, False, 4, 150, "late", 6, (0.03, 0.25), False, True),
 ]
+LARGE_CASES = CASES[-2:]
 
 
 def new_rule(board, N, temp, seed, start, noise, on_fast, solver):

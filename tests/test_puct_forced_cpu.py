@@ -273,6 +273,25 @@ def test_the_edge_cases_have_a_prior_above_one_and_a_visited_cell_of_prior_zero(
     assert kept and all(out[1][i][zero] == raw[i][zero] for i in kept)  # a prior of 0 keeps its count
 
 
+@pytest.mark.parametrize("name", cases.FLOOR_NAMES)
+def test_the_floor_cases_tell_n0_less_one_from_n0(name, monkeypatch):
+    """the floor's t from n_0 in the place of n_0 - 1, planted in the rule: other pruned counts on both large boards"""
+    import puct_forced_rule
+
+    _, want, _, rule = cases.floor_reference(name)
+    assert (rule.raw_visits != want[1]).any()
+
+    def planted(tree, a, n1, k_forced):
+        t = np.float32(np.float32(np.float32(k_forced) * tree.prior[0][a]) * np.float32(tree.n[0]))
+        return next((F for F in range(n1) if np.float32(np.float32(F) * np.float32(F)) >= t), n1)
+
+    monkeypatch.setattr(puct_forced_rule, "floor_of", planted)
+    got = cases.floor_rule(name).act(cases.rows_of(name), step=2)
+    rows = int((got[1] != want[1]).any(axis=1).sum())
+    print(name, "rows whose pruned counts differ", rows)
+    assert rows > 0
+
+
 @pytest.mark.parametrize("L,solver", cases.REUSE)
 def test_the_kept_tree_case_carries_a_root_whose_visits_exceed_its_childrens(L, solver):
     acts = cases.reuse_reference(L, solver)

@@ -236,7 +236,7 @@ def test_both_per_row_entry_points_run_on_every_kind_of_board():
 
     for keep in (False, True):
         kinds = {kind(c[0]) for c in async_cases.CASES if c[7] == keep}
-        assert kinds == builtin | {(5, 0, 0), (2, 0, 0)}, (keep, kinds)
+        assert kinds == builtin | {(5, 0, 0), (2, 0, 0), (10, 0, 0), (21, 0, 0)}, (keep, kinds)
     # the solver, the noise and a tree cut to keep_nodes each run on a multi-word built-in and on a generic form
     for option in (5, 6):
         kinds = {kind(c[0]) for c in async_cases.CASES if c[option]}

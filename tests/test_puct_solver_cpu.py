@@ -13,9 +13,9 @@ from puct_leaves_cases import reference as leaves_reference
 from puct_reuse_rule import ReusePuct
 from puct_rule import puct
 import puct_solver_rule
-from puct_solver_cases import (C_PUCT, CASES, ENV_ID0, LEAVES, MISLED_BOARD, MISLED_FAR, MISLED_I, MISLED_OBS, MISLED_WIN,
-                               REUSE_CASES, SEED, SIBLINGS, last_row_win, misled_reference, positions, reference,
-                               reuse_reference)
+from puct_solver_cases import (C_PUCT, CASES, ENV_ID0, LARGE, LEAVES, MISLED_BOARD, MISLED_FAR, MISLED_I, MISLED_OBS,
+                               MISLED_WIN, REUSE_CASES, SEED, SIBLINGS, last_row_win, misled_reference, positions,
+                               reference, reuse_reference)
 from puct_solver_rule import PROOF_UNKNOWN, SolverPuct, negamax, puct_solver, value_after
 from tactical_rule import random_positions, tactical_sets
 from test_gpu_puct_reuse import advance, exact_np, start
@@ -157,7 +157,15 @@ VARIANT_ROWS = {3: 3, 9: 9, 13: 13, 15: 15, 19: 19}  # the board a built-in vari
 
 
 def test_the_sibling_cases_hold_what_a_wrong_row_count_gets_wrong():
-    for name in SIBLINGS:
+    the_near_full_rows_hold_what_a_wrong_cell_count_gets_wrong(SIBLINGS)
+
+
+def test_the_large_cases_hold_what_a_cell_count_from_the_word_count_gets_wrong():
+    the_near_full_rows_hold_what_a_wrong_cell_count_gets_wrong(LARGE)
+
+
+def the_near_full_rows_hold_what_a_wrong_cell_count_gets_wrong(names):
+    for name in names:
         (m, n, k), rows, _ = CASES[name]
         obs = positions(name)
         free = (obs.reshape(rows, 2, -1) == 0).all(axis=1).sum(axis=1)
@@ -231,6 +239,27 @@ def test_the_sibling_cases_reject_the_variants_own_board(name, L, monkeypatch):
     assert 2 in differs and 4 in differs, (name, differs)  # the root values and the proofs
     if vm < m:
         assert got[4][4] != 1 and 1 in differs  # the win in row m - 1 is not seen: other visits too
+
+
+WORD_BOARD = {"17x17x5": (20, 16), "25x25x5": (28, 24)}  # rows x columns of 32 bits a plane word: 320 and 672 cells
+
+
+@pytest.mark.parametrize("L", LEAVES)
+@pytest.mark.parametrize("name", LARGE)
+def test_the_large_cases_reject_a_cell_count_taken_from_the_word_count(name, L, monkeypatch):
+    """the defect the near-full rows of the two large generic boards are there to catch, planted in the rule: a board
+    is full at 32 stones a plane word, 320 for 289 and 672 for 625.  The boards that fill inside the search are then
+    not drawn, and the proofs and root values of the batch are other ones."""
+    (m, n, k), rows, I = CASES[name]
+    vm, vn = WORD_BOARD[name]
+    assert vm >= m and m * n < vm * vn == 32 * ((m * (n + 1) + 31) // 32)  # (a row of the plane has a guard column)
+    obs, want, leaves = reference(name, L)
+    plant(monkeypatch, vm, vn)
+    rule = SolverPuct(k, I, C_PUCT, exact_np(m * n), L, seed=SEED, env_id0=ENV_ID0)
+    got = rule.act(obs, step=2)
+    differs = [j for j in range(5) if not np.array_equal(got[j], want[j])]
+    print(name, L, "differs in", differs, got[4][:5].tolist(), want[4][:5].tolist())
+    assert 2 in differs and 4 in differs, (name, differs)  # the root values and the proofs
 
 
 @pytest.mark.parametrize("distance", [1, 2])

@@ -149,6 +149,45 @@ def test_the_sibling_cases_reject_the_variants_own_board(case, monkeypatch):
     assert wrong.row_plies.tolist() != true.row_plies.tolist() or board == (8, 3, 3)
 
 
+def _large_cases():
+    from test_gpu_search_selfplay_async import LARGE_CASES
+
+    return LARGE_CASES
+
+
+@pytest.mark.parametrize("case", _large_cases(), ids=lambda c: "x".join(map(str, c[0])))
+def test_the_large_cases_end_games_out_of_step_and_reject_a_cell_count_from_the_word_count(case, monkeypatch):
+    """the GPU test's runs on 17x17x5 and 25x25x5 (ten and 21 words a plane) with the rule alone: a game ends, a board
+    fills and is drawn at m * n stones, fast and full plies are recorded, the rows run out of step -- and with 32 cells
+    a plane word for the cell count (320 for 289, 672 for 625) no board is ever full: other statistics, labels and rows"""
+    import test_gpu_search_selfplay_async as gpu_cases
+    from test_gpu_search_selfplay_async import new_rule
+
+    board, N, _, _, _, temp, rounds, start, seed = case
+    m, n, k = board
+    cells = 32 * ((m * (n + 1) + 31) // 32)
+    assert N % 4 and start == "late" and cells > m * n
+
+    class Planted(AsyncSelfPlayRule):
+        def _ply(self, i, visits, full):
+            self.C = cells
+            try:
+                return super()._ply(i, visits, full)
+            finally:
+                self.C = m * n
+
+    true = new_rule(board, N, temp, seed, start)
+    run_rule(true, rounds)
+    print(board, true.stats.tolist(), true.fast_records, true.full_records, true.row_plies.tolist())
+    assert true.stats[0] > 0 and true.stats[3] > 0 and not true.errors
+    assert true.fast_records > 0 and true.full_records > 0 and len(set(true.row_plies.tolist())) > 1
+    monkeypatch.setattr(gpu_cases, "AsyncSelfPlayRule", Planted)
+    wrong = new_rule(board, N, temp, seed, start)
+    assert type(wrong) is Planted
+    run_rule(wrong, rounds)
+    assert wrong.stats.tolist() != true.stats.tolist() and not np.array_equal(wrong.ring_z, true.ring_z)
+
+
 OLD_STARTS = {"12x12x5_meta": "1f5418751e261d337a1822836f24449adab097df432544ae05dec7e1464da01f",
               "12x12x5_planes": "f0c533aff52d3acfa622b6d989dcb6c46e16adbecefb02476bc4e688d2785ba9",
               "19x19x5_meta": "4402b87f47e4e9ba8fa460cea93dd1c265ea689ae68e6215beddb77cd047942c",

@@ -35,6 +35,10 @@ MIXED_CASES = [
     ((19, 19, 5), 3, 150, 6, "golden", "uint8", "float32", False),
     ((12, 12, 5), 3, 150, 6, "golden", "float32", "float32", True),
     ((7, 7, 4), 5, 500, 6, None, "uint8", "bfloat16", True),
+    # the generic forms of sixteen and of thirty-two words (ten and 21 words a plane; C = 289 and 625: the draw's row
+    # stride is not C), from a computed start ("late": five rows three to eight stones short of a drawn board)
+    ((17, 17, 5), 5, 150, 6, "late", "uint8", "float32", False),
+    ((25, 25, 5), 5, 150, 6, "late", "bfloat16", "bfloat16", True),
 ]
 
 
@@ -201,7 +205,7 @@ def test_the_new_boards_are_one_of_every_kind_and_every_dtype_is_read():
     """the boards of MIXED_CASES[3:] by the form that runs them (the built-in rows of MNK_DISPATCH are <1,3,3>, <3,9,5>,
     <6,13,5>, <8,15,5> and <12,19,5>: 32-bit words per plane, columns, k; any other board takes the generic form of its
     word count), and what the device reads and writes spread over them"""
-    new = MIXED_CASES[3:]
+    new = MIXED_CASES[3:8]
     assert [(record_words(b[0], b[1]), b[1], b[2]) for b, *_ in new[:3]] == [(6, 13, 5), (8, 15, 5), (12, 19, 5)]
     assert [record_words(b[0], b[1]) for b, *_ in new[3:]] == [5, 2]
     assert 16 * (15 + 1) % 32 == 0 and 19 * 19 % 4  # rows of n + 1 bits fill the last word; a row stride that is not C

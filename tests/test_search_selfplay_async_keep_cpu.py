@@ -174,15 +174,20 @@ def test_the_mixed_cases_show_what_the_gpu_test_needs(case):
     assert cases.MIXED[case][1] % 4 and not rule.errors
     assert many and fresh_after_end
     assert rule.fast_records > 0 and rule.full_records > 0 and len(set(rule.row_plies.tolist())) > 1
+    noise, solver = cases.MIXED[case][9], cases.MIXED[case][11]
+    by_proof = sum(1 for rec in rule.proven_plies if rec[4])
+    print("plies ended by proof", by_proof, "noised / plain roots", rule.noised_roots, rule.plain_roots)
+    assert by_proof > 0 or not solver  # with the solver a ply ends by proof,
+    assert rule.noised_roots > 0 or not noise  # and with noise a root takes it
 
 
 def test_some_mixed_case_truncates_and_some_carries_a_proven_root():
     found = [cases.conditions(cases.mixed_run(c)) for c in range(len(cases.MIXED))]
     assert any(f[2] for f in found) and any(f[3] for f, case in zip(found, cases.MIXED) if case[11])
     # and the last case has roots whose proof did not outlive the truncation, beside roots that kept theirs
-    last = cases.mixed_run(len(cases.MIXED) - 1)
+    last = cases.mixed_run(cases.TRUNCATED_SOLVER)
     assert cases.dropped_proofs(last) > 0 and any(t[7] for t in last.trace)
-    assert all(cases.dropped_proofs(cases.mixed_run(c)) == 0 for c in range(len(cases.MIXED) - 1))
+    assert all(cases.dropped_proofs(cases.mixed_run(c)) == 0 for c in range(len(cases.MIXED)) if c != cases.TRUNCATED_SOLVER)
 
 
 def test_the_chunk_case_keeps_more_than_a_chunk_and_no_multiple_of_eight():

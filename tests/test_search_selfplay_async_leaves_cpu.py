@@ -13,6 +13,7 @@ import pytest
 
 import puct_solver_rule as ps
 from player_cases import HEADER, check_header_and_binding, lib  # noqa: F401 (lib: the fixture)
+from search_selfplay_async_keep_cases import start_state
 from search_selfplay_async_leaves_rule import AsyncLeavesRule
 from search_selfplay_async_opts_rule import AsyncOptsRule
 from search_selfplay_async_rule import exact_np
@@ -222,6 +223,9 @@ GPU_CASES = {
     "8x3x3": ((8, 3, 3), 7, "u8", "bf16", False, 2, 200, None, 3, (0.02, 0.9), False, True, 4, 1.25),
     "19x19x5": ((19, 19, 5), 3, "f32", "f32", False, 4, 60, "golden", 3, (0.003, 0.9), False, True, 4, 4.0),
     "16x15x5": ((16, 15, 5), 5, "f32", "bf16", False, 4, 90, "golden", 3, (0.003, 0.9), False, False, 2, 4.0),
+    # the generic forms of sixteen and of thirty-two words, from a computed start ("late")
+    "17x17x5": ((17, 17, 5), 5, "u8", "f32", False, 4, 150, "late", 3, (0.003, 0.9), False, True, 4, 4.0),
+    "25x25x5": ((25, 25, 5), 5, "bf16", "bf16", False, 4, 150, "late", 3, (0.003, 0.9), False, False, 2, 4.0),
 }
 ENV_ID0 = 3
 
@@ -250,6 +254,8 @@ def assert_every_branch_was_reached(case, rule):
         assert rule.ring_wraps > 0
     if solver:
         assert by_proof > 0
+    if GPU_CASES[case][9]:
+        assert rule.noised_roots > 0  # with noise a root takes it
 
 
 @pytest.mark.parametrize("case", list(GPU_CASES))
@@ -259,6 +265,8 @@ def test_the_gpu_cases_reach_every_branch_of_the_rule(case):
         with np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden",
                                   "search_selfplay_async_starts.npz")) as z:
             state = z[case + "_planes"], z[case + "_meta"]
+    elif GPU_CASES[case][7] == "late":
+        state = start_state(GPU_CASES[case][0], "late")
     rule = gpu_rule(case, state)
     run(rule, GPU_CASES[case][6])
     assert_every_branch_was_reached(case, rule)

@@ -162,6 +162,32 @@ def test_with_the_solver_the_games_are_the_lockstep_solvers_and_proven_roots_pla
     assert lock.stats[0] > 0 and lock.ring_visits[:P].any()
 
 
+def _large_cases():
+    from test_gpu_search_selfplay_async_opts import LARGE_CASES
+
+    return LARGE_CASES
+
+
+@pytest.mark.parametrize("case", _large_cases(), ids=lambda c: "x".join(map(str, c[0])))
+def test_the_large_cases_use_every_option_they_turn_on(case):
+    """the GPU test's runs on 17x17x5 and 25x25x5 (ten and 21 words a plane) with the rule alone and its own noise: a
+    game ends, fast and full plies are recorded, the rows run out of step, a ply ends by proof, roots take the noise"""
+    from test_gpu_search_selfplay_async_opts import new_rule
+
+    board, N, _, _, _, temp, rounds, start, seed, noise, on_fast, solver = case
+    rule = new_rule(board, N, temp, seed, start, noise, on_fast, solver)
+    ev = exact_np(rule.C)
+    obs, mask = rule.view()
+    for _ in range(rounds):
+        obs, mask, _ = rule.advance(*ev(obs, mask))
+    by_proof = sum(1 for rec in rule.proven_plies if rec[4])
+    print(f"{board}: games {rule.stats[0]}, fast / full records {rule.fast_records} / {rule.full_records}, row plies "
+          f"{rule.row_plies.tolist()}, by proof {by_proof}, noised / plain roots {rule.noised_roots} / {rule.plain_roots}")
+    assert N % 4 and noise and solver and not on_fast and not rule.errors
+    assert rule.stats[0] > 0 and rule.fast_records > 0 and rule.full_records > 0
+    assert len(set(rule.row_plies.tolist())) > 1 and by_proof > 0 and rule.noised_roots > 0 and rule.plain_roots > 0
+
+
 def test_every_root_proven_by_the_rule_has_the_value_brute_force_gives_it():
     rule, _, _, _ = solver_runs()
     early = [rec for rec in rule.proven_plies if rec[4]]
