@@ -12,6 +12,7 @@ import functools
 
 import numpy as np
 
+import puct_ops
 import puct_solver_rule as ps
 from oracle import philox
 from playout_rule import has_run
@@ -31,7 +32,7 @@ def short_of_floor(tree, legal, kids, vl, k_forced):
         if ch is None or tree.n[ch] == 0:
             continue
         n1 = f32(tree.n[ch] + vl.get(ch, 0))
-        out[j] = f32(n1 * n1) < f32(f32(f32(k_forced) * tree.prior[0][a]) * S)
+        out[j] = f32(n1 * n1) < puct_ops.forcing_bound(k_forced, tree.prior[0][a], S)
     return out
 
 
@@ -72,9 +73,7 @@ def select(tree, root, m, n, k, c, vl, nodes0, solver, fpu=None, forced=None, lo
         na = np.array([0 if ch is None else tree.n[ch] for ch in kids], np.int64) + va
         wa = np.array([0 if ch is None else tree.w[ch] for ch in kids], np.float32) + (-va.astype(np.float32))
         q = np.where(na > 0, wa / np.maximum(na, 1).astype(np.float32), qu).astype(np.float32)
-        sq = np.sqrt(np.float32(tree.n[v] + vl.get(v, 0)))
-        u = (c * tree.prior[v][legal]) * sq / (1 + na).astype(np.float32)
-        s = (q + u.astype(np.float32)).astype(np.float32)
+        s = puct_ops.score(q, c, tree.prior[v][legal], puct_ops.sqrt(tree.n[v] + vl.get(v, 0)), na)
         a = int(legal[int(np.argmax(s))])  # (the first maximum: ties go to the lowest cell)
         if v == 0 and forced is not None:
             on = forced_cells(tree, legal, kids, vl, solver, forced)
@@ -119,13 +118,13 @@ def forced_selection(fpu, forced, log=None, shunned=None):
 def score(tree, a, j, c):
     """s_a(j) of the root's child through cell a"""
     ch = tree.kids[0][a]
-    q = f32(tree.w[ch]) / f32(tree.n[ch])
-    return f32(q + f32(f32(f32(f32(c) * tree.prior[0][a]) * np.sqrt(f32(tree.n[0]))) / f32(1 + j)))
+    q = np.array([f32(tree.w[ch]) / f32(tree.n[ch])], f32)
+    return puct_ops.score(q, f32(c), tree.prior[0][[a]], puct_ops.sqrt(tree.n[0]), np.array([j], np.int64))[0]
 
 
 def floor_of(tree, a, n1, k_forced):
     """min(n'_a, F_a): F_a the least integer F >= 0 with fl(F * F) >= t_a"""
-    t = f32(f32(f32(k_forced) * tree.prior[0][a]) * f32(tree.n[0] - 1))
+    t = puct_ops.floor_bound(k_forced, tree.prior[0][a], f32(tree.n[0] - 1))
     for F in range(n1):
         if f32(f32(F) * f32(F)) >= t:
             return F

@@ -13,6 +13,7 @@ import functools
 
 import numpy as np
 
+import puct_ops
 import puct_solver_rule as ps
 from playout_rule import has_run
 from search_selfplay_async_keep_rule import AsyncKeepRule
@@ -39,7 +40,7 @@ def untried_q(tree, v, visited_priors, fpu):
     """the q of node v's free cells without a visit; ``fpu`` = (fpu, fpu_root) as float32"""
     qv = np.float32(-np.float32(tree.w[v])) / np.float32(tree.n[v])  # (the stored counts: no virtual visits)
     r = fpu[1] if v == 0 else fpu[0]
-    return np.maximum(np.float32(qv - np.float32(r * mass_of(visited_priors))), np.float32(-1))
+    return np.maximum(puct_ops.fpu_q(qv, r, mass_of(visited_priors)), np.float32(-1))
 
 
 def select(tree, root, m, n, k, c, vl, nodes0, solver, fpu):
@@ -60,9 +61,7 @@ def select(tree, root, m, n, k, c, vl, nodes0, solver, fpu):
         na = np.array([0 if ch is None else tree.n[ch] for ch in kids], np.int64) + va
         wa = np.array([0 if ch is None else tree.w[ch] for ch in kids], np.float32) + (-va.astype(np.float32))
         q = np.where(na > 0, wa / np.maximum(na, 1).astype(np.float32), qu).astype(np.float32)
-        sq = np.sqrt(np.float32(tree.n[v] + vl.get(v, 0)))
-        u = (c * tree.prior[v][legal]) * sq / (1 + na).astype(np.float32)
-        s = (q + u.astype(np.float32)).astype(np.float32)
+        s = puct_ops.score(q, c, tree.prior[v][legal], puct_ops.sqrt(tree.n[v] + vl.get(v, 0)), na)
         a = int(legal[int(np.argmax(s))])  # (the first maximum: ties go to the lowest cell)
         side = d & 1
         pos[side, a] = True

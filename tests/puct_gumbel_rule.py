@@ -9,6 +9,7 @@ header says is f64 is numpy float64.
 """
 import numpy as np
 
+import puct_ops
 from oracle import philox
 from playout_rule import has_run
 from puct_rule import _backup, _canonical, _Tree
@@ -96,9 +97,7 @@ def _walk(tree, root, m, n, k, c, first):
             na = np.array([tree.n[tree.kids[v][a]] if a in tree.kids[v] else 0 for a in legal], np.int64)
             wa = np.array([tree.w[tree.kids[v][a]] if a in tree.kids[v] else 0 for a in legal], np.float32)
             q = np.where(na > 0, wa / np.maximum(na, 1).astype(np.float32), np.float32(0)).astype(np.float32)
-            sq = np.sqrt(np.float32(tree.n[v]))
-            u = (c * tree.prior[v][legal]) * sq / (1 + na).astype(np.float32)
-            a = int(legal[int(np.argmax((q + u.astype(np.float32)).astype(np.float32)))])
+            a = int(legal[int(np.argmax(puct_ops.score(q, c, tree.prior[v][legal], puct_ops.sqrt(tree.n[v]), na)))])
         side = d & 1
         pos[side, a] = True
         d += 1

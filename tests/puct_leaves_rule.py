@@ -16,6 +16,7 @@ slot of their round has as its leaf too) and ``live`` (the root has a legal cell
 """
 import numpy as np
 
+import puct_ops
 from oracle import philox
 from playout_rule import has_run
 from puct_reuse_rule import descend, match, rebase
@@ -35,9 +36,7 @@ def _select_vl(tree, root, m, n, k, c, vl, nodes0):
         na = np.array([0 if ch is None else tree.n[ch] for ch in kids], np.int64) + va
         wa = np.array([0 if ch is None else tree.w[ch] for ch in kids], np.float32) + (-va.astype(np.float32))
         q = np.where(na > 0, wa / np.maximum(na, 1).astype(np.float32), np.float32(0)).astype(np.float32)
-        sq = np.sqrt(np.float32(tree.n[v] + vl.get(v, 0)))
-        u = (c * tree.prior[v][legal]) * sq / (1 + na).astype(np.float32)
-        s = (q + u.astype(np.float32)).astype(np.float32)
+        s = puct_ops.score(q, c, tree.prior[v][legal], puct_ops.sqrt(tree.n[v] + vl.get(v, 0)), na)
         a = int(legal[int(np.argmax(s))])  # (the first maximum: ties go to the lowest cell)
         side = d & 1
         pos[side, a] = True
@@ -116,7 +115,7 @@ class LeavesPuct:
             priors = np.asarray(priors, np.float32).reshape(N * L, C)
             values = np.asarray(values, np.float32).reshape(N * L)
             for i in range(N):
-                for j in range(L):
+                for j in puct_ops.backup_order(L):
                     if paths[i][j] is None:
                         continue
                     if it == 0 and cont[i]:

@@ -12,6 +12,7 @@ float operation is a numpy float32 operation, rounded on its own.
 """
 import numpy as np
 
+import puct_ops
 from oracle import philox
 from playout_rule import has_run
 from tactical_rule import _as_bool
@@ -47,9 +48,7 @@ def _select(tree, root, m, n, k, c):
         na = np.array([tree.n[tree.kids[v][a]] if a in tree.kids[v] else 0 for a in legal], np.int64)
         wa = np.array([tree.w[tree.kids[v][a]] if a in tree.kids[v] else 0 for a in legal], np.float32)
         q = np.where(na > 0, wa / np.maximum(na, 1).astype(np.float32), np.float32(0)).astype(np.float32)
-        sq = np.sqrt(np.float32(tree.n[v]))
-        u = (c * tree.prior[v][legal]) * sq / (1 + na).astype(np.float32)
-        s = (q + u.astype(np.float32)).astype(np.float32)
+        s = puct_ops.score(q, c, tree.prior[v][legal], puct_ops.sqrt(tree.n[v]), na)
         a = int(legal[int(np.argmax(s))])  # (the first maximum: ties go to the lowest cell)
         side = d & 1
         pos[side, a] = True

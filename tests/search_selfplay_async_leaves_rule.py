@@ -15,6 +15,7 @@ a leaf), ``void_by_cap`` (slots from s on), ``ring_wraps`` (records written over
 """
 import numpy as np
 
+import puct_ops
 import puct_solver_rule as ps
 from puct_rule import _canonical
 from search_selfplay_async_opts_rule import AsyncOptsRule, adjusted_counts
@@ -70,7 +71,8 @@ class AsyncLeavesRule(AsyncOptsRule):
                 self.errors.append((ERR_VISITS, i))
             else:
                 full = self.is_full(i)
-                for j, slot in enumerate(self.slots[i]):
+                for j in puct_ops.backup_order(L):
+                    slot = self.slots[i][j]
                     if slot is None:
                         continue
                     path, kind = slot
