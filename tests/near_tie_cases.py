@@ -96,14 +96,14 @@ def run(name, form, evaluator=None, gscore=None, noise=None, today=False, L=None
     dict(obs, out = (actions, visits, root_value, carried, proof), raw = n' or None, policy = the Gumbel root's improved
     policy or None, gscore, leaves = every evaluation's (leaf_obs, leaf_mask)).  ``evaluator``: instead of the case's own;
     ``gscore`` / ``noise``: a kernel's Gumbel scores / noised root priors to search with; ``today``: the dyadic evaluator
-    of tests/test_gpu_puct_reuse.py and the constants of the older tests in the place of the case's; ``L``: leaves per row
+    of tests/puct_reuse_cases.py and the constants of the older tests in the place of the case's; ``L``: leaves per row
     other than the case's; ``table``: (ulps, table seed) other than the case's first"""
     (m, n, k), rows, I, _, _ = BOARDS[name]
     C, L = m * n, L or leaves_of(name, form)
     ev = evaluator or near_np(C, *(table or choice(name, form)))
     C_PUCT, FPU, K_FORCED = (globals()[x] for x in ("C_PUCT", "FPU", "K_FORCED"))
     if today:
-        from test_gpu_puct_reuse import exact_np
+        from puct_reuse_cases import exact_np
 
         ev, (C_PUCT, FPU, K_FORCED) = exact_np(C), TODAY
     obs, seen = rows_of(name), []
@@ -130,7 +130,7 @@ def run(name, form, evaluator=None, gscore=None, noise=None, today=False, L=None
     if form == "gumbel":
         a, visits, value, policy, gs = gumbel_puct(obs, k, I, C_PUCT, ev, CONSIDERED, step=STEP, gscore=gscore, **kw)
         return [dict(act((a, visits, value) + none), policy=policy, gscore=gs)]
-    from test_gpu_puct_reuse import advance  # (that module imports torch)
+    from puct_reuse_cases import advance
 
     distance = {"reuse1": 1, "reuse2": 2}[form]
     rule, acts, resets = ReusePuct(k, I, C_PUCT, ev, None, SEED, ENV_ID0, leaves=seen), [], np.zeros(rows, np.int64)

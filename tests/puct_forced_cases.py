@@ -195,7 +195,7 @@ def reuse_rule(L, solver, seen=None):
 @functools.lru_cache(maxsize=None)
 def reuse_reference(L, solver):
     """per act: (obs, the act's outputs, its evaluations' leaves, raw_visits, the root's n_0 of every row)"""
-    from test_gpu_puct_reuse import advance
+    from puct_reuse_cases import advance
 
     (m, n, k), _, _, _ = BOARDS[REUSE_NAME]
     seen = []

@@ -7,8 +7,8 @@ import functools
 import numpy as np
 
 from puct_leaves_rule import LeavesPuct
+from puct_reuse_cases import exact_np
 from tactical_rule import random_positions
-from test_gpu_puct_reuse import exact_np
 
 C_PUCT, SEED, ENV_ID0 = 1.25, 43, 7
 #        name      board        rows  I     the L of the case

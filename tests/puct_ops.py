@@ -1,8 +1,7 @@
 """The float operations of the PUCT rules that include/mnk_hip.h pins down to the single rounding, each written once
-(test helper).  The rules (tests/puct_rule.py, puct_leaves_rule.py, puct_solver_rule.py, puct_fpu_rule.py,
-puct_forced_rule.py, puct_gumbel_rule.py) call them as ``puct_ops.NAME``, so that a test can put a defect a kernel could
-have in the place of one of them (tests/test_near_tie_cpu.py) and see whether its inputs notice.  Every operation is a
-numpy float32 operation, rounded on its own."""
+(test helper).  The rules (tests/puct_rule.py, puct_search_rule.py, puct_gumbel_rule.py) call them as ``puct_ops.NAME``,
+so that a test can put a defect a kernel could have in the place of one of them (tests/test_near_tie_cpu.py) and see
+whether its inputs notice.  Every operation is a numpy float32 operation, rounded on its own."""
 import numpy as np
 
 f32 = np.float32

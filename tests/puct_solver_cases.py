@@ -7,9 +7,9 @@ import numpy as np
 
 from playout_rule import has_run
 from player_cases import board
+from puct_reuse_cases import advance, exact_np
 from puct_solver_rule import SolverPuct
 from tactical_rule import random_positions, tactical_sets
-from test_gpu_puct_reuse import advance, exact_np
 
 C_PUCT, SEED, ENV_ID0 = 1.25, 47, 3
 #        name      board        rows  I

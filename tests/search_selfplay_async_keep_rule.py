@@ -3,24 +3,23 @@ is stated in include/mnk_hip.h, mnk_search_selfplay_advance_keep).
 
 ``AsyncKeepRule`` is an ``AsyncOptsRule`` with ``keep_tree`` and ``tree_nodes``.  With ``keep_tree`` off it is that rule
 line for line.  With it, the end of a ply carries the subtree of the root's child through the move
-(``puct_reuse_rule.rebase`` through ``puct_solver_rule._rebase``, which keeps the proofs; the child is what
-``puct_reuse_rule.descend`` finds for the one-ply path) when the game goes on, and the budget of a ply counts the
+(``puct_search_rule.rebase``, which keeps the proofs; the child is what
+``puct_search_rule.descend`` finds for the one-ply path) when the game goes on, and the budget of a ply counts the
 iterations above the visits the root was carried with.  ``carried`` (int32 [N, 2]) is the entry point's; ``trace`` lists,
 for every ply that ended, (row, ply, full, kept, carried n, the kept child's proof before the carry, keep_nodes, the proof
 the new root kept): kept = 0 for a row that then started fresh.
 """
 import numpy as np
 
-import puct_solver_rule as ps
-from puct_reuse_rule import descend
+import puct_search_rule as ps
 from puct_rule import _canonical
-from search_selfplay_async_opts_rule import AsyncOptsRule, adjusted_counts
+from search_selfplay_async_opts_rule import AsyncOptsRule
 from search_selfplay_rule import ERR_VISITS
 
 
 class AsyncKeepRule(AsyncOptsRule):
     def __init__(self, m, n, k, N, T, full, fast, threshold, c, temp_plies, seed, env_id0=0, root_noise=None,
-                 noise_on_fast=False, solver=False, keep_tree=False, tree_nodes=None):
+                 noise_on_fast=False, solver=False, keep_tree=False, tree_nodes=None, fpu=None, forced=None):
         if not keep_tree:
             assert tree_nodes is None
             tree_nodes = full + 1
@@ -31,7 +30,7 @@ class AsyncKeepRule(AsyncOptsRule):
         self.carried = np.zeros((N, 2), np.int32)
         self.trace = []
         super().__init__(m, n, k, N, T, full, fast, threshold, c, temp_plies, seed, env_id0, root_noise, noise_on_fast,
-                         solver)
+                         solver, fpu, forced)
 
     def begin(self):
         self.renew = [False] * self.N  # the pending evaluation is a carried root's: it only renews the root's priors
@@ -46,11 +45,11 @@ class AsyncKeepRule(AsyncOptsRule):
     def _carry(self, i, a):
         """the row's tree becomes the subtree of its root's child through cell a: False when there is none to keep"""
         tree = self.trees[i]
-        v = descend(tree, [a])
+        v = ps.descend(tree, [a])
         if v is None:
             return False
         proof = tree.proof[v]
-        new = ps._rebase(tree, v, self.keep_nodes)
+        new, _ = ps.rebase(tree, v, self.keep_nodes)
         if self.solver and proof and len(new.n) > 1:
             kids = [new.proof[ch] for ch in new.kids[0].values()]
             # the proof it had as a child, when the kept children still justify it: it plays in the launch that renews it
@@ -90,22 +89,17 @@ class AsyncKeepRule(AsyncOptsRule):
                     if self.renew[i]:
                         tree.prior[0] = np.asarray(prior, np.float32).copy()  # the priors again: no visit, no value
                     else:
-                        ps._backup(tree, root, self.paths[i], self.kinds[i], prior, values[i], self.solver)
+                        ps.backup(tree, root, self.paths[i], self.kinds[i], prior, values[i], self.solver)
                     self.pending[i] = self.renew[i] = False
                 budget = self.full if full else self.fast
                 proven = self.solver and tree.proof[0] != 0
                 it = max(int(tree.n[0]) - max(int(self.carried[i, 1]), 1), 0)  # the iterations of this ply
                 if it < budget and not proven:
                     assert len(tree.n) <= self.tree_nodes - 1
-                    self.paths[i], pos, d, self.kinds[i] = ps._select(tree, root, m, n, self.k, self.c, {}, len(tree.n),
-                                                                      self.solver)
+                    self.paths[i], pos, d, self.kinds[i] = self._walk(i, {}, len(tree.n))
                     self.pending[i] = True
                 else:
-                    visits, kinds = np.zeros(C, np.int64), np.zeros(C, np.int64)
-                    for a, ch in tree.kids[0].items():
-                        visits[a], kinds[a] = tree.n[ch], tree.proof[ch]
-                    if self.solver:
-                        visits = adjusted_counts(visits, kinds)
+                    visits, _ = ps.root_counts(tree, C, self.solver)
                     if proven:
                         self.proven_plies.append((i, int(self.row_plies[i]), root.copy(), tree.proof[0], it < budget))
                     before, p = self.boards[i].copy(), int(self.row_plies[i])

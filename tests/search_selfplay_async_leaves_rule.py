@@ -3,9 +3,9 @@ rule is stated in include/mnk_hip.h, mnk_search_selfplay_advance_leaves).
 
 ``AsyncLeavesRule`` is an ``AsyncOptsRule`` whose rows hold L slots -- per row a list of (path, kind) or None for a void
 slot -- and a counter of the simulations the row's current ply has been offered (``row_sims``).  A launch backs the row's
-pending slots up in slot order (``puct_solver_rule._backup``), then either ends the ply (the counter has reached the ply's
+pending slots up in slot order (``puct_search_rule.backup``), then either ends the ply (the counter has reached the ply's
 budget, or the root is proven) or lets ``s = min(L, budget - row_sims)`` slots select one after the other under the virtual
-visits of the slots before them (``puct_solver_rule._select`` with the round's ``vl`` and ``nodes0``, as ``SolverPuct.act``
+visits of the slots before them (``puct_search_rule.select`` with the round's ``vl`` and ``nodes0``, as ``PuctSearch.act``
 uses them); the slots from s on are void.  Slot j of row i is batch row ``i * L + j``.
 
 ``advance(priors [N * L, C], values [N * L], root_priors=None) -> (leaf_obs [N * L, 2, m, n], leaf_mask [N * L, C], fresh
@@ -16,22 +16,22 @@ a leaf), ``void_by_cap`` (slots from s on), ``ring_wraps`` (records written over
 import numpy as np
 
 import puct_ops
-import puct_solver_rule as ps
+import puct_search_rule as ps
 from puct_rule import _canonical
-from search_selfplay_async_opts_rule import AsyncOptsRule, adjusted_counts
+from search_selfplay_async_opts_rule import AsyncOptsRule
 from search_selfplay_rule import ERR_VISITS
 
 
 class AsyncLeavesRule(AsyncOptsRule):
     def __init__(self, m, n, k, N, T, full, fast, threshold, c, temp_plies, seed, env_id0=0, root_noise=None,
-                 noise_on_fast=False, solver=False, leaves=1):
+                 noise_on_fast=False, solver=False, leaves=1, fpu=None, forced=None):
         assert 1 <= leaves <= 16 and full % leaves == 0
         self.L = leaves
         self.void_by_walk = 0
         self.void_by_cap = 0
         self.ring_wraps = 0
         super().__init__(m, n, k, N, T, full, fast, threshold, c, temp_plies, seed, env_id0, root_noise, noise_on_fast,
-                         solver)
+                         solver, fpu, forced)
 
     def begin(self):
         """every row's search starts afresh: slot 0 is the root, the others are void and show it"""
@@ -79,7 +79,7 @@ class AsyncLeavesRule(AsyncOptsRule):
                     prior = priors[i * L + j]
                     if j == 0 and len(path) == 1:  # evaluation 0: the pending leaf is the root of a fresh tree
                         prior = self._root_priors(i, prior, full, root_priors)
-                    ps._backup(tree, root, path, kind, prior, values[i * L + j], self.solver)
+                    ps.backup(tree, root, path, kind, prior, values[i * L + j], self.solver)
                     self.slots[i][j] = None
                 budget = self.full if full else self.fast
                 proven = self.solver and tree.proof[0] != 0
@@ -90,7 +90,7 @@ class AsyncLeavesRule(AsyncOptsRule):
                     for j in range(s):
                         got = None
                         if open_ and len(tree.n) <= self.full:
-                            got = ps._select(tree, root, m, n, self.k, self.c, vl, nodes0, self.solver)
+                            got = self._walk(i, vl, nodes0)
                         if got is None:
                             open_ = False
                             self.void_by_walk += 1
@@ -108,11 +108,7 @@ class AsyncLeavesRule(AsyncOptsRule):
                         self.row_sims[i] += s
                     self.slots[i] = slots
                 else:
-                    visits, kinds = np.zeros(C, np.int64), np.zeros(C, np.int64)
-                    for a, ch in tree.kids[0].items():
-                        visits[a], kinds[a] = tree.n[ch], tree.proof[ch]
-                    if self.solver:
-                        visits = adjusted_counts(visits, kinds)
+                    visits, _ = ps.root_counts(tree, C, self.solver)
                     if proven:
                         self.proven_plies.append((i, int(self.row_plies[i]), root.copy(), tree.proof[0],
                                                   self.row_sims[i] < budget))

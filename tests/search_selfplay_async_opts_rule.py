@@ -1,9 +1,10 @@
 """numpy restatement of search self-play with per-row budgets and its two options, root noise and the solver (test
 helper; the rule is stated in include/mnk_hip.h, mnk_search_selfplay_advance_opts).
 
-``AsyncOptsRule`` is an ``AsyncSelfPlayRule`` whose trees carry proofs (``puct_solver_rule``: its backup, its selection,
-and ``decided`` inside the backup) and whose roots take ``puct_noise_rule.root_noise`` at step = the row's ply count.  With
-both options off it plays what ``AsyncSelfPlayRule`` plays.
+``AsyncOptsRule`` is an ``AsyncSelfPlayRule`` whose trees carry proofs (``puct_search_rule``: its backup, its selection
+with ``solver``, ``fpu`` and ``forced`` as arguments -- a ply FORCES iff it is full or ``noise_on_fast`` is set --, and
+``decided`` inside the backup) and whose roots take ``puct_noise_rule.root_noise`` at step = the row's ply count.  With
+every option off it plays what ``AsyncSelfPlayRule`` plays.  ``picks`` and ``shunned`` are the selection's records.
 
 ``advance(priors, values, root_priors=None)``: ``root_priors`` (float32 [N, C]) optionally hands in the priors the kernel
 stored on the roots; the rows that back up a root's evaluation in this launch then store those instead of the rule's own,
@@ -12,24 +13,18 @@ is kept in ``root_wanted`` ({row: (noised, float32 [C])} of the last launch) to 
 """
 import numpy as np
 
-import puct_solver_rule as ps
+import puct_search_rule as ps
 from puct_noise_rule import root_noise
 from puct_rule import _canonical
 from search_selfplay_async_rule import AsyncSelfPlayRule
 from search_selfplay_rule import ERR_VISITS
 
 
-def adjusted_counts(visits, kinds):
-    """the root children's visits (int64 [C]; ``kinds``: their proofs) as mnk_puct_step_solver adjusts them: only the WIN
-    children's when there is one, else all but the LOSS children's; the raw ones when that leaves nothing"""
-    adjusted = np.where(kinds == ps.WIN, visits, 0) if (kinds == ps.WIN).any() else np.where(kinds == ps.LOSS, 0, visits)
-    return adjusted if adjusted.any() else visits
-
-
 class AsyncOptsRule(AsyncSelfPlayRule):
     def __init__(self, m, n, k, N, T, full, fast, threshold, c, temp_plies, seed, env_id0=0, root_noise=None,
-                 noise_on_fast=False, solver=False):
+                 noise_on_fast=False, solver=False, fpu=None, forced=None):
         self.root_noise, self.noise_on_fast, self.solver = root_noise, noise_on_fast, solver
+        self.fpu, self.forced, self.picks, self.shunned = ps.as_pair(fpu), forced, [], []
         self.noised_roots = 0  # roots backed up with noise / without (the counters are the helper's own)
         self.plain_roots = 0
         self.proven_plies = []  # (row, ply, root bool [2, C], the root's proof, ended before its budget) of proven roots
@@ -42,8 +37,18 @@ class AsyncOptsRule(AsyncSelfPlayRule):
 
     def _fresh(self, i):
         super()._fresh(i)
-        self.trees[i] = ps._ProofTree()  # (no proof on the root)
+        self.trees[i] = ps.Tree()  # (no proof on the root)
         self.kinds[i] = 0
+
+    def forces(self, i):
+        """whether row i's current ply forces"""
+        return self.forced is not None and (self.is_full(i) or self.noise_on_fast)
+
+    def _walk(self, i, vl, nodes0):
+        """``select`` on row i's tree with the row's options"""
+        return ps.select(self.trees[i], self.roots[i], self.m, self.n, self.k, self.c, vl, nodes0, solver=self.solver,
+                         fpu=self.fpu, forced=self.forced if self.forces(i) else None, log=self.picks,
+                         shunned=self.shunned)
 
     def _root_priors(self, i, prior, full, given):
         """what the root of row i stores at the backup of its evaluation"""
@@ -79,20 +84,15 @@ class AsyncOptsRule(AsyncSelfPlayRule):
                     prior = priors[i]
                     if len(self.paths[i]) == 1:  # evaluation 0: the pending leaf is the root of a fresh tree
                         prior = self._root_priors(i, prior, full, root_priors)
-                    ps._backup(tree, root, self.paths[i], self.kinds[i], prior, values[i], self.solver)
+                    ps.backup(tree, root, self.paths[i], self.kinds[i], prior, values[i], self.solver)
                     self.pending[i] = False
                 budget = self.full if full else self.fast
                 proven = self.solver and tree.proof[0] != 0
                 if tree.n[0] - 1 < budget and not proven:
-                    self.paths[i], pos, d, self.kinds[i] = ps._select(tree, root, m, n, self.k, self.c, {}, len(tree.n),
-                                                                      self.solver)
+                    self.paths[i], pos, d, self.kinds[i] = self._walk(i, {}, len(tree.n))
                     self.pending[i] = True
                 else:
-                    visits, kinds = np.zeros(C, np.int64), np.zeros(C, np.int64)
-                    for a, ch in tree.kids[0].items():
-                        visits[a], kinds[a] = tree.n[ch], tree.proof[ch]
-                    if self.solver:
-                        visits = adjusted_counts(visits, kinds)
+                    visits, _ = ps.root_counts(tree, C, self.solver)
                     if proven:
                         self.proven_plies.append((i, int(self.row_plies[i]), root.copy(), tree.proof[0],
                                                   tree.n[0] - 1 < budget))

@@ -10,6 +10,7 @@ import torch.nn as nn
 
 from player_cases import DEV, _score, hip, positions  # noqa: F401 (hip: the fixture)
 from puct_rule import puct
+from search_selfplay_async_rule import exact_np  # (the table and the value of ``exact_torch`` below, in numpy)
 
 pytestmark = pytest.mark.gpu
 DTYPES = (torch.float32, torch.bfloat16, torch.uint8)
@@ -18,17 +19,6 @@ DTYPES = (torch.float32, torch.bfloat16, torch.uint8)
 def prior_table(C):
     """a per-cell table of dyadic f32 values (exact in bfloat16 too)"""
     return ((np.arange(C) * 37) % 16 + 1).astype(np.float32) / 16
-
-
-def exact_np(C):
-    table = prior_table(C)
-
-    def evaluate(leaf_obs, leaf_mask):
-        cnt = leaf_obs.reshape(len(leaf_obs), 2, -1).sum(axis=2)
-        v = (np.mod(cnt[:, 0] - 2 * cnt[:, 1], 5) - 2) / 4
-        return leaf_mask * table, v.astype(np.float32)
-
-    return evaluate
 
 
 def exact_torch(C, out_dtype=torch.float32, record=None):

@@ -10,10 +10,9 @@ import pytest
 import torch
 
 from player_cases import DEV, _score, hip  # noqa: F401 (hip: the fixture)
-from playout_rule import has_run
+from puct_reuse_cases import advance, exact_np, place, prior_table, start, value_weights  # noqa: F401
 from puct_reuse_rule import ReusePuct
 from search_selfplay_rule import SelfPlayRule
-from tactical_rule import random_positions
 
 pytestmark = pytest.mark.gpu
 C_PUCT, SEED, ENV_ID0 = 1.25, 41, 5
@@ -25,33 +24,6 @@ BOARDS = [((3, 3, 3), 6, 10),    # NW = 1; games end inside the sequence
           ((7, 9, 7), 5, 24),    # generic
           ((17, 17, 5), 3, 8),   # generic, ten words: the sixteen-word instantiation
           ((25, 25, 5), 3, 8)]   # generic, 21 words: the 32-word instantiation
-
-
-def prior_table(C, mult=1):
-    """a per-cell table of powers of two (exact in bfloat16 too), peaked on the lowest cells (``mult`` = 1): trees narrow
-    enough for a child to own a subtree worth carrying, and in which the second mover's lowest free cell was searched"""
-    a = (np.arange(C) * mult) % C
-    return (2.0 ** -(np.minimum(a // 4, 7) + 1 + max(int(np.ceil(np.log2(C))) - 4, 0))).astype(np.float32)
-
-
-def value_weights(C):
-    return (np.arange(C) % 7 + 1).astype(np.float32)
-
-
-def exact_np(C, J=None):
-    """a deterministic function of the leaf: the table on its legal cells, a value k / 8 from a weighted stone difference;
-    with ``J``, every call 0 (mod J + 1) -- the roots' -- answers with another table"""
-    tables, weights = (prior_table(C), prior_table(C, 11)), value_weights(C)
-    calls = [0]
-
-    def evaluate(leaf_obs, leaf_mask):
-        table = tables[1 if J is not None and calls[0] % (J + 1) == 0 else 0]
-        calls[0] += 1
-        o = leaf_obs.reshape(len(leaf_obs), 2, -1)
-        s = ((o[:, 0] - o[:, 1]) * weights).sum(axis=1)
-        return leaf_mask * table, ((np.mod(s, 9) - 4) / 8).astype(np.float32)
-
-    return evaluate
 
 
 def exact_torch(C, out_dtype=torch.float32, record=None, J=None):
@@ -103,39 +75,6 @@ def same_leaves(rec, leaves, what):
     assert len(rec) == len(leaves), what
     for e, ((lo, lm), (wo, wm)) in enumerate(zip(rec, leaves)):
         assert np.array_equal(lo, wo) and np.array_equal(lm, wm), (what, "evaluation", e)
-
-
-def start(m, n, k, rows, seed):
-    """the rows a sequence starts on: an empty board, then positions a few stones in"""
-    obs = random_positions(m, n, k, rows, np.random.default_rng(seed), max_fill=0.25)
-    obs[0] = 0
-    return obs
-
-
-def place(obs, i, cell, k):
-    """row i's side to move plays ``cell``; the row as its next side to move sees it, or an empty board when that ended
-    the game.  Returns whether it did."""
-    _, m, n = obs[i].shape
-    me = obs[i, 0].reshape(-1).copy()
-    assert me[cell] == 0 and obs[i, 1].reshape(-1)[cell] == 0
-    me[cell] = 1
-    other = obs[i, 1].copy()
-    ended = bool(has_run(me.reshape(1, m, n) != 0, k)[0]) or bool((me + other.reshape(-1)).all())
-    obs[i, 0], obs[i, 1] = (0, 0) if ended else (other, me.reshape(m, n))
-    return ended
-
-
-def advance(obs, actions, k, distance, resets):
-    """the next roots: every row's action played and, with ``distance`` 2, the lowest free cell by a second mover;
-    ``resets[i]`` counts the games of row i that ended"""
-    obs = obs.copy()
-    for i in range(len(obs)):
-        ended = place(obs, i, int(actions[i]), k)
-        if not ended and distance == 2:
-            free = np.flatnonzero((obs[i, 0] + obs[i, 1]).reshape(-1) == 0)
-            ended = place(obs, i, int(free[0]), k)
-        resets[i] += ended
-    return obs
 
 
 def run_sequence(hip, board, rows, J, plies, distance, tree_nodes=None, dtype=torch.float32, leaf_dtype=torch.float32,

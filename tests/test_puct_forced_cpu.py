@@ -11,7 +11,7 @@ import numpy as np
 import pytest
 
 import puct_forced_cases as cases
-import puct_solver_rule as ps
+import puct_search_rule as ps
 from player_cases import HEADER, check_header_and_binding, lib  # noqa: F401 (lib: the fixture)
 from puct_forced_rule import floor_of, prune, root_counts, score
 from puct_fpu_rule import FpuPuct
@@ -242,7 +242,7 @@ def test_the_lockstep_cases_together_show_the_single_visit_cut_and_a_tied_maximu
 
 def test_the_single_visit_cut_and_the_tie_on_a_tree_by_hand():
     """root n_0 = 9, c = 1, k = 2: cells 0 and 1 tied on 3 visits (c* = 0, the lowest), cell 2 forced to 2 visits"""
-    tree = ps._ProofTree()
+    tree = ps.Tree()
     tree.n[0], tree.w[0] = 9, np.float32(0)
     tree.prior[0] = np.array([0.25, 0.25, 0.25, 0.0], np.float32)
     for a, (n, w) in enumerate([(3, 0.75), (3, 0.75), (2, -2.0), (1, 0.5)]):
@@ -276,8 +276,6 @@ def test_the_edge_cases_have_a_prior_above_one_and_a_visited_cell_of_prior_zero(
 @pytest.mark.parametrize("name", cases.FLOOR_NAMES)
 def test_the_floor_cases_tell_n0_less_one_from_n0(name, monkeypatch):
     """the floor's t from n_0 in the place of n_0 - 1, planted in the rule: other pruned counts on both large boards"""
-    import puct_forced_rule
-
     _, want, _, rule = cases.floor_reference(name)
     assert (rule.raw_visits != want[1]).any()
 
@@ -285,7 +283,7 @@ def test_the_floor_cases_tell_n0_less_one_from_n0(name, monkeypatch):
         t = np.float32(np.float32(np.float32(k_forced) * tree.prior[0][a]) * np.float32(tree.n[0]))
         return next((F for F in range(n1) if np.float32(np.float32(F) * np.float32(F)) >= t), n1)
 
-    monkeypatch.setattr(puct_forced_rule, "floor_of", planted)
+    monkeypatch.setattr(ps, "floor_of", planted)
     got = cases.floor_rule(name).act(cases.rows_of(name), step=2)
     rows = int((got[1] != want[1]).any(axis=1).sum())
     print(name, "rows whose pruned counts differ", rows)

@@ -133,7 +133,7 @@ def test_the_classes_check_fpu_before_touching_the_gpu(lib):
 @pytest.mark.parametrize("name,L,solver", [("3x3x3", 1, True), ("5x5x4", 4, False), ("9x9x5", 4, True)])
 def test_without_fpu_the_rule_is_the_rule_it_is_built_on(name, L, solver):
     from puct_solver_rule import SolverPuct
-    from test_gpu_puct_reuse import exact_np
+    from puct_reuse_cases import exact_np
 
     (m, n, k), _, I = CASES[name]
     obs, seen_a, seen_b = positions(name), [], []
@@ -182,7 +182,7 @@ def test_fpu_zero_is_not_fpu_none():
     tree.n[0], tree.w[0] = 4, np.float32(-1.5)  # the root's mean value for its side to move: +3/8
     assert untried_q(tree, 0, np.array([0.5, 0.25], np.float32), as_pair(0)) == np.float32(0.375)
     (m, n, k), _, I = CASES["9x9x5"]
-    from test_gpu_puct_reuse import exact_np
+    from puct_reuse_cases import exact_np
 
     obs = positions("9x9x5")[:5]
     a = FpuPuct(k, I, C_PUCT, exact_np(m * n), 1, seed=SEED, fpu=0).act(obs, step=2)

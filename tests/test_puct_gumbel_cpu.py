@@ -233,7 +233,7 @@ def test_with_exact_values_the_move_and_the_policy_find_the_one_winning_move():
 # ----------------------------------------------------------------------------- 5. the improved policy is a distribution
 @pytest.mark.parametrize("board,I,cons", [((3, 3, 3), 8, 4), ((4, 6, 3), 16, 8)])
 def test_the_policy_sums_to_one_over_the_free_cells(board, I, cons):
-    from test_gpu_puct_reuse import exact_np
+    from puct_reuse_cases import exact_np
 
     m, n, k = board
     obs = random_positions(m, n, k, 12, np.random.default_rng(9), max_fill=0.9)

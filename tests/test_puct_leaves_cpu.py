@@ -10,8 +10,8 @@ import pytest
 from player_cases import HEADER, check_header_and_binding, header_constants, lib, positions  # noqa: F401 (lib: the fixture)
 from puct_leaves_cases import CASES, PARAMS, reference
 from puct_leaves_rule import LeavesPuct, puct_leaves
+from puct_reuse_cases import exact_np
 from puct_rule import puct
-from test_gpu_puct_reuse import exact_np
 
 
 # ----------------------------------------------------------------------------- the rule

@@ -10,15 +10,15 @@ from player_cases import check_header_and_binding, header_constants, lib  # noqa
 from playout_rule import has_run
 from puct_leaves_cases import CASES as LEAVES_CASES
 from puct_leaves_cases import reference as leaves_reference
+from puct_reuse_cases import advance, exact_np, start
 from puct_reuse_rule import ReusePuct
 from puct_rule import puct
-import puct_solver_rule
+import puct_search_rule
 from puct_solver_cases import (C_PUCT, CASES, ENV_ID0, LARGE, LEAVES, MISLED_BOARD, MISLED_FAR, MISLED_I, MISLED_OBS,
                                MISLED_WIN, REUSE_CASES, SEED, SIBLINGS, last_row_win, misled_reference, positions,
                                reference, reuse_reference)
 from puct_solver_rule import PROOF_UNKNOWN, SolverPuct, negamax, puct_solver, value_after
 from tactical_rule import random_positions, tactical_sets
-from test_gpu_puct_reuse import advance, exact_np, start
 
 
 def same(got, want, what):
@@ -189,23 +189,25 @@ STUCK = 4  # in the planted rule's trees: a full board that it did not call draw
 
 
 def plant(monkeypatch, vm, vn):
-    """``puct_solver_rule`` as a kernel that took the variant's own board for the board would search: a new node is
-    terminal when its mover has a run in the first ``vm`` rows or ``vm * vn`` stones lie on the board.  A full board
-    that is then not terminal has no cell to go on to: the walk ends there every time, the node is evaluated again and
-    its proof stays unknown (marked STUCK in the tree for ``_select`` to stop at, read as unknown by ``decided``)."""
-    select, decided = puct_solver_rule._select, puct_solver_rule.decided
+    """``puct_search_rule`` as a kernel that took the variant's own board for the board would search, through the rule's
+    patch point (``terminal`` and ``decided``): a new node is terminal when its mover has a run in the first ``vm`` rows
+    or ``vm * vn`` stones lie on the board.  A full board that is then not terminal has no cell to go on to: the walk
+    ends there every time, the node is evaluated again and its proof stays unknown (marked STUCK in the tree for
+    ``select`` to stop at, read as unknown by ``decided``)."""
+    select, decided = puct_search_rule.select, puct_search_rule.decided
 
-    def planted_select(tree, root, m, n, k, c, vl, nodes0, solver):
+    def planted_terminal(pos, side, m, n, k):
+        won = bool(has_run(pos[side].reshape(1, m, n)[:, :vm], k)[0])
+        return 1 if won else (2 if (pos[0] | pos[1]).sum() >= vm * vn else 0)
+
+    def planted_select(tree, root, *args, **kw):
         before = len(tree.n)
-        got = select(tree, root, m, n, k, c, vl, nodes0, solver)
+        got = select(tree, root, *args, **kw)
         if got is None:
             return got
         path, pos, d, kind = got
-        if len(tree.n) > before:
-            won = bool(has_run(pos[(d - 1) & 1].reshape(1, m, n)[:, :vm], k)[0])
-            kind = 1 if won else (2 if (pos[0] | pos[1]).sum() >= vm * vn else 0)
-            tree.term[path[-1]] = kind
-            tree.proof[path[-1]] = kind or (STUCK if (pos[0] | pos[1]).all() else 0)
+        if len(tree.n) > before and not kind and (pos[0] | pos[1]).all():
+            tree.proof[path[-1]] = STUCK
         return path, pos, d, 0 if kind == STUCK else kind
 
     def planted_decided(tree, x, occupied):
@@ -216,8 +218,9 @@ def plant(monkeypatch, vm, vn):
         finally:
             tree.proof = kept
 
-    monkeypatch.setattr(puct_solver_rule, "_select", planted_select)
-    monkeypatch.setattr(puct_solver_rule, "decided", planted_decided)
+    monkeypatch.setattr(puct_search_rule, "terminal", planted_terminal)
+    monkeypatch.setattr(puct_search_rule, "select", planted_select)
+    monkeypatch.setattr(puct_search_rule, "decided", planted_decided)
 
 
 @pytest.mark.parametrize("L", LEAVES)
